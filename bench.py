@@ -9,13 +9,20 @@ One step = one pass of the hot path over one batch of synthetic input on every r
 Inputs (the uint8 video) are resident in HBM before the timed region.  value = windows all ranks processed
 per second of max-over-ranks step time.  Weak scaling: every rank owns N windows.
 
-TWO encoder precisions are timed, K steps each, and both are in the JSON line:
-  value / ms_per_step / roofline   the CONTRACT-GRADE mode (--precision, default f16x3: split-plane MFMA, scores within
-                                   1e-3 of fp32 encoders on the same frames — what the reference computes in);
-  fast_mode                        the bf16 path (5x faster, scores off by up to 1e-1: outside the contract).
-"precision" holds the deviation of both from fp32 nn.Module encoders measured in this run on the same frames.
+A plain run sets up, warms up, times K steps of the CONTRACT-GRADE mode (--precision, default f16x3: split-plane MFMA,
+scores within 1e-3 of fp32 encoders on the same frames — what the reference computes in) and prints the JSON line:
+  value / ms_per_step / roofline   that leg (roofline from launches sampled inside the timed steps).
+--dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+--full adds everything else the benchmark measures, after the headline leg (each still switched off by its --no-* flag):
+  fast_mode                        the bf16 path timed the same way (5x faster, scores off by up to 1e-1: outside the contract);
+  value_inputs_r03                 the headline leg again on round 3's inputs, a few steps;
+  precision                        the deviation of both modes from fp32 nn.Module encoders on the same frames;
+  nxn_legs / interpolation         the N x N build and SuperSloMo on their own, per kernel;
+  cpu_baseline                     the CPU oracle on a sample of the same workload;
+  train_*                          config 5's training step (8 items, one item eager and as a HIP graph).
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 """
@@ -133,8 +140,9 @@ def build_inputs(args, rank, dev):
     return video, q_mod.eval(), t_mod.eval()
 
 
-def run_mode(args, precision, video, q_mod, t_mod, rank, world, dev):
-    """K timed steps of the hot path with the encoders in `precision` -> result dict (rank 0) / None."""
+def run_mode(args, precision, video, q_mod, t_mod, rank, world, dev, dump=None):
+    """K timed steps of the hot path with the encoders in `precision` -> result dict (rank 0) / None.  dump: a directory that
+    rank 0 writes the last timed step's outputs to (dump_outputs)."""
     from avtex import dist as adist, ops
     import avtex.fused_slowfast as fsf
     import avtex.texture as texture_mod
@@ -164,6 +172,7 @@ def run_mode(args, precision, video, q_mod, t_mod, rank, world, dev):
     sampled_clips = [0, 0]  # clips / batches of the encoder batches whose launches were timed one by one (over all timed steps)
     esz = 2 * (2 if eng.planes else 1)
     sim_last = [None]
+    kept = {} if dump else None  # (the step's outputs, held for dump_outputs)
 
     def step():
         outs = [[], []]
@@ -219,6 +228,8 @@ def run_mode(args, precision, video, q_mod, t_mod, rank, world, dev):
         if args.topk:  # config 4's stitch leg: the k best targets of every row of the rank's block
             sel["topk"] = timer.run("row_topk", lambda: ops.row_topk(sim, args.topk, self_col=q_ids))
         sim_last[0] = sim
+        if kept is not None:
+            kept.update(sel=sel, sim=sim, qn=qn, tn=tn)
         return sel
 
     def sync():
@@ -242,6 +253,8 @@ def run_mode(args, precision, video, q_mod, t_mod, rank, world, dev):
     value = n_total * args.steps / total_s
     if rank != 0:
         return None
+    if dump:
+        dump_outputs(dump, kept)
 
     rows = timer.rows()
     kern = []
@@ -811,10 +824,10 @@ def build_parser():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-precision-block", action="store_true")
     ap.add_argument("--no-nxn-legs", action="store_true")
-    ap.add_argument("--no-train-leg", action="store_true", help="skip the 2-step config-5 training leg of the default run")
+    ap.add_argument("--no-train-leg", action="store_true", help="skip the 6-step config-5 training legs of a --full run")
     ap.add_argument("--train-extra-streams", type=int, default=0,
                     help="(diagnostic) --mode train: create N more HIP streams with work on them before the step's own streams exist")
-    ap.add_argument("--train-leg-idle", type=float, default=0.0, help="(diagnostic) seconds of idle before the config-5 leg of the default run")
+    ap.add_argument("--train-leg-idle", type=float, default=0.0, help="(diagnostic) seconds of idle before the config-5 leg of a --full run")
     ap.add_argument("--no-inputs-r03-leg", "--no-r03-leg", dest="no_inputs_r03_leg", action="store_true", help="skip the short second leg on round 3's inputs (value_inputs_r03)")
     ap.add_argument("--mode", default="synth", choices=["synth", "train"],
                     help="synth: the synthesis hot path (headline); train: BASELINE config 5, contrastive training at size")
@@ -833,11 +846,11 @@ def build_parser():
                     help="--mode train: the target encoder's fast pathway on a side stream (slowfast.PATHWAY_STREAMS; default: the module's)")
     ap.add_argument("--train-items", type=int, default=0,
                     help="--mode train: items of the global batch (0 = 8, BASELINE config 5); 1 = one item = 16 clips per step: the shape "
-                         "every rank of an 8-GPU run of config 5 sees (the default run reports it as train_clips_per_s_one_item)")
+                         "every rank of an 8-GPU run of config 5 sees (a --full run reports it as train_clips_per_s_one_item)")
     ap.add_argument("--train-graph", type=int, default=0, choices=[0, 1],
                     help="--mode train: capture the device side of a step as ONE HIP graph and replay it (train_ops.GraphedStep): for "
                          "steps the host cannot issue as fast as the device runs them (one item per rank); one pass per step, one rank")
-    ap.add_argument("--no-train-one-item-leg", action="store_true", help="skip the one-item config-5 leg of the default run")
+    ap.add_argument("--no-train-one-item-leg", action="store_true", help="skip the one-item config-5 legs of a --full run")
     ap.add_argument("--train-fused-sgd", type=int, default=1, choices=[0, 1], help="--mode train: torch's fused SGD kernel (0: the multi-tensor form)")
     ap.add_argument("--train-pass-items", type=int, default=0,
                     help="--mode train: items per forward/backward pass (0 = all of the rank's items as one batch with per-item "
@@ -869,6 +882,14 @@ def build_parser():
                          "(--trained-steps optimizer steps, ~0.35 s each), as the reference's train-then-evaluate workflow has it")
     ap.add_argument("--trained-steps", type=int, default=300)
     ap.add_argument("--topk", type=int, default=0, help="k of the extra top-k leg in the timed step (0 = none; --config 4 sets 8)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline leg, also run every other measurement: the bf16 fast leg and, on one GPU, the leg on "
+                         "round 3's inputs, the precision block, the N x N and interpolation legs, the CPU baseline and the training "
+                         "legs (each still off with its --no-* flag)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, at most 64 MB; "
+                         "rank 0's rows): the row select's arrays, and the similarity matrix and both normalised embedding tables "
+                         "on a fixed seeded sample of rows")
     return ap
 
 
@@ -918,10 +939,10 @@ def main():
     t_start = time.perf_counter()
     video, q_mod, t_mod = build_inputs(args, rank, dev)
     note("inputs built; timing the %s leg" % args.precision)
-    main_res = run_mode(args, args.precision, video, q_mod, t_mod, rank, world, dev)
+    main_res = run_mode(args, args.precision, video, q_mod, t_mod, rank, world, dev, dump=args.dump_outputs)
     note("contract-grade leg done")
     fast_res = None
-    if not args.no_fast and args.precision != "bf16" and args.encoder == "mfma":
+    if args.full and not args.no_fast and args.precision != "bf16" and args.encoder == "mfma":
         fast_res = run_mode(args, "bf16", video, q_mod, t_mod, rank, world, dev)
         note("fast leg done")
     if rank != 0:
@@ -971,7 +992,7 @@ def main():
     if fast_res is not None:
         out["fast_mode_value"], out["fast_mode_ms_per_step"] = fast_res["value"], fast_res["ms_per_step"]
         detail["fast_mode"] = {"note": "the bf16 encoder path: NOT contract grade (see precision.bf16)", "unit": "clip-windows/s", **fast_res}
-    if world == 1 and args.inputs != "r03" and args.weights == "synthetic" and not args.no_inputs_r03_leg and args.encoder == "mfma":
+    if args.full and world == 1 and args.inputs != "r03" and args.weights == "synthetic" and not args.no_inputs_r03_leg and args.encoder == "mfma":
         # the SAME code on round 3's inputs, a short second leg: a round-over-round delta is then attributable from the line
         # alone (sparser inputs run the same kernels ~5 % faster — the chip holds a higher clock on zero operands)
         a3 = argparse.Namespace(**vars(args))
@@ -983,7 +1004,7 @@ def main():
         del v3, q3, t3
         torch.cuda.empty_cache()
         note("round-3-inputs leg done")
-    if world == 1 and not args.no_precision_block and args.encoder == "mfma":
+    if args.full and world == 1 and not args.no_precision_block and args.encoder == "mfma":
         modes = [args.precision] + (["bf16"] if args.precision != "bf16" else [])
         prec = detail["precision"] = precision_block(args, video, q_mod, t_mod, dev, modes)
         out["precision_max_abs_dscore"] = prec[args.precision]["max_abs_dscore"]
@@ -996,20 +1017,20 @@ def main():
                            "tie_rows_subset_of_fp32_ties": t0_.get("tie_rows_survivors_subset_of_ref_ties"),
                            "max_fp32_gap_on_differing_rows": t0_.get("max_ref_gap_on_differing_rows")}
         note("precision block done")
-    if world == 1 and not args.no_nxn_legs:
+    if args.full and world == 1 and not args.no_nxn_legs:
         detail["nxn_legs"] = nxn_legs(dev)
         detail["interpolation"] = interpolation_leg(dev)
         f32 = [l for l in detail["nxn_legs"] if l["case"].startswith("N=4096 D=2304") and l["sim_mode"] == "f32"]
         if f32:
             out["nxn_build_ms_seeded_th0"] = f32[0]["build_ms_th0.0"]
         note("NxN legs done")
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cb = cpu_baseline(video.cpu(), q_mod, t_mod, 20, 4, N, D, 0.1, args)
         detail["cpu_baseline"] = cb
         out["cpu_baseline"] = {k: cb[k] for k in ("value", "unit", "cores", "kind")}
         out["cpu_baseline"]["sample"] = cb["sample_short"]
         note("CPU baseline done")
-    if world == 1 and not args.no_train_leg:
+    if args.full and world == 1 and not args.no_train_leg:
         del video, q_mod, t_mod
         import gc
 
@@ -1078,6 +1099,41 @@ def emit(out, detail):
     if detail:
         print("[bench-detail] " + json.dumps(detail, default=str), file=sys.stderr, flush=True)
     print(line, flush=True)
+
+
+DUMP_LIMIT = 64 << 20   # bytes of --dump-outputs in all
+DUMP_ROWS = 512         # rows of the similarity matrix and the embedding tables in the dump (a fixed seeded sample)
+
+
+def dump_outputs(path, kept, seed=0):
+    """--dump-outputs DIR: what the last timed step computed, as DIR/<name>.npy, float32 where the device holds fp32 and float64
+    (exact) for indices and counts.  select_{idx,seg,p,cnt,stats} = the row select's dict (ops.row_transition), topk_{idx,val} = the
+    top-k leg's when it ran; sim_rows, q_emb_rows, t_emb_rows = the similarity matrix and the normalised q / t embedding tables on
+    the rows listed in `rows`, a sample drawn from a seeded generator (the select's arrays too when they alone would pass half of
+    DUMP_LIMIT).  Inputs are seeded: two builds run with the same arguments compare array for array."""
+    sel, sim = kept["sel"], kept["sim"]
+    n, n_total = sim.shape
+    per_row = {"select_" + k: sel[k] for k in ("idx", "seg", "p", "cnt", "stats")}
+    if "topk" in sel:
+        per_row["topk_idx"], per_row["topk_val"] = sel["topk"]
+    # half of the budget for the select's arrays (8 bytes an element at most), half for the sampled fp32 rows
+    whole = n * sum(8 * t[0].numel() for t in per_row.values()) <= DUMP_LIMIT // 2
+    n_rows = max(1, min(n, DUMP_ROWS, (DUMP_LIMIT // 2) // (4 * (n_total + 2 * kept["qn"].shape[1]))))
+    rows = np.sort(np.random.default_rng(seed).choice(n, size=n_rows, replace=False))
+    ridx = torch.from_numpy(rows).to(sim.device)
+    arrays = {k: (t if whole else t.index_select(0, ridx)) for k, t in per_row.items()}
+    arrays.update(sim_rows=sim.index_select(0, ridx), q_emb_rows=kept["qn"].index_select(0, ridx),
+                  t_emb_rows=kept["tn"].index_select(0, ridx))
+    out = {"rows": rows.astype(np.float64)}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        out[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_LIMIT, "dump of %d bytes is over %d" % (total, DUMP_LIMIT)
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    print("[bench] %d outputs of the last timed step (%.1f MB) -> %s" % (len(out), total / 2 ** 20, path), file=sys.stderr, flush=True)
 
 
 def self_launch(n):

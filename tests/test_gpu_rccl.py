@@ -17,7 +17,7 @@ def test_bench_under_torchrun_one_rank_rccl(dev):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
            "127.0.0.1", "--master-port", "29517", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--windows", "128",
            "--enc-batch", "64",  # (two batches: the bf16 leg's two encoder streams have something to overlap)
-           "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-precision-block", "--no-nxn-legs", "--no-train-leg"]
+           "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-precision-block", "--no-nxn-legs", "--no-train-leg"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]

@@ -409,6 +409,50 @@ def test_cli_and_bench_usage_text_renders(avt):
     assert a.dist_backend == "nccl" and a.gpus == 1  # RCCL unless asked otherwise
 
 
+def test_bench_plain_run_is_the_headline_leg_alone():
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times the headline leg only; every other leg waits for --full."""
+    bench = _load_bench()
+    a = bench.build_parser().parse_args(["--gpus", "1", "--steps", "3", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 3 and a.warmup == 2
+    a = bench.build_parser().parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    for leg in ("not args.no_fast", "not args.no_inputs_r03_leg", "not args.no_precision_block", "not args.no_nxn_legs",
+                "not args.no_cpu_baseline", "not args.no_train_leg"):
+        line = [l for l in src.splitlines() if leg in l and l.lstrip().startswith("if ")]
+        assert len(line) == 1 and "args.full and" in line[0], (leg, line)
+
+
+def test_bench_dump_outputs_float_arrays_within_the_budget(tmp_path):
+    """--dump-outputs: the last step's select arrays whole (integers as exact float64), the similarity matrix and both embedding
+    tables on a seeded sample of rows, float32 / float64 only, at most 64 MB; the same sample every time."""
+    bench = _load_bench()
+    g = torch.Generator().manual_seed(0)
+    n, n_total, d, cap = 700, 1400, 96, 64
+    sim = torch.randn((n, n_total), generator=g)
+    sel = {"idx": torch.randint(0, n_total, (n, cap), generator=g, dtype=torch.int32),
+           "seg": torch.randint(0, n_total, (n, cap), generator=g, dtype=torch.int32), "p": torch.rand((n, cap), generator=g),
+           "cnt": torch.randint(0, cap, (n,), generator=g, dtype=torch.int32), "stats": torch.rand((n, 4), generator=g),
+           "topk": (torch.randint(0, n_total, (n, 8), generator=g, dtype=torch.int32), torch.rand((n, 8), generator=g))}
+    kept = {"sel": sel, "sim": sim, "qn": torch.randn((n, d), generator=g), "tn": torch.randn((n, d), generator=g)}
+    bench.dump_outputs(str(tmp_path / "a"), kept)
+    bench.dump_outputs(str(tmp_path / "b"), kept)
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(x + ".npy" for x in ("rows", "select_idx", "select_seg", "select_p", "select_cnt", "select_stats",
+                                                "topk_idx", "topk_val", "sim_rows", "q_emb_rows", "t_emb_rows"))
+    got = {x[:-4]: np.load(tmp_path / "a" / x) for x in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    assert sum(v.nbytes for v in got.values()) <= bench.DUMP_LIMIT
+    rows = got["rows"].astype(np.int64)
+    assert len(rows) == bench.DUMP_ROWS and np.all(np.diff(rows) > 0) and rows[-1] < n
+    assert np.array_equal(got["select_idx"], sel["idx"].numpy().astype(np.float64)) and got["select_idx"].dtype == np.float64
+    assert np.array_equal(got["select_p"], sel["p"].numpy()) and got["select_p"].dtype == np.float32
+    assert np.array_equal(got["sim_rows"], sim.numpy()[rows]) and np.array_equal(got["t_emb_rows"], kept["tn"].numpy()[rows])
+    assert np.array_equal(got["topk_val"], sel["topk"][1].numpy())
+    for x in names:
+        assert np.array_equal(np.load(tmp_path / "b" / x), got[x[:-4]])
+
+
 def test_bench_config4_is_one_flag(monkeypatch):
     """`bench.py --config 4` = BASELINE.json's config 4 on one rank: 2048 windows per GPU and the top-k (k = 8) leg."""
     bench = _load_bench()

@@ -1,6 +1,6 @@
 #!/bin/bash
 # On the GPU box, ONE script for everything profiles/rNN/ quotes about the final code (so the files agree with each other):
-#   1. python bench.py                                  -> bench.json (the headline line, both precision legs)
+#   1. python bench.py --full                           -> bench.json (the headline line, both precision legs)
 #   2. rocprofv3 --kernel-trace --stats of the same cmd -> rocprof_kernel_stats.csv (per-kernel time; no PMC in this pass)
 #   3. rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE    -> pmc_fetch_write_summary.json (separate passes, kernel-trace only,
 #      over tools/pmc_kernels.py: every hand-written kernel at the bench shapes; FETCH_SIZE is doubled by the READER
@@ -11,7 +11,7 @@ TAG=${1:-r04}
 OUT=$R/gpurun_out/profile_$TAG
 mkdir -p $OUT
 cd $R
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 cp $R/bench_detail.json $OUT/bench_detail.json
 cd /tmp && export TMPDIR=/tmp
 # the profiled command runs NOTHING but the headline leg (no round-3-inputs leg, no precision block: both launch the same kernel symbols),
