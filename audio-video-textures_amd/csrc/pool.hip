@@ -210,6 +210,68 @@ __global__ __launch_bounds__(256) void maxpool3_x3_kernel(const uint16_t* __rest
   }
 }
 
+// MaxPool3d(3, stride 2, padding 1) over T, H and W: the stem pool of the 3D ResNets (resnet3d.py; the reference's
+// models/video_models/resnet3d.py:157).  One thread owns 8 channels of one output position and walks its 27 taps a frame
+// tap at a time (18 16-byte loads in flight); taps outside the clip are clamped onto the nearest valid one, which a max does
+// not notice, so no tap is ever -inf padding.  HBM-bound: the taps of neighbouring outputs overlap and are served by the caches.
+template <bool F16>
+__global__ __launch_bounds__(256) void maxpool3d_x3_kernel(const uint16_t* __restrict__ in_hi, const uint16_t* __restrict__ in_lo,
+                                                            uint16_t* __restrict__ out_hi, uint16_t* __restrict__ out_lo, int T,
+                                                            int H, int W, int C, int ldi, int ldo, int To, int Ho, int Wo,
+                                                            unsigned total) {
+  const unsigned cpr = (unsigned)C >> 3;
+  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
+    unsigned p = i / cpr;
+    const unsigned cc = i - p * cpr;
+    unsigned q = p / (unsigned)Wo;
+    const int wo = (int)(p - q * Wo);
+    p = q / (unsigned)Ho;
+    const int ho = (int)(q - p * Ho);
+    const unsigned b = p / (unsigned)To;
+    const int to = (int)(p - b * To);
+    const int64_t clip = (int64_t)b * T * H * W;
+    float m[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) m[e] = -INFINITY;
+#pragma unroll 1
+    for (int dt = 0; dt < 3; ++dt) {
+      int ti = 2 * to - 1 + dt;
+      ti = ti < 0 ? 0 : (ti > T - 1 ? T - 1 : ti);
+      uint4 vh[9], vl[9];
+#pragma unroll
+      for (int dh = 0; dh < 3; ++dh) {
+        int hi = 2 * ho - 1 + dh;
+        hi = hi < 0 ? 0 : (hi > H - 1 ? H - 1 : hi);
+#pragma unroll
+        for (int dw = 0; dw < 3; ++dw) {
+          int wi = 2 * wo - 1 + dw;
+          wi = wi < 0 ? 0 : (wi > W - 1 ? W - 1 : wi);
+          const int64_t o = (clip + ((int64_t)ti * H + hi) * W + wi) * ldi + cc * 8;
+          vh[dh * 3 + dw] = *reinterpret_cast<const uint4*>(in_hi + o);
+          vl[dh * 3 + dw] = *reinterpret_cast<const uint4*>(in_lo + o);
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 9; ++k) {
+        const uint32_t* ph = reinterpret_cast<const uint32_t*>(&vh[k]);
+        const uint32_t* pl = reinterpret_cast<const uint32_t*>(&vl[k]);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const avt::f32x2 v = avt::join2<F16>(ph[e], pl[e]);
+          // (x > m ? x : m keeps a NaN of x; fmaxf would drop it)
+          m[2 * e] = (v.x > m[2 * e] || v.x != v.x) ? v.x : m[2 * e];
+          m[2 * e + 1] = (v.y > m[2 * e + 1] || v.y != v.y) ? v.y : m[2 * e + 1];
+        }
+      }
+    }
+    uint4 oh, ol;
+    avt::split8<F16>(m, oh, ol);
+    const int64_t o = (((int64_t)(b * To + to) * Ho + ho) * Wo + wo) * ldo + cc * 8;
+    *reinterpret_cast<uint4*>(out_hi + o) = oh;
+    *reinterpret_cast<uint4*>(out_lo + o) = ol;
+  }
+}
+
 template <bool F16>
 __global__ __launch_bounds__(256) void mean_positions_x3_kernel(const uint16_t* __restrict__ in_hi,
                                                                  const uint16_t* __restrict__ in_lo, int P, int C, int ldi,
@@ -271,6 +333,31 @@ extern "C" int avt_maxpool_hw3s2_ndhwc_x3(const void* in_hi, const void* in_lo, 
   else
     hipLaunchKernelGGL((maxpool3_x3_kernel<false>), dim3(grid), dim3(256), 0, st, ih, il, oh, ol, bt, h, w, c, ldi, ldo, ho, wo, tgroup, frame_idx);
   return avt::check_launch("avt_maxpool_hw3s2_ndhwc_x3");
+}
+
+extern "C" int avt_maxpool3d_k3s2_ndhwc_x3(const void* in_hi, const void* in_lo, void* out_hi, void* out_lo, int batch, int t,
+                                           int h, int w, int c, int ldi, int ldo, int plane_dtype, void* stream) {
+  AVT_REQUIRE(in_hi && in_lo && out_hi && out_lo, "avt_maxpool3d_k3s2_ndhwc_x3: NULL pointer");
+  AVT_REQUIRE(batch > 0 && t > 0 && h > 0 && w > 0 && c > 0 && c % 8 == 0 && ldi % 8 == 0 && ldo % 8 == 0 && ldi >= c && ldo >= c,
+              "avt_maxpool3d_k3s2_ndhwc_x3: channels / leading dimensions must be multiples of 8 and cover the channels");
+  AVT_REQUIRE(avt::aligned16(in_hi) && avt::aligned16(in_lo) && avt::aligned16(out_hi) && avt::aligned16(out_lo),
+              "avt_maxpool3d_k3s2_ndhwc_x3: pointers must be 16-byte aligned");
+  AVT_REQUIRE(plane_dtype == AVT_X3_BF16 || plane_dtype == AVT_X3_F16, "avt_maxpool3d_k3s2_ndhwc_x3: bad plane_dtype");
+  const int to = (t - 1) / 2 + 1, ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
+  const int64_t total = (int64_t)batch * to * ho * wo * (c / 8);
+  AVT_REQUIRE(total < (1ll << 31), "avt_maxpool3d_k3s2_ndhwc_x3: more than 2^31 output chunks");
+  const int64_t blocks = (total + 255) / 256;
+  const unsigned grid = (unsigned)(blocks < 65536 ? blocks : 65536);
+  auto ih = static_cast<const uint16_t*>(in_hi), il = static_cast<const uint16_t*>(in_lo);
+  auto oh = static_cast<uint16_t*>(out_hi), ol = static_cast<uint16_t*>(out_lo);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (plane_dtype == AVT_X3_F16)
+    hipLaunchKernelGGL((maxpool3d_x3_kernel<true>), dim3(grid), dim3(256), 0, st, ih, il, oh, ol, t, h, w, c, ldi, ldo, to, ho, wo,
+                       (unsigned)total);
+  else
+    hipLaunchKernelGGL((maxpool3d_x3_kernel<false>), dim3(grid), dim3(256), 0, st, ih, il, oh, ol, t, h, w, c, ldi, ldo, to, ho, wo,
+                       (unsigned)total);
+  return avt::check_launch("avt_maxpool3d_k3s2_ndhwc_x3");
 }
 
 extern "C" int avt_maxpool_hw2s2_ndhwc_x3(const void* in_hi, const void* in_lo, void* out_hi, void* out_lo, int bt, int h, int w,

@@ -106,7 +106,9 @@ def build_parser():
            "249 +1.3-2 %% more; ~37 GB of activations at 224^2).  Cut to texture.max_enc_batch(img_size) — the kernels' signed "
            "32-bit element offsets allow 267 clips at 224^2, 204 at 256^2; the bf16 path's dense clips 166 at 224^2")
     a("--enc_impl", default="auto", choices=["auto", "mfma", "module"],
-      help="SlowFast at -e: hand-written MFMA convolutions (auto/mfma) or the nn.Module on MIOpen (module)")
+      help="encoders at -e: SlowFast on the hand-written MFMA convolutions (auto/mfma) or the nn.Module on MIOpen (module); "
+           "ResNet3d (resnet10/18/34/50) on the contract-grade MFMA kernels with mfma (fp32 = f16x3, or bf16x3; not bf16), "
+           "the nn.Module with auto / module")
     a("--dump_png", default=False, action="store_true",
       help="also write the reference's per-frame PNG folder (validate.py:789-792); default: frames go to the encoder directly")
     a("--vcam", default=False, action="store_true", help="defined for validate.py:299; CAM dumps are out of scope")

@@ -793,6 +793,13 @@ def maxpool_hw2s2_x3(x_ptrs, out_ptrs, bt, h, w, c, ldi, ldo, plane_dtype):
                                                      int(ldo), int(plane_dtype), _stream()), "avt_maxpool_hw2s2_ndhwc_x3")
 
 
+def maxpool3d_k3s2_x3(x_ptrs, out_ptrs, batch, t, h, w, c, ldi, ldo, plane_dtype):
+    """MaxPool3d(3, 2, 1) over T, H and W on plane pairs (NDHWC rows): the 3D ResNets' stem pool."""
+    _lib.check(_lib.lib().avt_maxpool3d_k3s2_ndhwc_x3(C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]), C.c_void_p(out_ptrs[0]),
+                                                      C.c_void_p(out_ptrs[1]), int(batch), int(t), int(h), int(w), int(c),
+                                                      int(ldi), int(ldo), int(plane_dtype), _stream()), "avt_maxpool3d_k3s2_ndhwc_x3")
+
+
 def mean_positions_x3(x_ptrs, batch, p, c, ldi, out, col0, plane_dtype):
     _dev(out, "out", torch.float32)
     _lib.check(_lib.lib().avt_mean_positions_x3(C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]), int(batch), int(p), int(c),

@@ -84,6 +84,13 @@ def max_enc_batch(img_size, planes=True):
     return max(1, cap)
 
 
+def max_enc_batch_resnet3d(img_size, window):
+    """Largest 3D-ResNet encoder batch the split-plane kernels take (fused_resnet3d.ResNet3dMFMA): the widest tensor of a forward is
+    the stem output [n, W, ceil(hw/2), ceil(hw/2), 64], addressed with signed 32-bit element offsets (133 clips at W = 20, 224^2)."""
+    h2 = -(-int(img_size) // 2)
+    return max(1, ((1 << 31) - 64) // (int(window) * h2 * h2 * 64))
+
+
 class TextureEngine:
     # per-channel statistics of the reference's non-SlowFast transform (validate.py:90-92, dataset.py:50-52)
     GENERIC_MEAN = (0.4345, 0.4051, 0.3775)
@@ -115,6 +122,11 @@ class TextureEngine:
             cap = max_enc_batch(self.hw, self.planes is not None)
             if self.enc_batch > cap:
                 self.enc_batch = cap
+        # 3D-ResNet encoders on the split-plane kernels (fused_resnet3d.ResNet3dMFMA): set_video writes the normalised frames once
+        # as a plane-pair table and embed_windows hands the encoders frame ids only — no clip is gathered per window
+        self.frame_table = not self.slowfast and all(getattr(e, "frame_table_input", False) for e in (q_encoder, t_encoder))
+        if self.frame_table:
+            self.enc_batch = min(self.enc_batch, max_enc_batch_resnet3d(self.hw, self.W))
         self.frames = None
         self.A = self.A_da = self.Ad = None
         self._cache = {"q": {}, "t": {}}
@@ -148,6 +160,9 @@ class TextureEngine:
             sd = torch.tensor(self.GENERIC_STD, device=self.dev).view(1, 3, 1, 1)
             x = ((x - m) / sd).to(self.pack_dtype)
             self._norm_pad = torch.cat([x, torch.zeros_like(x[:1])], 0)  # padding is zero AFTER the transform
+            if self.frame_table:  # ... as NDHWC plane pairs [F+1, hw, hw, 4] (channel 3 zero), one pass over the video
+                hi, lo = ops.clip_planes_f32(self._norm_pad.permute(1, 0, 2, 3).unsqueeze(0), self.q_enc.x3)
+                self._table = (hi[0], lo[0])
         return self.N
 
     def set_audio(self, audio_eg, driving_eg=None, da_encoder=None):
@@ -276,6 +291,12 @@ class TextureEngine:
             with torch.no_grad():
                 for i in range(0, n, self.enc_batch):
                     part = np.asarray(ids[i : i + self.enc_batch], np.int64)
+                    if self.frame_table:
+                        fidx = torch.from_numpy(np.where(part < 0, self.F, part).reshape(-1).astype(np.int32)).to(self.dev)
+                        for k, enc in enumerate(encoders):
+                            outs[k].append(enc.forward_frames(self._table[0], self._table[1], fidx, len(part), self.W))
+                        self.encoded += len(part) * len(encoders)
+                        continue
                     flat = torch.from_numpy(np.where(part < 0, self.F, part).reshape(-1)).to(self.dev)
                     x = self._norm_pad.index_select(0, flat).view(len(part), self.W, 3, self.hw, self.hw)
                     x = x.permute(0, 2, 1, 3, 4).contiguous()  # (B,window,C,H,W) -> (B,C,window,H,W), models.py:332

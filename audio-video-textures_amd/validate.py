@@ -211,14 +211,27 @@ def validate(model, args, video_name="", epoch=None, tb_logger=None, model_type=
         # what the reference computes in: models.py:335, 399) = the contract-grade split-plane kernels (f16x3: scores
         # within 3e-5 of the fp32 nn.Module's on the same frames, tests/test_gpu_x3.py); bf16 = the fast path, which does
         # NOT meet the 1e-3 score contract (off by up to 1e-1) and must be asked for by name.
+        from .fused_resnet3d import ResNet3dMFMA, resnet3d_of
         from .fused_slowfast import SlowFastMFMA
         from .slowfast import SlowFast
 
+        precision = None
         if isinstance(q_enc, SlowFast) and isinstance(t_enc, SlowFast):
             precision = {"fp32": "f16x3", "bf16": "bf16", "bf16x3": "bf16x3", "f16x3": "f16x3"}[enc_dtype]
             print("Encoders: SlowFast on the MFMA kernels, precision {} ({})".format(
                 precision, "fast path, outside the 1e-3 score contract" if precision == "bf16" else "contract grade"))
             q_enc, t_enc = SlowFastMFMA(q_enc, dev, precision=precision), SlowFastMFMA(t_enc, dev, precision=precision)
+        elif impl == "mfma" and resnet3d_of(q_enc) is not None and resnet3d_of(t_enc) is not None:
+            # the 3D ResNets (--enc_arch resnet10/18/34/50) on the split-plane kernels; --enc_impl auto keeps the module for them
+            if enc_dtype == "bf16":
+                raise AvtError("enc_dtype=bf16: the bf16 fast path covers SlowFast encoders only; ResNet3d encoders run on the "
+                               "MFMA kernels in a contract-grade mode (fp32 / f16x3 / bf16x3)")
+            precision = {"fp32": "f16x3", "bf16x3": "bf16x3", "f16x3": "f16x3"}[enc_dtype]
+            print("Encoders: ResNet3d on the MFMA kernels, precision {} (contract grade)".format(precision))
+            q_enc, t_enc = ResNet3dMFMA(q_enc, dev, precision=precision), ResNet3dMFMA(t_enc, dev, precision=precision)
+        elif impl == "mfma":
+            raise AvtError("enc_impl=mfma needs SlowFast or ResNet3d encoders (got {})".format(type(q_enc).__name__))
+        if precision is not None:
             # ... and so does VGGish (audio_models/vggish.py), for the model's audio branch and the driving branch, in the SAME
             # arithmetic as the video encoders: split planes in the contract-grade modes, bf16 in the fast mode
             from .fused_vggish import VGGishMFMA
@@ -228,8 +241,6 @@ def validate(model, args, video_name="", epoch=None, tb_logger=None, model_type=
                 a_enc = VGGishMFMA(a_enc, dev, precision=precision)
             if isinstance(da_model, VGGish):
                 da_model = a_enc if (da_model is own and isinstance(a_enc, VGGishMFMA)) else VGGishMFMA(da_model, dev, precision=precision)
-        elif impl == "mfma":
-            raise AvtError("enc_impl=mfma needs SlowFast encoders (got {})".format(type(q_enc).__name__))
     eng = texture.TextureEngine(q_enc, t_enc, a_enc,
                                 window=W, stride=S, temp=net.temp, img_size=args.img_size,
                                 model_type=net.model_type, device=dev,

@@ -489,6 +489,12 @@ int avt_maxpool_hw2s2_ndhwc_x3(const void* in_hi, const void* in_lo, void* out_h
 int avt_maxpool_hw3s2_ndhwc_x3(const void* in_hi, const void* in_lo, void* out_hi, void* out_lo, int bt, int h,
                                int w, int c, int ldi, int ldo, int tgroup, int plane_dtype, const int32_t* frame_idx,
                                void* stream);
+/* MaxPool3d(3, stride 2, padding 1) over T, H and W on plane pairs: the 3D ResNets' stem pool (resnet3d.py).  in_* [batch, t, h,
+ * w] NDHWC rows of `ldi` elements (the c channels first), out_* [batch, (t-1)/2+1, (h-1)/2+1, (w-1)/2+1] rows of `ldo`.  The max
+ * is taken on hi + lo and split again (value-preserving, NaN propagates); padding never wins, as with -inf padding.  Added
+ * without an ABI bump: a new symbol, no existing entry changed. */
+int avt_maxpool3d_k3s2_ndhwc_x3(const void* in_hi, const void* in_lo, void* out_hi, void* out_lo, int batch, int t, int h,
+                                int w, int c, int ldi, int ldo, int plane_dtype, void* stream);
 int avt_mean_positions_x3(const void* in_hi, const void* in_lo, int batch, int p, int c, int ldi,
                           float* out, int ldo, int plane_dtype, void* stream);
 
