@@ -1,6 +1,6 @@
 """The 3D-ResNet encoders (resnet10/18/34; the reference's default --enc_arch resnet18) on the contract-grade split-plane kernels
 (fused_resnet3d.ResNet3dMFMA): the new 3D max-pool against torch, the whole encoder against the fp32 nn.Module, the engine's
-frame-table path, and validate() dispatch end to end."""
+frame-table path (at the production batch of 133 clips, and over a table above 4 GiB), and validate() dispatch end to end."""
 import os
 import sys
 from types import SimpleNamespace
@@ -175,6 +175,116 @@ def test_frame_table_embed_windows_equals_module(avt, dev, hw, window):
         rel = max(_rel(q, q32), _rel(t, t32))
         ds = (F.normalize(q, dim=1) @ F.normalize(t, dim=1).T - F.normalize(q32, dim=1) @ F.normalize(t32, dim=1).T).abs().max().item() / 0.1
         assert rel <= 1e-4 and ds <= 1e-3, "%s: rel %.3e, max |d score| %.3e" % (list(kw), rel, ds)
+
+
+def _mod_compare(q, t, q32, t32):
+    """(rel embedding error, max |d score|) of q / t against the fp32 module's q32 / t32."""
+    rel = max(_rel(q, q32), _rel(t, t32))
+    ds = (F.normalize(q, dim=1) @ F.normalize(t, dim=1).T - F.normalize(q32, dim=1) @ F.normalize(t32, dim=1).T).abs().max().item() / 0.1
+    return rel, ds
+
+
+@pytest.mark.parametrize("mode", ["f16x3", "bf16x3"])
+def test_production_batch_embeds_like_module(avt, dev, mode):
+    """The default encoder at its production batch: enc_batch 249 is cut to 133 clips at 224^2, W = 20, where layer3's 3x3x3
+    convolutions run on the XL tile and the stem output is just under 2^31 - 64 elements.  140 windows (one full batch + a ragged
+    batch of 7) against the fp32 module on a subset (clips 131 and 132 own the stem rows nearest 2^31), and the same subset
+    re-embedded as one small batch (layer3 on the 128 x 128 tile) agrees with the full batch."""
+    from avtex import ops
+    from avtex.fused_resnet3d import ResNet3dMFMA
+    from avtex.texture import TextureEngine
+    from resnet3d_cases import TOL
+
+    hw, W, S = 224, 20, 4
+    video, q_mod, t_mod = _setup(dev, "resnet18", hw, W, S, 141)
+    eng = TextureEngine(ResNet3dMFMA(q_mod, dev, mode), ResNet3dMFMA(t_mod, dev, mode), None, window=W, stride=S, img_size=hw,
+                        device=dev, enc_batch=249, enc_arch="resnet18")
+    assert eng.frame_table and eng.enc_batch == 133
+    assert 133 * W * (hw // 2) ** 2 * 64 < (1 << 31) - 64 <= 134 * W * (hw // 2) ** 2 * 64
+    plan = dict((n, e) for n, e, _ in eng.q_enc.plan(hw, W))
+    for (c1, c2, _), name in zip(eng.q_enc.blocks[4:6], ("layer3.0", "layer3.1")):
+        m1 = int(np.prod(plan[name]))
+        for fc in (c1, c2):
+            assert ops.conv3d_igemm_x3_xl_picked(fc.cout, fc.wt.shape[1], 133 * m1), name
+            assert not ops.conv3d_igemm_x3_xl_picked(fc.cout, fc.wt.shape[1], 5 * m1), name
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated(dev)
+    torch.cuda.reset_peak_memory_stats(dev)
+    assert eng.set_video(video) == 140
+    starts = np.arange(140) * S
+    q, t = eng.embed_windows([eng.q_enc, eng.t_enc], starts=starts)
+    torch.cuda.synchronize()
+    peak = torch.cuda.max_memory_allocated(dev)
+    assert q.shape == (140, 512) and torch.isfinite(q).all() and torch.isfinite(t).all()
+    sub = np.array([0, 66, 131, 132, 137])
+    ids = starts[sub][:, None] + np.arange(W)[None, :]
+    x = _module_clips(eng, ids)
+    with torch.no_grad():
+        q32, t32 = q_mod(x).flatten(1), t_mod(x).flatten(1)
+    rel, ds = _mod_compare(q[sub], t[sub], q32, t32)
+    q5, t5 = eng.embed_windows([eng.q_enc, eng.t_enc], ids=ids)
+    d = max((q5 - q[sub]).abs().max().item(), (t5 - t[sub]).abs().max().item())
+    scale = max(q[sub].abs().max().item(), t[sub].abs().max().item())
+    msg = ("resnet18 224^2 W=20 %s batch 133: rel embedding error %.3e (bound %.0e), max |d score| %.3e (bound 1e-3); batch 133 vs "
+           "batch 5 max |d| %.3e (bound %.3e = TOL x scale %.3f); peak device memory %.2f GB (%.2f GB above the %.2f GB before "
+           "set_video)" % (mode, rel, 1e-4 if mode == "f16x3" else 5e-4, ds, d, TOL[mode] * scale, scale, peak / 1e9,
+                           (peak - base) / 1e9, base / 1e9))
+    print(msg)
+    assert rel <= (1e-4 if mode == "f16x3" else 5e-4), msg
+    assert ds <= 1e-3, msg
+    assert d <= TOL[mode] * scale, msg
+
+
+def test_frame_table_above_4gib(avt, dev):
+    """A 10750-frame video at 224^2: the plane-pair frame table passes 2^32 - 64 bytes, so forward_frames hands the stem kernel
+    only the frames a batch reads (torch.unique + remapped ids).  One batch mixing frames below and above the 2^32-byte mark and
+    the zero frame == the fp32 module; the stem kernel itself refuses the whole table on the host."""
+    from avtex import ops, synth
+    from avtex._lib import AvtError
+    from avtex.fused_resnet3d import ResNet3dMFMA
+    from avtex.fused_slowfast import Act, new_act
+    from avtex.texture import TextureEngine
+
+    hw, W, S, n_frames = 224, 20, 4, 10750
+    _, q_mod, t_mod = _setup(dev, "resnet18", hw, W, S, 141)
+    frame_bytes = hw * (hw // 2) * 16  # one frame of one plane: 16-byte pixel pairs
+    mark = -(-(1 << 32) // frame_bytes)  # the first frame that starts past byte 2^32 of a plane (10700)
+    eng = TextureEngine(ResNet3dMFMA(q_mod, dev), ResNet3dMFMA(t_mod, dev), None, window=W, stride=S, img_size=hw, device=dev,
+                        enc_batch=249, enc_arch="resnet18")
+    video = synth.structured_video(9, n_frames, hw, hw, device=dev)
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated(dev)
+    torch.cuda.reset_peak_memory_stats(dev)
+    eng.set_video(video)
+    torch.cuda.synchronize()
+    peak = torch.cuda.max_memory_allocated(dev)
+    assert eng._table[0].shape == (n_frames + 1, hw, hw, 4)
+    assert (eng.F + 1) * frame_bytes >= (1 << 32) - 64 and eng.F > mark
+    ids = np.stack([np.arange(W), np.arange(W) + mark - W // 2, np.arange(W) + n_frames - W, np.arange(W) + mark + 15])
+    ids[3, ::3] = -1
+    ids[3, 1] = 7
+    assert (ids[1] < mark).any() and (ids[1] >= mark).any() and ids.max() == n_frames - 1
+    q, t = eng.embed_windows([eng.q_enc, eng.t_enc], ids=ids)
+    x = _module_clips(eng, ids)
+    with torch.no_grad():
+        q32, t32 = q_mod(x).flatten(1), t_mod(x).flatten(1)
+    rel, ds = _mod_compare(q, t, q32, t32)
+    msg = ("%d-frame table (%.2f GiB per plane): rel embedding error %.3e (bound 1e-4), max |d score| %.3e (bound 1e-3); set_video "
+           "peak device memory %.2f GB (%.2f GB above the %.2f GB before)" % (n_frames + 1, (n_frames + 1) * frame_bytes / 2 ** 30,
+                                                                            rel, ds, peak / 1e9, (peak - base) / 1e9, base / 1e9))
+    print(msg)
+    assert rel <= 1e-4 and ds <= 1e-3, msg
+    # the whole table through the stem kernel: refused on the host (32-bit byte offsets), before any launch
+    conv = eng.q_enc.stem
+    tab = Act(eng._table[0].reshape(-1, 8), (1, W, hw, hw // 2), lo=eng._table[1].reshape(-1, 8))
+    y = new_act(W * (hw // 2) ** 2, conv.cout, (1, W, hw // 2, hw // 2), dev, True)
+    fidx = torch.arange(W, dtype=torch.int32, device=dev)
+    with pytest.raises(AvtError, match="too large for 32-bit offsets"):
+        ops.stem_conv_x3(tab.ptrs, conv.wt_lds, conv.wt_lds_lo, conv.bias, conv.wscale, y.ptrs, 1, W, hw, hw // 2, conv.cout,
+                         conv.kernel[0], conv.stride[0], conv.pad[0], eng.q_enc.x3, relu=True, frame_idx=fidx,
+                         table_frames=eng.F + 1)
+    del eng, video, tab
+    torch.cuda.empty_cache()
 
 
 def _validate_args(hw, W, S, **kw):
