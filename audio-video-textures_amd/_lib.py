@@ -103,6 +103,8 @@ SIGNATURES = {
     "avt_weight_planes_multi": [_vp, _vp, C.c_int, _vp],
     "avt_maxpool_train_fwd": [_vp, _vp, _vp] + [C.c_int] * 4 + [C.c_int64, _vp],
     "avt_maxpool_train_bwd": [_vp, _vp, _vp] + [C.c_int] * 4 + [C.c_int64, _vp],
+    "avt_maxpool3d_train_fwd": [_vp, _vp, _vp] + [C.c_int] * 5 + [C.c_int64, _vp],
+    "avt_maxpool3d_train_bwd": [_vp, _vp, _vp] + [C.c_int] * 5 + [C.c_int64, _vp],
     "avt_stem_wgrad_x3_supported": [C.c_int] * 4,
     "avt_stem_wgrad_x3": [_vp] * 4 + [C.c_int] * 7 + [_vp],
     "avt_pw_x3_supported": [C.c_int] * 2,

@@ -312,6 +312,111 @@ __global__ __launch_bounds__(256) void maxpool_train_bwd_kernel(MpArgs a) {
   }
 }
 
+// ---- MaxPool3d(3, stride 2, padding 1) in the training step (the 3D-ResNet stems' pool) -------------------------------------------
+// fp32 NDHWC rows, the 3D counterpart of the pair above.  Forward: the maximum of the 27-tap window and WHICH tap held it (one byte
+// per element, tap = (dt * 3 + dh) * 3 + dw), scanned in (t, h, w) order with torch's rule — `val > max || isnan(val)`, so the FIRST
+// maximum keeps the gradient (the input is post-ReLU: exact zeros tie all the time) and a NaN takes it; padding never wins.  Backward as
+// a GATHER: an input position sums the dy of the (at most eight) windows that cover it and whose recorded tap is this position, in a
+// fixed order — no atomics, dx deterministic and fully written (no memset).  A thread owns one float4 of channels of one position:
+// consecutive lanes walk consecutive 16-byte chunks of a row, so every load and store is a coalesced run along C; both passes are
+// HBM-bound (the forward's window re-reads meet in L1 / L2), no LDS.  Positions are 32-bit, element offsets 64-bit.
+struct Mp3Args {
+  const float* x;
+  float* y;
+  uint8_t* tap;  // [b, To, Ho, Wo, C]: one byte per output element
+  const float* dy;
+  float* dx;
+  int T, H, W, C, To, Ho, Wo;
+  int64_t total;  // float4 chunks of the tensor the pass writes
+  int64_t ld;     // floats between consecutive rows of the forward's y / the backward's dy
+};
+
+__global__ __launch_bounds__(256) void maxpool3d_train_fwd_kernel(Mp3Args a) {
+  const unsigned cpr = (unsigned)a.C >> 2;  // float4 chunks per row
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.total; i += (int64_t)gridDim.x * 256) {
+    unsigned p = (unsigned)(i / cpr);
+    const unsigned cc = (unsigned)(i - (int64_t)p * cpr);
+    const unsigned row = p;
+    const int wo = (int)(p % (unsigned)a.Wo);
+    p /= (unsigned)a.Wo;
+    const int ho = (int)(p % (unsigned)a.Ho);
+    p /= (unsigned)a.Ho;
+    const int to = (int)(p % (unsigned)a.To);
+    const unsigned b = p / (unsigned)a.To;
+    const float* clip = a.x + (int64_t)b * a.T * a.H * a.W * a.C + cc * 4;
+    float m[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    unsigned t[4] = {0u, 0u, 0u, 0u};
+    bool first = true;
+#pragma unroll
+    for (int dt = 0; dt < 3; ++dt) {
+      const int ti = 2 * to - 1 + dt;
+      if ((unsigned)ti >= (unsigned)a.T) continue;  // padding: never the maximum
+#pragma unroll
+      for (int dh = 0; dh < 3; ++dh) {
+        const int hi = 2 * ho - 1 + dh;
+        if ((unsigned)hi >= (unsigned)a.H) continue;
+#pragma unroll
+        for (int dw = 0; dw < 3; ++dw) {
+          const int wi = 2 * wo - 1 + dw;
+          if ((unsigned)wi >= (unsigned)a.W) continue;
+          const float4 v = *reinterpret_cast<const float4*>(clip + (int64_t)((ti * a.H + hi) * a.W + wi) * a.C);
+          const float x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (first || x[e] > m[e] || x[e] != x[e]) {  // strictly greater: the first maximum stays; a NaN takes it
+              m[e] = x[e];
+              t[e] = (unsigned)((dt * 3 + dh) * 3 + dw);
+            }
+          first = false;
+        }
+      }
+    }
+    *reinterpret_cast<float4*>(a.y + (int64_t)row * a.ld + cc * 4) = make_float4(m[0], m[1], m[2], m[3]);
+    *reinterpret_cast<uint32_t*>(a.tap + (int64_t)row * a.C + cc * 4) = t[0] | (t[1] << 8) | (t[2] << 16) | (t[3] << 24);
+  }
+}
+
+__global__ __launch_bounds__(256) void maxpool3d_train_bwd_kernel(Mp3Args a) {
+  const unsigned cpr = (unsigned)a.C >> 2;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.total; i += (int64_t)gridDim.x * 256) {
+    unsigned p = (unsigned)(i / cpr);
+    const unsigned cc = (unsigned)(i - (int64_t)p * cpr);
+    const unsigned row = p;
+    const int w = (int)(p % (unsigned)a.W);
+    p /= (unsigned)a.W;
+    const int h = (int)(p % (unsigned)a.H);
+    p /= (unsigned)a.H;
+    const int t = (int)(p % (unsigned)a.T);
+    const unsigned b = p / (unsigned)a.T;
+    float g[4] = {0.f, 0.f, 0.f, 0.f};
+    // windows (to, ho, wo) with 2 to - 1 + dt == t: to = (t + 1 - dt) / 2 for the dt of t + 1's parity — at most two per axis
+#pragma unroll
+    for (int dt = 0; dt < 3; ++dt) {
+      const int tt = t + 1 - dt;
+      if (tt < 0 || (tt & 1) || (tt >> 1) >= a.To) continue;
+#pragma unroll
+      for (int dh = 0; dh < 3; ++dh) {
+        const int hh = h + 1 - dh;
+        if (hh < 0 || (hh & 1) || (hh >> 1) >= a.Ho) continue;
+#pragma unroll
+        for (int dw = 0; dw < 3; ++dw) {
+          const int ww = w + 1 - dw;
+          if (ww < 0 || (ww & 1) || (ww >> 1) >= a.Wo) continue;
+          const int64_t orow = (int64_t)(((b * a.To + (tt >> 1)) * a.Ho + (hh >> 1)) * a.Wo + (ww >> 1));
+          const uint32_t tp = *reinterpret_cast<const uint32_t*>(a.tap + orow * a.C + cc * 4);
+          const float4 d = *reinterpret_cast<const float4*>(a.dy + orow * a.ld + cc * 4);
+          const unsigned me = (unsigned)((dt * 3 + dh) * 3 + dw);
+          g[0] += ((tp & 255u) == me) ? d.x : 0.f;
+          g[1] += (((tp >> 8) & 255u) == me) ? d.y : 0.f;
+          g[2] += (((tp >> 16) & 255u) == me) ? d.z : 0.f;
+          g[3] += ((tp >> 24) == me) ? d.w : 0.f;
+        }
+      }
+    }
+    *reinterpret_cast<float4*>(a.dx + (int64_t)row * a.C + cc * 4) = make_float4(g[0], g[1], g[2], g[3]);
+  }
+}
+
 // ---- weight planes of the training convolutions ------------------------------------------------------------------------------
 // The optimizer changes every weight every step, so every step re-splits them into the planes conv_x3 reads.  As torch ops that
 // was ~35 tiny launches per convolution (abs / amax / log2 / floor / pow / mul / casts / flip / permute-copies): 7 600 launches
@@ -394,10 +499,19 @@ __global__ __launch_bounds__(256) void weight_planes_t_kernel(WtArgs a) {
                         (int)blockIdx.z, tile);
 }
 
+// Dynamic LDS of stem_wgrad_kernel<KT, CO>: the patch planes + the dY rows of KT output frames.  A CU has 160 KB.  The 3D-ResNet stem
+// (kt = 7, 64 channels = <7, 16>) would need 54 912 + 229 376 = 284 288 bytes: it is not instantiated, avt_stem_wgrad_x3_supported says
+// no to kt = 7, and that stem's weight gradient runs as seven [1,7,7] slices of wgrad_x3 (train_ops._conv_wgrad).
+constexpr int stem_wgrad_lds_bytes(int kt, int co) {
+  return 2 * PROWS * PWP * 16 + 2 * ((kt + (co == 8 ? 2 : 1) - 1) / (co == 8 ? 2 : 1)) * (co == 8 ? 2 : 1) * RB * 32 * KBLK * co * 2;
+}
+constexpr int CU_LDS_BYTES = 160 * 1024;
+static_assert(stem_wgrad_lds_bytes(1, 16) <= CU_LDS_BYTES && stem_wgrad_lds_bytes(5, 8) <= CU_LDS_BYTES,
+              "the two SlowFast stems' weight-gradient instances fit a CU's LDS");
+
 template <int KT, int CO>
 int launch_wgrad(SwArgs& a, hipStream_t st) {
-  constexpr int FP = CO == 8 ? 2 : 1, NP = (KT + FP - 1) / FP;
-  constexpr int lds_bytes = 2 * PROWS * PWP * 16 + 2 * NP * FP * RB * 32 * KBLK * CO * 2;
+  constexpr int lds_bytes = stem_wgrad_lds_bytes(KT, CO);
   static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(stem_wgrad_kernel<KT, CO>),
                                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
   if (e != hipSuccess) {
@@ -503,6 +617,44 @@ extern "C" int avt_maxpool_train_bwd(const float* dy, const void* tap, float* dx
   hipLaunchKernelGGL(maxpool_train_bwd_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), a);
   return avt::check_launch("avt_maxpool_train_bwd");
+}
+
+// MaxPool3d(3, 2, 1) of the training step on fp32 NDHWC rows (see include/avt.h)
+static int maxpool3d_train_args(Mp3Args& a, const char* who, int batch, int t, int h, int w, int c, int64_t ld) {
+  AVT_REQUIRE(batch > 0 && t > 0 && h > 0 && w > 0 && c > 0 && c % 4 == 0, "%s: bad sizes (c %% 4 == 0)", who);
+  AVT_REQUIRE(ld == 0 || (ld >= c && ld % 4 == 0), "%s: the row pitch %lld must be 0 (contiguous) or a multiple of 4 >= c", who, (long long)ld);
+  AVT_REQUIRE((int64_t)batch * t * h * w < (1ll << 31), "%s: more than 2^31 positions", who);
+  a.T = t; a.H = h; a.W = w; a.C = c;
+  a.To = (t - 1) / 2 + 1; a.Ho = (h - 1) / 2 + 1; a.Wo = (w - 1) / 2 + 1;
+  a.ld = ld ? ld : c;
+  return AVT_OK;
+}
+
+extern "C" int avt_maxpool3d_train_fwd(const float* x, float* y, void* tap, int batch, int t, int h, int w, int c, int64_t ldy, void* stream) {
+  AVT_REQUIRE(x && y && tap, "avt_maxpool3d_train_fwd: NULL pointer");
+  AVT_REQUIRE(avt::aligned16(x) && avt::aligned16(y) && avt::aligned16(tap), "avt_maxpool3d_train_fwd: pointers must be 16-byte aligned");
+  Mp3Args a = {};
+  if (int rc = maxpool3d_train_args(a, "avt_maxpool3d_train_fwd", batch, t, h, w, c, ldy)) return rc;
+  a.x = x; a.y = y; a.tap = static_cast<uint8_t*>(tap);
+  a.total = (int64_t)batch * a.To * a.Ho * a.Wo * (c / 4);
+  const int64_t blocks = (a.total + 255) / 256;
+  hipLaunchKernelGGL(maxpool3d_train_fwd_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), a);
+  return avt::check_launch("avt_maxpool3d_train_fwd");
+}
+
+extern "C" int avt_maxpool3d_train_bwd(const float* dy, const void* tap, float* dx, int batch, int t, int h, int w, int c, int64_t ld_dy,
+                                       void* stream) {
+  AVT_REQUIRE(dy && dx && tap, "avt_maxpool3d_train_bwd: NULL pointer");
+  AVT_REQUIRE(avt::aligned16(dy) && avt::aligned16(dx) && avt::aligned16(tap), "avt_maxpool3d_train_bwd: pointers must be 16-byte aligned");
+  Mp3Args a = {};
+  if (int rc = maxpool3d_train_args(a, "avt_maxpool3d_train_bwd", batch, t, h, w, c, ld_dy)) return rc;
+  a.dy = dy; a.dx = dx; a.tap = const_cast<uint8_t*>(static_cast<const uint8_t*>(tap));
+  a.total = (int64_t)batch * t * h * w * (c / 4);
+  const int64_t blocks = (a.total + 255) / 256;
+  hipLaunchKernelGGL(maxpool3d_train_bwd_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), a);
+  return avt::check_launch("avt_maxpool3d_train_bwd");
 }
 
 // Weight planes of a training convolution (see include/avt.h)

@@ -48,7 +48,8 @@ def build_parser():
     a("--alpha", "-alpha", default=0.5, type=float, help="alpha for validation to control driving audio")
     a("--SF", "-SF", default=5, type=int, help="slomo factor N")
     a("--train_layout", default="ndhwc", choices=["ndhwc", "ncdhw"],
-      help="memory layout of the encoders in training: ndhwc = channels_last_3d (+ fused BatchNorm passes), ncdhw = torch default")
+      help="memory layout of the encoders in training: ndhwc = channels_last_3d (the hand-written training passes of train_ops, for the "
+           "SlowFast and the 3D-ResNet encoders), ncdhw = torch default (MIOpen autograd)")
     a("--bn_replicas", default=1, type=int,
       help="train(): normalise the rank's batch as this many equal groups of items, each with its own BatchNorm statistics — "
            "what the reference's DataParallel gives every GPU's share of the batch (main.py:420), running statistics from "
@@ -61,7 +62,8 @@ def build_parser():
     a("--train_conv", default="x3", choices=["x3", "fp32"],
       help="arithmetic of the training convolutions (with --train_layout ndhwc): x3 = split-plane MFMA kernels, fp32 "
            "accumulation, forward 2^-22 / gradients 2^-16 per product (default; train_ops.py); fp32 = MIOpen's fp32 "
-           "convolutions, the reference's arithmetic (train.py:114-141)")
+           "convolutions, the reference's arithmetic (train.py:114-141), with the fused BatchNorm / pool passes kept; both for SlowFast "
+           "and for the 3D-ResNets")
     a("--slomo_ckpt", default="ckpt/SuperSloMo.ckpt", type=str,
       help="SuperSloMo checkpoint (validate.py:183 hard-codes this path); 'random' = seeded weights; missing file = cuts")
     a("-long", "--long", dest="long", default=False, action="store_true", help="unused in the reference")

@@ -5,10 +5,20 @@ Same layer layout and state-dict keys as the reference's Kensho-Hara style netwo
 its final fixed-size AvgPool3d (the operator pools again with AdaptiveAvgPool3d(1), models.py:253-260)
 and [quirk] that "resnet50" is built from BasicBlocks (resnet3d.py:265-304).  ResNeXt/DenseNet
 factories of the reference cannot be reached (kwarg mismatch) and are not built.
+
+MI355X notes: this nn.Module is the weight container and the plugin surface.  At `-e --enc_impl mfma` its weights run on
+fused_resnet3d.ResNet3dMFMA; in train mode, in the training layout (channels_last_3d), its convolutions / BatchNorms / stem pool run on
+the hand-written passes of train_ops, as SlowFast's do.  The fixed AvgPool3d head stays a torch op (a few KB).
 """
 import math
 
 import torch.nn as nn
+
+from .train_ops import bn_act, conv3d, conv3d_fork, max_pool3d
+
+
+def _is_projection(m):
+    return isinstance(m, nn.Sequential) and len(m) == 2 and isinstance(m[0], nn.Conv3d) and isinstance(m[1], nn.BatchNorm3d)
 
 
 class BasicBlock(nn.Module):
@@ -24,10 +34,18 @@ class BasicBlock(nn.Module):
         self.downsample = downsample
 
     def forward(self, x):
-        r = x if self.downsample is None else self.downsample(x)
-        y = self.relu(self.bn1(self.conv1(x)))
-        y = self.bn2(self.conv2(y))
-        return self.relu(y + r)
+        # (train mode on the GPU in the training layout: the hand-written passes of train_ops — the shortcut's / projection's gradient
+        #  is summed in conv1's input-gradient launch, BatchNorm statistics ride on the convolutions' epilogues, bn2 + shortcut + ReLU
+        #  is one pass; every entry is the module's own op otherwise, so eval mode and the CPU compute what they always did)
+        y, xs = conv3d_fork(x, self.conv1, stats=self.bn1)
+        if self.downsample is None:
+            r = xs
+        elif _is_projection(self.downsample):
+            r = bn_act(conv3d(xs, self.downsample[0], stats=self.downsample[1]), self.downsample[1], relu=False)
+        else:
+            r = self.downsample(xs)
+        y = bn_act(y, self.bn1, relu=True)
+        return bn_act(conv3d(y, self.conv2, stats=self.bn2), self.bn2, res=r, relu=True)
 
 
 class ResNet3d(nn.Module):
@@ -60,7 +78,7 @@ class ResNet3d(nn.Module):
         return nn.Sequential(*layers)
 
     def forward(self, x):
-        x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
+        x = max_pool3d(bn_act(conv3d(x, self.conv1, stats=self.bn1), self.bn1, relu=True), self.maxpool)
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         return self.avgpool(x)
 

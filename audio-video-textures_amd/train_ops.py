@@ -8,6 +8,9 @@ when the model is in the training layout (channels_last_3d, main.py --train_layo
   3-channel clip) on the patch-resident kernels (csrc/stem_conv.hip forward with fp32 output, csrc/stem_train.hip weight
   gradient, both in the pixel-pair form); the strided layers' input gradients as one stride-1 convolution of dY per residue
   class of the input position (`_dgrad_strided`).  No MIOpen convolution is left in the step.
+  The 3D-ResNet modules (resnet3d.py) call the same entries: 3x3x3 / 1x1x1 convolutions at stride 1 and (2,2,2), the 7x7x7 stem on the
+  generic route (conv_x3 on the clip zero-padded to 8 channels, its weight gradient as seven [1,7,7] slices of wgrad_x3: the
+  patch-resident weight-gradient kernel would need 284 KB of LDS at kt = 7), `max_pool3d` for the stem's MaxPool3d(3, 2, 1).
 
 ARITHMETIC (main.py --train_conv, set_conv_mode): "x3" (the default on the MI355X) computes every product from two 16-bit
 planes with fp32 accumulation — forward in fp16 planes (2^-22 per product), input and weight gradients in bf16 planes (2^-16
@@ -82,7 +85,7 @@ except ImportError:  # (torch < 2.0: callers invalidate by hand, as train() alwa
 # per-process launch counters of the hand-written training kernels (tests assert that the default path really runs them)
 CALLS = {"conv_fwd_x3": 0, "dgrad_x3": 0, "dgrad_strided_x3": 0, "wgrad_x3": 0, "wgrad_stem_x3": 0, "bn_fwd": 0, "bn_bwd": 0,
          "miopen_dgrad": 0, "miopen_wgrad": 0, "stem_fwd_patch": 0, "wgrad_stem_patch": 0, "maxpool_hip": 0, "pw_f32": 0,
-         "bn_fwd_pre": 0, "bn_bwd_pre": 0, "dgrad_bwdstats": 0, "planes_multi": 0}
+         "bn_fwd_pre": 0, "bn_bwd_pre": 0, "dgrad_bwdstats": 0, "planes_multi": 0, "maxpool3d_hip": 0}
 
 
 def _p(t):
@@ -1026,25 +1029,38 @@ def _dgrad_strided(dy, weight, stride, padding, kernel, xshape):
     stride (a transposed convolution decomposed so that no zero is multiplied): class r gathers the taps d = (r + p) mod s,
     + s, ... and writes the positions s i + r through the kernel's output-row remap.  SlowFast's three kinds: [1,3,3] stride
     (1,2,2) (4 classes of 1, 2, 2, 4 taps), 1x1x1 stride (1,2,2) (one class; the other positions are zeros), [7,1,1] stride
-    (4,1,1) (4 temporal classes of 1, 2, 2, 2 taps).  -> dx, or None outside that domain (the caller falls back to MIOpen)."""
+    (4,1,1) (4 temporal classes of 1, 2, 2, 2 taps).  The 3D-ResNets' kind: 3x3x3 and 1x1x1 at stride (2,2,2), 8 classes of
+    1 ... 8 taps (seven of the projection's eight are zeros).  There frame i_t of a class is frame 2 i_t + r_t, which is the spatial
+    remap over PAIRS of frames (2 h rows) as long as T is even — so odd extents (T = 5 and 3 at W = 20) are computed on a grid
+    rounded up to even extents and cropped.  -> dx, or None outside that domain (the caller falls back to MIOpen)."""
     from . import ops
     from .fused_slowfast import split_planes
     b, cin, t, h, w = xshape
     cout = weight.shape[0]
     st, sh, sw = stride
-    if not ((st == 1 and sh == sw and sh > 1) or (sh == 1 and sw == 1 and st > 1)) or cin % 8 or cout % 8:
+    cube = st == sh == sw == 2
+    if not ((st == 1 and sh == sw and sh > 1) or (sh == 1 and sw == 1 and st > 1) or cube) or cin % 8 or cout % 8:
         return None
-    if (st > 1 and t % st) or (sh > 1 and (h % sh or w % sw)) or dy.numel() >= (1 << 30) - 64:
+    if dy.numel() >= (1 << 30) - 64:
+        return None
+    full = (t, h, w)
+    if cube:  # the grid the classes tile: every extent rounded up to the stride
+        t, h, w = (-(-n // 2) * 2 for n in full)
+        if b * t * h * w * cin >= (1 << 31) - 64:
+            return None
+    elif (st > 1 and t % st) or (sh > 1 and (h % sh or w % sw)):
         return None
     to, ho, wo = dy.shape[2], dy.shape[3], dy.shape[4]
-    if st > 1 and to * st != t:
+    if st > 1 and not cube and to * st != t:
         return None
-    key = (id(weight), "strided", tuple(stride), tuple(padding))
+    key = (id(weight), "strided", tuple(stride), tuple(padding)) + (((t, h, w),) if cube else ())
     classes = _plane_lookup(key, weight)
     if classes is None:
         per_dim = [_stride_classes(k, s_, p, x, y) for k, s_, p, x, y in zip(kernel, stride, padding, (t, h, w), (to, ho, wo))]
         if any(c is None for c in per_dim):
             return None
+        if cube and any(taps and n > y for c, y in zip(per_dim, (to, ho, wo)) for _, taps, _, n in c):
+            return None  # (a class longer than dY with its far-side taps: not a 3D-ResNet shape)
         classes, jobs = [], []
         with torch.no_grad():
             wd = weight.detach()
@@ -1079,12 +1095,16 @@ def _dgrad_strided(dy, weight, stride, padding, kernel, xshape):
         hi, lo, kern, pad_b, n = c
         if n[0] * n[1] * n[2] == 0:
             continue
-        if st > 1:   # temporal classes: frame i_t of class rt is frame st * i_t + rt: a grid of st * h rows per group of st frames
+        if cube:     # position (i_t, i_h, i_w) of class (rt, rh, rw) is (2 i_t + rt, 2 i_h + rh, 2 i_w + rw): a pair of frames as 2 h rows
+            out_rows, first = (2, 2 * h, w), (rt * h + rh) * w + rw
+        elif st > 1:  # temporal classes: frame i_t of class rt is frame st * i_t + rt: a grid of st * h rows per group of st frames
             out_rows, first = (1, st * h, w), rt * h * w
         else:        # spatial classes: position (i_h, i_w) of class (rh, rw) is (sh * i_h + rh, sw * i_w + rw)
             out_rows, first = (sh, h, w), rh * w + rw
         ops.conv3d_igemm_x3_f32_ex(dyr, hi, lo, None, rows[first:], _ktab(cout, kern, ho, wo, cout, dy.device), (b, to, ho, wo), cout,
                                    cin, kern, pad_b, n, cout, cin, ops.X3_BF16, out_rows=out_rows)
+    if (t, h, w) != full:  # the rounded-up grid's last frame / row / column is no input position
+        dx = dx[:, :, : full[0], : full[1], : full[2]].contiguous(memory_format=torch.channels_last_3d)
     return dx
 
 
@@ -1244,6 +1264,50 @@ def max_pool_hw(x, pool, cat_extra=0):
         y = _MaxPoolHW.apply(x, cat)
         y._avt_cat = cat
         return y
+    return pool(x)
+
+
+class _MaxPool3d(torch.autograd.Function):
+    """MaxPool3d(3, 2, 1) on channels-last fp32 (csrc/stem_train.hip, the 3D-ResNets' stem pool): the forward records which of the 27
+    taps held each maximum (one byte per element, torch's tie / NaN rule), the backward gathers the gradient from it."""
+
+    @staticmethod
+    def forward(ctx, x):
+        b, c, t, h, w = x.shape
+        to, ho, wo = (t - 1) // 2 + 1, (h - 1) // 2 + 1, (w - 1) // 2 + 1
+        y = torch.empty((b, c, to, ho, wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last_3d)
+        tap = torch.empty(y.numel(), dtype=torch.uint8, device=x.device)
+        CALLS["maxpool3d_hip"] += 1
+        _lib.check(_lib.lib().avt_maxpool3d_train_fwd(_p(x), _p(y), _p(tap), b, t, h, w, c, 0, _stream()), "avt_maxpool3d_train_fwd")
+        ctx.save_for_backward(tap)
+        ctx.dims = (b, c, t, h, w)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (tap,) = ctx.saved_tensors
+        b, c, t, h, w = ctx.dims
+        ld_dy = _row_ld(dy)
+        if ld_dy is None:
+            dy, ld_dy = dy.contiguous(memory_format=torch.channels_last_3d), c
+        dx = torch.empty((b, c, t, h, w), dtype=torch.float32, device=dy.device, memory_format=torch.channels_last_3d)
+        _lib.check(_lib.lib().avt_maxpool3d_train_bwd(_p(dy), _p(tap), _p(dx), b, t, h, w, c, ld_dy, _stream()), "avt_maxpool3d_train_bwd")
+        return dx
+
+
+def _triple(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v, v)
+
+
+def max_pool3d(x, pool):
+    """pool(x) for the 3D-ResNet stems' nn.MaxPool3d(3, stride=2, padding=1): the HIP pair above on channels-last fp32 device tensors
+    that carry a gradient in train mode, the module itself otherwise (eval mode, CPU, other layouts / dtypes, any other window)."""
+    if (_FUSED and pool.training and x.is_cuda and x.dtype == torch.float32 and x.dim() == 5 and x.requires_grad and
+            x.shape[1] % 4 == 0 and x.is_contiguous(memory_format=torch.channels_last_3d) and
+            _triple(pool.kernel_size) == (3, 3, 3) and _triple(pool.stride) == (2, 2, 2) and _triple(pool.padding) == (1, 1, 1) and
+            not pool.ceil_mode and _triple(pool.dilation) == (1, 1, 1) and not pool.return_indices and
+            x.numel() // x.shape[1] < (1 << 31)):
+        return _MaxPool3d.apply(x)
     return pool(x)
 
 

@@ -712,6 +712,14 @@ int avt_weight_planes_multi(const void* jobs, const int32_t* blk2job, int nblock
  * the first lateral fusion). */
 int avt_maxpool_train_fwd(const float* x, float* y, void* tap, int bt, int h, int w, int c, int64_t ldy, void* stream);
 int avt_maxpool_train_bwd(const float* dy, const void* tap, float* dx, int bt, int h, int w, int c, int64_t ld_dy, void* stream);
+/* MaxPool3d(3, stride 2, padding 1) of the 3D-ResNet stems in the training step on fp32 NDHWC rows [batch, t, h, w, c] (csrc/stem_train.hip;
+ * the reference: nn.MaxPool3d under autograd, models/video_models/resnet3d.py:141).  Output extents (n - 1) / 2 + 1 per axis.  fwd: y and
+ * `tap` (one byte per output element: which of the 27 taps, (dt * 3 + dh) * 3 + dw, held the maximum — the first one in (t, h, w) scan
+ * order on ties, a NaN wins, padding never does: the rule of the framework's own kernel).  bwd: dx = the gradient routed to those taps as
+ * a gather over the at most 8 windows that cover a position (no atomics, fixed order; dx is fully written).  c % 4 == 0; ldy / ld_dy as
+ * above (0 = c); fewer than 2^31 positions, 64-bit element offsets.  Additive symbols: the ABI version stays 8. */
+int avt_maxpool3d_train_fwd(const float* x, float* y, void* tap, int batch, int t, int h, int w, int c, int64_t ldy, void* stream);
+int avt_maxpool3d_train_bwd(const float* dy, const void* tap, float* dx, int batch, int t, int h, int w, int c, int64_t ld_dy, void* stream);
 
 /* SuperSloMo interpolation at the jumps of the stitched video (contrastive_video_textures/interpolate.py:75-147, called from
  * validate.py:588-611): the passes around the two UNets, whose convolutions are avt_conv3d_igemm_x3 with relu = 2
