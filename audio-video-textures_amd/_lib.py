@@ -90,6 +90,8 @@ SIGNATURES = {
     "avt_negative_sample_mt19937": [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp],
     "avt_clip_pack_gather_u8": [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                 C.c_int, _vp, _vp, C.c_int, _vp],
+    "avt_frames_resize_aa_norm_u8": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p, _vp, _vp],
+    "avt_clip_gather_frames_f32": [_vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp],
     "avt_stem_conv_x3": [_vp] * 8 + [C.c_int] * 11 + [_vp, C.c_int, _vp],
     "avt_lateral_x3_supported": [C.c_int] * 3,
     "avt_lateral_x3": [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp] + [C.c_int] * 10 + [_vp],

@@ -133,32 +133,47 @@ class DeviceSegmentBatcher:
     (dataset.py:121-253) without its per-item CPU preprocessing (dataset.py:145-209: process_cv2_inputs + interpolate per
     segment in DataLoader workers) and without a host round trip per step:
 
-      * the uint8 video (and the log-mel examples) stay resident in HBM;
+      * the video (and the audio examples) stay resident in HBM: as uint8 frames for SlowFast; for every other encoder (the
+        3D-ResNets) as the fp32 table [F, 3, hw, hw] the dataset keeps on the host — /255, antialiased resize, per-channel
+        normalisation — built once by ops.frames_resize_aa_norm (F * 3 * hw^2 * 4 bytes: 361 MB per 600 frames at 224^2),
+        after which the uint8 copy is dropped;
       * negatives are drawn by the device MT19937 kernel from NumPy's own stream (ops.negative_sample: the state of
         np.random is uploaded once by `seed_from_numpy()` and can be handed back by `sync_to_numpy()`), with the
         reference's hard-negative overwrite (dataset.py:183-190);
-      * query / positive / negative windows are packed by the gather kernel (ops.clip_pack_gather), starts read on device.
+      * query / positive / negative windows are packed by the gather kernels (ops.clip_pack_gather for SlowFast,
+        ops.clip_gather_frames over the table otherwise), starts read on device.
 
     batch(idx) -> (q_frames, t_frames, q_audio_eg, t_audio_eg) with the shapes the DataLoader would deliver:
-    q_frames [slow [B,3,8,hw,hw], fast [B,3,32,hw,hw]], t_frames [slow [B,1+negs,3,8,hw,hw], fast [B,1+negs,3,32,hw,hw]]."""
+    SlowFast: q_frames [slow [B,3,8,hw,hw], fast [B,3,32,hw,hw]], t_frames [slow [B,1+negs,3,8,hw,hw], fast [B,1+negs,3,32,hw,hw]];
+    otherwise: q_frames [B,W,3,hw,hw], t_frames [B,1+negs,W,3,hw,hw].
+    loader(batch_size) is the form train() iterates."""
 
     def __init__(self, dataset, device, dtype=torch.float32):
         from . import ops
 
-        if dataset.enc_arch != "slowfast" or dataset.split != "train":
-            raise ValueError("DeviceSegmentBatcher packs SlowFast training items")
+        if dataset.split != "train":
+            raise ValueError("DeviceSegmentBatcher packs training items")
+        self.slowfast = dataset.enc_arch == "slowfast"
+        if not self.slowfast and dtype != torch.float32:
+            raise ValueError("DeviceSegmentBatcher: the frame table of %s is float32, not %s" % (dataset.enc_arch, dtype))
         self.ops, self.ds, self.dev, self.dtype = ops, dataset, torch.device(device), dtype
-        self.frames = dataset.video_u8.to(self.dev).contiguous()
-        self.audio_eg = dataset.audio_eg.to(self.dev) if dataset.audio_eg.dim() == 4 else None
-        self.state = None
-        self._gauss = (0, 0.0)
-        # segment ids the sampler can produce are 0 .. len(ds) (positive = idx + 1, negatives from [0, len]); the gather kernel
-        # reads its starts on the device and CLAMPS frame ids (a bad id cannot fault, but would silently repeat edge frames),
+        self.n_frames = int(dataset.video_u8.shape[0])
+        # segment ids the sampler can produce are 0 .. len(ds) (positive = idx + 1, negatives from [0, len]); the gather kernels
+        # read their starts on the device and CLAMP frame ids (a bad id cannot fault, but would silently repeat edge frames),
         # so the one check that every id is in range is made here, once
         need = len(dataset) * dataset.stride + dataset.window
-        if need > self.frames.shape[0]:
+        if need > self.n_frames:
             raise ValueError("DeviceSegmentBatcher: segment %d needs frames up to %d, the video has %d"
-                             % (len(dataset), need, self.frames.shape[0]))
+                             % (len(dataset), need, self.n_frames))
+        self.frames = dataset.video_u8.to(self.dev).contiguous()
+        self.table = None
+        if not self.slowfast:
+            self.table = ops.frames_resize_aa_norm(self.frames, dataset.img_size)
+            self.frames = None  # (the table is all this branch reads)
+        self.audio_eg = dataset.audio_eg.to(self.dev) if dataset.audio_eg.dim() == 4 else None
+        self._audio_any = None  # loader(): the examples of any rank, the dummy [n, 10] of adata=None included
+        self.state = None
+        self._gauss = (0, 0.0)
 
     def seed_from_numpy(self):
         st = np.random.get_state()
@@ -180,19 +195,58 @@ class DeviceSegmentBatcher:
         neg = self.ops.negative_sample(self.state, idx, len(self.ds), self.ds.n_negs)
         return idx + 1, neg
 
-    def batch(self, idx):
+    def _pack(self, idx):
+        """idx int64 [B] (device) -> (q_frames, t_frames, target segment ids [B, 1 + negs])."""
         ds, S, W = self.ds, self.ds.stride, self.ds.window
-        idx = torch.as_tensor(idx, dtype=torch.int64).to(self.dev).contiguous()
         b = idx.numel()
         pos, neg = self.sample(idx)
         tgt = torch.cat((pos.view(b, 1), neg.to(torch.int64)), 1)  # [B, 1 + negs] segment ids
         starts = (torch.cat((idx, tgt.reshape(-1))) * S).to(torch.int32).contiguous()
-        slow, fast = self.ops.clip_pack_gather(self.frames, starts, W, out_hw=ds.img_size, dtype=self.dtype)
         hw, n = ds.img_size, tgt.shape[1]
+        if not self.slowfast:
+            clips = self.ops.clip_gather_frames(self.table, starts, W)  # [B + B n, W, 3, hw, hw]
+            return clips[:b], clips[b:].view(b, n, W, 3, hw, hw), tgt
+        slow, fast = self.ops.clip_pack_gather(self.frames, starts, W, out_hw=hw, dtype=self.dtype)
         q_frames = [slow[:b], fast[:b]]
         t_frames = [slow[b:].view(b, n, 3, 8, hw, hw), fast[b:].view(b, n, 3, 32, hw, hw)]
+        return q_frames, t_frames, tgt
+
+    def batch(self, idx):
+        idx = torch.as_tensor(idx, dtype=torch.int64).to(self.dev).contiguous()
+        b = idx.numel()
+        q_frames, t_frames, tgt = self._pack(idx)
         q_ae = t_ae = None
         if self.audio_eg is not None:
             q_ae = self.audio_eg[idx]
-            t_ae = self.audio_eg[tgt.reshape(-1)].view(b, n, *self.audio_eg.shape[1:])
+            t_ae = self.audio_eg[tgt.reshape(-1)].view(b, tgt.shape[1], *self.audio_eg.shape[1:])
         return q_frames, t_frames, q_ae, t_ae
+
+    def loader(self, batch_size, shuffle=True, drop_last=True):
+        """The DataLoader's place in train(): a re-iterable with __len__ whose epochs yield
+        (q_frames, None, q_audio_eg, t_frames, None, t_audio_eg) — train() never touches the waveform fields."""
+        return _DeviceLoader(self, int(batch_size), shuffle, drop_last)
+
+
+class _DeviceLoader:
+    def __init__(self, batcher, batch_size, shuffle, drop_last):
+        if batch_size < 1:
+            raise ValueError("DeviceSegmentBatcher.loader: batch_size must be positive")
+        self.bat, self.batch_size, self.shuffle, self.drop_last = batcher, batch_size, shuffle, drop_last
+
+    def __len__(self):
+        n = len(self.bat.ds)
+        return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
+
+    def __iter__(self):
+        bat = self.bat
+        if bat._audio_any is None:
+            bat._audio_any = bat.audio_eg if bat.audio_eg is not None else bat.ds.audio_eg.to(bat.dev)
+        audio = bat._audio_any
+        n = len(bat.ds)
+        order = torch.randperm(n) if self.shuffle else torch.arange(n)  # (host order; not RandomSampler's stream)
+        for i in range(len(self)):
+            idx = order[i * self.batch_size : (i + 1) * self.batch_size].to(bat.dev)
+            q_frames, t_frames, tgt = bat._pack(idx)
+            # audio examples as the dataset indexes them (audio_eg[idx]; audio_eg[idx + 1] then audio_eg[neg]), whatever their rank
+            t_ae = audio[tgt.reshape(-1)].view(idx.numel(), tgt.shape[1], *audio.shape[1:])
+            yield q_frames, None, audio[idx], t_frames, None, t_ae

@@ -3,7 +3,7 @@ reference parser with the same names, defaults and types; `main(args, video_name
 loop with the fps -> window/stride override (main.py:511-516) and default checkpoint name (:520-534).
 
 Additions (all optional): --stitch_mode {compat,aligned}, --ref_num_gpus, --enc_dtype {fp32,bf16},
---enc_batch, --vcam (the flag validate.py:299 reads but the reference never defines [quirk Q2]).
+--enc_batch, --train_input {loader,device}, --vcam (the flag validate.py:299 reads but the reference never defines [quirk Q2]).
 Multi-GPU: one process per GPU under torch.distributed.run instead of torch.nn.DataParallel (main.py:420).
 """
 import argparse
@@ -59,6 +59,11 @@ def build_parser():
       help="1: train() captures the device side of a step (forward, loss, backward, optimizer) once per batch shape as a HIP graph and "
            "replays it (train_ops.GraphedStep) — for small batches whose launches the host issues slower than the device runs them; one "
            "process only; the first batch of a shape also serves the two warm-up steps (not in the reference)")
+    a("--train_input", default="loader", choices=["loader", "device"],
+      help="where train() gets its batches: loader = torch DataLoader over AudioVideoSegments (host preprocessing, the reference's "
+           "path); device = dataset.DeviceSegmentBatcher: the video resident in HBM (SlowFast: uint8 frames; other encoders: the "
+           "resized and normalised fp32 frame table), negatives drawn and windows gathered by HIP kernels, no per-step host copy; "
+           "one process only (the sharded sampler stays the DataLoader's)")
     a("--train_conv", default="x3", choices=["x3", "fp32"],
       help="arithmetic of the training convolutions (with --train_layout ndhwc): x3 = split-plane MFMA kernels, fp32 "
            "accumulation, forward 2^-22 / gradients 2^-16 per product (default; train_ops.py); fp32 = MIOpen's fp32 "
@@ -131,6 +136,13 @@ def main(args, video_name, itr=0):
         train_loader = torch.utils.data.DataLoader(dataset_train, batch_size=max(args.batch_size // world, 1),
                                                    shuffle=sampler is None, sampler=sampler,
                                                    num_workers=args.workers, drop_last=True)
+        if getattr(args, "train_input", "loader") == "device":
+            if world > 1:
+                raise ValueError("--train_input device assembles every batch on one GPU and has no sharded sampler: run one process, "
+                                 "or keep --train_input loader under torch.distributed.run")
+            from .dataset import DeviceSegmentBatcher
+
+            train_loader = DeviceSegmentBatcher(dataset_train, device).loader(max(args.batch_size, 1), shuffle=True, drop_last=True)
     print("=> creating model '{}'".format(args.model_type))
     builder = ModelBuilder3D()
     q_image_enc_model, fc_dim = builder.build_network(arch=args.enc_arch, img_size=args.size, window=args.window)

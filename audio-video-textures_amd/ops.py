@@ -237,6 +237,37 @@ def clip_pack_gather(frames_u8, win_start_dev, win_len, out_hw=224, mean=0.45, s
     return slow, fast
 
 
+RESNET_MEAN, RESNET_STD = (0.4345, 0.4051, 0.3775), (0.2768, 0.2713, 0.2737)  # dataset.py:48-49, RGB
+
+
+def frames_resize_aa_norm(frames_u8, out_hw, mean=RESNET_MEAN, std=RESNET_STD):
+    """frames_u8 [F,H,W,3] uint8 RGB (device) -> fp32 [F,3,hw,hw]: /255, F.interpolate(bilinear, antialias=True) unless the frames
+    already are hw x hw, (x - mean_c) / std_c — the 3D-ResNets' frame preprocessing (dataset.py:44-58), once per video."""
+    _dev(frames_u8, "frames_u8", torch.uint8)
+    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
+        raise _lib.AvtError("frames_resize_aa_norm: frames_u8 must be [F, H, W, 3]")
+    n_frames, h, w, _ = frames_u8.shape
+    out = torch.empty((n_frames, 3, int(out_hw), int(out_hw)), dtype=torch.float32, device=frames_u8.device)
+    m, s = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
+    _lib.check(_lib.lib().avt_frames_resize_aa_norm_u8(_p(frames_u8), n_frames, h, w, int(out_hw), m, s, _p(out), _stream()),
+               "avt_frames_resize_aa_norm_u8")
+    return out
+
+
+def clip_gather_frames(table, win_start_dev, win_len):
+    """table fp32 [F,3,hw,hw], window starts int32 [n] (both device) -> fp32 [n, win_len, 3, hw, hw], out[i, t] = table[start[i] + t]
+    (frame ids clamped to the table: the caller checks the range of its starts once)."""
+    _dev(table, "table", torch.float32)
+    _dev(win_start_dev, "win_start", torch.int32)
+    if table.dim() != 4 or table.shape[1] != 3 or table.shape[2] != table.shape[3]:
+        raise _lib.AvtError("clip_gather_frames: table must be [F, 3, hw, hw]")
+    n_frames, hw, n_win = int(table.shape[0]), int(table.shape[2]), int(win_start_dev.numel())
+    out = torch.empty((n_win, int(win_len), 3, hw, hw), dtype=torch.float32, device=table.device)
+    _lib.check(_lib.lib().avt_clip_gather_frames_f32(_p(table), n_frames, hw, _p(win_start_dev), n_win, int(win_len), _p(out),
+                                                     _stream()), "avt_clip_gather_frames_f32")
+    return out
+
+
 def negative_sample(mt_state, idx, n_len, n_negs):
     """mt_state int32/uint32-bits [625] device tensor (np.random.get_state() key + pos), advanced in place; idx int64 [B]
     device -> negatives int32 [B, n_negs] (dataset.py:181-190 semantics, NumPy's stream)."""

@@ -511,6 +511,25 @@ int avt_negative_sample_mt19937(uint32_t* mt_state, const int64_t* idx, int batc
 int avt_clip_pack_gather_u8(const uint8_t* frames, int n_frames, int height, int width,
                             const int32_t* win_start, int n_win, int win_len, int out_hw, float mean,
                             float std, int bgr, void* slow, void* fast, int out_dtype, void* stream);
+/* The same path for the 3D-ResNet encoders (csrc/frame_table.hip; the host preprocessing of dataset/dataset.py:44-58 and the
+ * per-item slicing of :145-209).  Added without an ABI bump: new symbols, no existing entry changed.
+ * avt_frames_resize_aa_norm_u8: frames uint8 [n_frames, height, width, 3] RGB (device) -> out fp32 [n_frames, 3, out_hw, out_hw]
+ * (device), once per video:  v = u8 / 255, then the antialiased bilinear resize of ATen (F.interpolate(mode="bilinear",
+ * antialias=True): per axis scale = in / out, support = max(scale, 1), center = scale (i + 0.5), taps int(center - support + 0.5)
+ * .. int(center + support + 0.5) clipped to [0, in), triangle weights divided by their sum; x first, then y, fp32), then
+ * (. - mean[c]) / std[c] with mean / std HOST arrays of 3 floats in RGB order.  height == width == out_hw applies no filter and is
+ * bit-identical to (u8 / 255 - mean) / std in fp32.  Upscaling is the two-tap case of the same formula.  The taps are walked in a
+ * loop with no compile-time bound; what bounds the ratio is the workgroup's LDS: (min(out_hw, 256) rounded up to 64) *
+ * (2 ceil(max(width / out_hw, 1)) + 1) + 3 * (source pixels under 256 output columns) floats must fit 64 KiB, e.g. 1920 -> 224
+ * takes 41.5 KiB and 3840 -> 224 (82 KiB) does not fit: refused with AVT_ERR_ARG.  out_hw <= 8192.
+ * avt_clip_gather_frames_f32: out fp32 [n_win, win_len, 3, out_hw, out_hw], out[n, t] = table[clamp(win_start[n] + t, 0,
+ * n_frames - 1)] with table fp32 [n_frames, 3, out_hw, out_hw] and win_start int32 [n_win] both on the device (the clamp of
+ * avt_clip_pack_gather_u8: a bad start cannot fault; the caller checks the range once).  Frame bases are 64-bit: the table and
+ * the output may each pass 2^31 elements; n_win * win_len * ceil(3 out_hw^2 / 4096) workgroups must stay below 2^31. */
+int avt_frames_resize_aa_norm_u8(const uint8_t* frames, int n_frames, int height, int width, int out_hw, const float* mean,
+                                 const float* std, float* out, void* stream);
+int avt_clip_gather_frames_f32(const float* table, int n_frames, int out_hw, const int32_t* win_start, int n_win, int win_len,
+                               float* out, void* stream);
 
 /* Train-mode BatchNorm3d fused with the shortcut add and the ReLU that follow it in the SlowFast blocks (csrc/bn_train.hip;
  * the model the reference trains, train.py:114-141 / models/models.py:385-417), on channels-last fp32 rows [m, c] (c a power of
