@@ -996,12 +996,14 @@ extern "C" int avt_conv3d_igemm_x3_xl_picked(int cout, int k, int m) {
   return (cout % 256 == 0 && k >= 256 && k <= kMaxTabSteps * 64 && m >= 256 * 64) ? 1 : 0;
 }
 
-static int igemm_x3_impl(const void* in_hi, const void* in_lo, const void* wt_hi, const void* wt_lo,
-                         const float* bias, const void* res_hi, const void* res_lo, void* out_hi, void* out_lo,
-                         const int32_t* ktab, int batch, int t, int h, int w, int cin, int cout, int kt, int kh,
-                         int kw, int st, int sh, int sw, int pt, int ph, int pw, int to, int ho, int wo, int ldi,
-                         int ldo, int ldr, int relu, int out_row_stride, int out_h, int out_w, int plane_dtype,
-                         const float* wscale, void* stream, int wblk) {
+// one launch: every plane of the input within 32-bit byte offsets (conv_args_fill).  xl = the tile the WHOLE layer runs on
+// (avt_conv3d_igemm_x3_xl_picked of all its rows): the frame ranges of a split layer stay on one tile and one weight order
+static int igemm_x3_one(const void* in_hi, const void* in_lo, const void* wt_hi, const void* wt_lo,
+                        const float* bias, const void* res_hi, const void* res_lo, void* out_hi, void* out_lo,
+                        const int32_t* ktab, int batch, int t, int h, int w, int cin, int cout, int kt, int kh,
+                        int kw, int st, int sh, int sw, int pt, int ph, int pw, int to, int ho, int wo, int ldi,
+                        int ldo, int ldr, int relu, int out_row_stride, int out_h, int out_w, int plane_dtype,
+                        const float* wscale, void* stream, int wblk, int xl) {
   AVT_REQUIRE(plane_dtype == AVT_X3_BF16 || plane_dtype == AVT_X3_F16, "avt_conv3d_igemm_x3: plane_dtype must be 0 (bf16) or 1 (fp16)");
   AVT_REQUIRE(!wscale || avt::aligned16(wscale), "avt_conv3d_igemm_x3: wscale must be 16-byte aligned");
   AVT_REQUIRE(in_lo && wt_lo && out_lo && (!res_hi == !res_lo), "avt_conv3d_igemm_x3: every tensor needs both planes");
@@ -1022,10 +1024,9 @@ static int igemm_x3_impl(const void* in_hi, const void* in_lo, const void* wt_hi
   a.wblk = wblk;
   hipStream_t s = static_cast<hipStream_t>(stream);
   // long-K layers whose output channels fill 256-wide tiles: the XL tile
-  AVT_REQUIRE(!wblk || (avt_conv3d_igemm_x3_xl_picked(cout, a.K, a.M) && a.K % 32 == 0),
+  AVT_REQUIRE(!wblk || (xl && a.K % 32 == 0),
               "avt_conv3d_igemm_x3_wblk: K-blocked weights are the 256 x 256 tile's (avt_conv3d_igemm_x3_xl_picked, K %% 32 == 0)");
-  if (avt_conv3d_igemm_x3_xl_picked(cout, a.K, a.M))
-    return plane_dtype == AVT_X3_F16 ? launch_x3_xl<true>(a, s) : launch_x3_xl<false>(a, s);
+  if (xl) return plane_dtype == AVT_X3_F16 ? launch_x3_xl<true>(a, s) : launch_x3_xl<false>(a, s);
   if (plane_dtype == AVT_X3_F16) {
     if (cout <= 32) return launch_x3<128, 32, 32, true>(a, s);
     if (cout <= 64) return launch_x3<128, 64, 64, true>(a, s);
@@ -1034,6 +1035,66 @@ static int igemm_x3_impl(const void* in_hi, const void* in_lo, const void* wt_hi
   if (cout <= 32) return launch_x3<128, 32, 32, false>(a, s);
   if (cout <= 64) return launch_x3<128, 64, 64, false>(a, s);
   return launch_x3<128, 128, 64, false>(a, s);
+}
+
+// Both tiles address the activations through 32-bit byte offsets into a buffer resource (rowoff = m * ldi, aoffs = (rowoff + tap) * 2),
+// so ONE launch reads input planes below 2^32 bytes (conv_args_fill: batch * t * h * w * ldi < 2^31 - 64 elements).  A layer without
+// temporal taps (kt = 1, temporal stride 1, no temporal padding) treats every frame by itself: where its input plane is longer — the
+// first slow res3 block at 249 clips, whose 6 246 912 input rows are widened from 320 to 448 columns for the K-concatenated c (5.6 GB
+// per plane) — the launcher walks the frames in ranges whose planes each stay below the limit, one launch per range with the plane,
+// residual and output pointers advanced on the host (64-bit).  The K loops are untouched.  The output side needs nothing: rows are
+// 32-bit, their byte offsets 64-bit (out_row).  The limit NOW: one frame's plane h * w * ldi < 2^31 - 64 elements for kt = 1 layers
+// (all frames together as before for layers with temporal taps), and fewer than 2^31 output rows (and remapped rows) per layer;
+// anything past it is rejected with AVT_ERR_ARG.
+static int igemm_x3_impl(const void* in_hi, const void* in_lo, const void* wt_hi, const void* wt_lo,
+                         const float* bias, const void* res_hi, const void* res_lo, void* out_hi, void* out_lo,
+                         const int32_t* ktab, int batch, int t, int h, int w, int cin, int cout, int kt, int kh,
+                         int kw, int st, int sh, int sw, int pt, int ph, int pw, int to, int ho, int wo, int ldi,
+                         int ldo, int ldr, int relu, int out_row_stride, int out_h, int out_w, int plane_dtype,
+                         const float* wscale, void* stream, int wblk) {
+  constexpr int64_t kMaxPlane = (1ll << 31) - 64;  // elements of one input plane per launch
+  const bool sane = batch > 0 && t > 0 && h > 0 && w > 0 && ldi > 0 && ldo > 0 && cin > 0 && cout > 0 && kt >= 1 && kh >= 1 && kw >= 1 &&
+                    st >= 1 && sh >= 1 && sw >= 1 && ph >= 0 && pw >= 0 && ho >= 0 && wo >= 0 && out_row_stride >= 1 && out_h >= 0 && out_w >= 0;
+  const int64_t frame = sane ? (int64_t)h * w * ldi : 0, frames = sane ? (int64_t)batch * t : 0;
+  if (!sane || frame * frames < kMaxPlane || kt != 1 || st != 1 || pt != 0 || (to != 0 && to != t)) {
+    // one launch (or conv_args_fill's rejection: bad arguments, or temporal taps over a plane past the limit)
+    const int64_t k_all = (int64_t)kt * kh * kw * cin;
+    int xl = 0;
+    if (sane && k_all < (1ll << 31)) {
+      const int64_t fho = ho > 0 ? ho : (h + 2 * ph - kh) / sh + 1, fwo = wo > 0 ? wo : (w + 2 * pw - kw) / sw + 1;
+      const int64_t fto = to > 0 ? to : (t + 2 * pt - kt) / st + 1;
+      const int64_t m = (int64_t)batch * fto * fho * fwo;
+      xl = (m > 0 && m < (1ll << 31)) ? avt_conv3d_igemm_x3_xl_picked(cout, (int)k_all, (int)m) : 0;
+    }
+    return igemm_x3_one(in_hi, in_lo, wt_hi, wt_lo, bias, res_hi, res_lo, out_hi, out_lo, ktab, batch, t, h, w, cin, cout, kt, kh, kw, st,
+                        sh, sw, pt, ph, pw, to, ho, wo, ldi, ldo, ldr, relu, out_row_stride, out_h, out_w, plane_dtype, wscale, stream, wblk,
+                        xl);
+  }
+  AVT_REQUIRE(frame < kMaxPlane, "avt_conv3d_igemm_x3: one frame's input plane (%d x %d x %d elements) is too large for 32-bit offsets", h, w,
+              ldi);
+  AVT_REQUIRE(in_hi && in_lo && out_hi && out_lo && (!res_hi == !res_lo), "avt_conv3d_igemm_x3: every tensor needs both planes");
+  const int fho = ho > 0 ? ho : (h + 2 * ph - kh) / sh + 1, fwo = wo > 0 ? wo : (w + 2 * pw - kw) / sw + 1;
+  AVT_REQUIRE(fho > 0 && fwo > 0, "avt_conv3d_igemm_x3: bad output extent");
+  const bool remap = out_row_stride > 1 || (out_h > 0 && out_w > 0);
+  const int64_t m_all = frames * fho * fwo;
+  const int64_t orows = remap ? (int64_t)out_h * out_w : (int64_t)fho * fwo;  // output-buffer rows per frame
+  AVT_REQUIRE(m_all < (1ll << 31) && frames * orows < (1ll << 31) && (int64_t)kh * kw * cin < (1ll << 31),
+              "avt_conv3d_igemm_x3: tensor too large for 32-bit rows");
+  const int xl = avt_conv3d_igemm_x3_xl_picked(cout, kh * kw * cin, (int)m_all);
+  const int64_t fmax = kMaxPlane / frame;                 // frames whose planes one launch can address (>= 1)
+  const int64_t nrange = (frames + fmax - 1) / fmax;
+  const int64_t per = (frames + nrange - 1) / nrange;     // even ranges: no short tail launch
+  for (int64_t f0 = 0; f0 < frames; f0 += per) {
+    const int nf = (int)((frames - f0 < per) ? frames - f0 : per);
+    const int64_t io = f0 * frame, oo = f0 * orows * ldo, ro = f0 * fho * fwo * ldr;
+    auto adv = [](const void* p, int64_t e) { return p ? static_cast<const void*>(static_cast<const uint16_t*>(p) + e) : nullptr; };
+    const int rc = igemm_x3_one(adv(in_hi, io), adv(in_lo, io), wt_hi, wt_lo, bias, adv(res_hi, ro), adv(res_lo, ro),
+                                const_cast<void*>(adv(out_hi, oo)), const_cast<void*>(adv(out_lo, oo)), ktab, nf, 1, h, w, cin, cout, kt, kh,
+                                kw, st, sh, sw, pt, ph, pw, to ? 1 : 0, ho, wo, ldi, ldo, ldr, relu, out_row_stride, out_h, out_w,
+                                plane_dtype, wscale, stream, wblk, xl);
+    if (rc != AVT_OK) return rc;
+  }
+  return AVT_OK;
 }
 
 extern "C" int avt_conv3d_igemm_x3(const void* in_hi, const void* in_lo, const void* wt_hi, const void* wt_lo,

@@ -32,6 +32,10 @@ _FUSE_KCAT = 1       # slow res2 first block: shortcut folded into c's GEMM (K =
 _XB = 1              # bf16: long-K layers with fragment-order weights that bypass the LDS (XB tile)
 _FUSE_SCAT = 1       # bf16: slow res3-5 first blocks: strided shortcut folded into c's GEMM
 _FUSE_TCHUNK = 0     # bf16 fused blocks: frames walked per workgroup (2 halo frames each); 0 = by width: 16 at 56 columns, else 32
+_FUSE_SCAT_X3 = 1    # contract grade: slow res3-5 first blocks: strided shortcut folded into c's GEMM (_BlockX3.scat)
+# ... except the (cin, cout) of first blocks whose merged GEMM measured SLOWER than the shortcut + c launches it replaces (none:
+# profiles/r07/scat_x3_ab.md)
+_SCAT_X3_SKIP = set()
 _FUSE_BLOCK_X3 = 1   # contract grade: fast-pathway bottlenecks as one kernel (csrc/bneck_x3.hip)
 _FUSE_TCHUNK_X3 = 0  # contract grade: frames walked per workgroup; 0 = by width (11 at 14 columns, else 8)
 _CHAIN_X3 = 1        # contract grade: slow res2 c (+ residual) -> next a in one pass (pw_chain_x3_kernel)
@@ -873,8 +877,12 @@ class _Block:
 
 class _BlockX3:
     """A residual block in the contract-grade mode.  Fast-pathway blocks with an identity shortcut (res2-4) and res2's
-    8-channel first block run as ONE kernel (csrc/bneck_x3.hip: the x3 counterpart of the bf16 path's bottleneck_fused);
-    every other block is four split-plane convolutions (shortcut, a, b, c + residual)."""
+    8-channel first block run as ONE kernel (csrc/bneck_x3.hip: the x3 counterpart of the bf16 path's bottleneck_fused); slow
+    res2's identity blocks too (fp16 planes, csrc/res2_x3.hip).  The first block of a slow stage folds its shortcut conv into c's
+    GEMM over K = [x | b-output] when the caller left `extra` spare columns behind x's channels: three launches (a, b, merged c) —
+    `ccat` (res2, stride 1) and `scat` (res3-5: the shortcut and b have spatial stride 2, b writes into x's own rows (2 ho, 2 wo)).
+    Every other block, and a first block whose input has no spare columns or an odd height / width, is split-plane convolutions
+    one by one (shortcut, a, b, c + residual)."""
 
     def __init__(self, blk, device, x3):
         self.b1 = FusedConv(blk.branch1, blk.branch1_bn, False, device, x3=x3) if hasattr(blk, "branch1") else None
@@ -922,12 +930,32 @@ class _BlockX3:
             self.ccat = FusedConv(None, None, True, device, folded=(torch.cat([wsc, wc], 1), bc + bsc, (1, 1, 1), (0, 0, 0)), x3=x3)
             self.ccat.alg_flops_per_row = self.c.alg_flops_per_row + self.b1.alg_flops_per_row
             self.extra = self.c.cin
+        # first block of a stage with a STRIDED 1x1x1 shortcut (slow res3 / res4 / res5; the same rule as _Block.scat): b ([1,3,3],
+        # stride 2) writes its output behind x's channels in x's OWN rows (2 ho, 2 wo) (out_rows), so c and the shortcut are one
+        # stride-2 pointwise GEMM over K = [x | b-output] with one shared per-channel weight scale: no shortcut launch, no shortcut
+        # tensor written as two planes and read straight back as c's residual
+        self.scat = None
+        if (_FUSE_SCAT_X3 and self.b1 is not None and self.fused is None and self.ccat is None and
+                self.c.kernel == (1, 1, 1) and self.b1.kernel == (1, 1, 1) and self.b.kernel == (1, 3, 3) and
+                self.b.stride == (1, 2, 2) and self.b1.stride == (1, 2, 2) and self.a.stride == (1, 1, 1) and
+                self.c.stride == (1, 1, 1) and self.a.kernel[1:] == (1, 1) and self.b1._folded is not None and
+                (self.a.cin, self.c.cout) not in _SCAT_X3_SKIP):
+            (wsc, bsc), (wc, bc) = self.b1._folded, self.c._folded
+            self.scat = FusedConv(None, None, True, device, folded=(torch.cat([wsc, wc], 1), bc + bsc, (1, 2, 2), (0, 0, 0)), x3=x3)
+            self.scat.alg_flops_per_row = self.c.alg_flops_per_row + self.b1.alg_flops_per_row
+            self.extra = self.c.cin
+
+    def _scat_ok(self, x):
+        return (self.scat is not None and x.c0 == 0 and x.lo is not None and x.ld >= x.C + self.extra and x.C == self.a.cin and
+                x.dims[2] % 2 == 0 and x.dims[3] % 2 == 0)
 
     def can_chain(self, nxt):
         """True when this block's c (+ residual + ReLU) and the next block's a (+ ReLU) run as ONE pointwise pass
         (csrc/pw_x3.hip, the chained form): both pointwise on the streaming kernel, identity shortcut here."""
         if self.res2 is not None or (nxt is not None and nxt.res2 is not None):
             return False  # (a block that runs as one kernel neither hands its c to a chain nor takes its a from one)
+        if self.scat is not None or (nxt is not None and nxt.scat is not None):
+            return False  # (nor does a block whose c is the K-concatenated strided GEMM: its c reads x's rows, its a x's slice)
         return (_CHAIN_X3 and nxt is not None and self.b1 is None and self.fused is None and nxt.fused is None and
                 getattr(self.c, "pw", None) is not None and getattr(nxt.a, "pw", None) is not None and nxt.ccat is None and
                 nxt.a.cin == self.c.cout and ops.pw_chain_x3_supported(self.c.cin, self.c.cout, nxt.a.cout))
@@ -935,6 +963,9 @@ class _BlockX3:
     def __call__(self, x, out=None, chain=None, a_pre=None):
         """chain = the next block (can_chain(...) holds): returns (y, a-output of the next block); a_pre = this block's a-output
         when the previous block's chained pass has already produced it."""
+        if chain is None and a_pre is None and self._scat_ok(x):
+            self.b(self.a(x), out=Act(x.buf, x.dims, x.C, self.extra, lo=x.lo), out_rows=(2, x.dims[2], x.dims[3]))
+            return self.scat(Act(x.buf, x.dims, 0, x.C + self.extra, lo=x.lo), out=out)
         if chain is not None or a_pre is not None:
             m = self._b(a_pre if a_pre is not None else self.a(x))
             sc = self.b1(x) if self.b1 is not None else x
@@ -1211,10 +1242,12 @@ class SlowFastMFMA(nn.Module):
                 if i == len(slow_blocks) - 1 and not last:  # straight into the next fusion's concat buffer
                     od = blk.b.out_dims(blk.a.out_dims(s_act.dims))
                     cs, cf = blk.c.cout, f_act.C
-                    cat = new_act(od[0] * od[1] * od[2] * od[3], cs + 2 * cf, od, self.dev, True)
+                    # (+ spare columns for the next stage's K-concatenated strided c, where its rows are even: _BlockX3.scat)
+                    extra = self.stages[k + 1][0][0].extra if (od[2] % 2 == 0 and od[3] % 2 == 0) else 0
+                    cat = new_act(od[0] * od[1] * od[2] * od[3], cs + 2 * cf + extra, od, self.dev, True)
                     blk(s_act, out=sl(cat, 0, cs), a_pre=a_pre)
                     self.fuse[k + 1](f_act, out=sl(cat, cs, 2 * cf))
-                    s_act = cat
+                    s_act = sl(cat, 0, cs + 2 * cf)
                 else:
                     s_act = blk(s_act, a_pre=a_pre)
         emb = torch.empty((b, s_act.C + f_act.C), dtype=torch.float32, device=self.dev)

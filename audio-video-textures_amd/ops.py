@@ -913,9 +913,18 @@ def res2_x3(x_ptrs, ldi, out_ptrs, ldo, packed, batch, t, h, w, plane_dtype):
     _dev(coef, "coef", torch.float32)
     if wfrag.numel() * 2 != _lib.lib().avt_res2_x3_wfrag_bytes():
         raise _lib.AvtError("res2_x3: wfrag holds %d bytes, the kernel streams %d" % (wfrag.numel() * 2, _lib.lib().avt_res2_x3_wfrag_bytes()))
-    _lib.check(_lib.lib().avt_res2_x3(C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]), C.c_void_p(out_ptrs[0]), C.c_void_p(out_ptrs[1]),
-                                      _p(wfrag), _p(coef), int(batch), int(t), int(h), int(w), int(ldi), int(ldo), int(plane_dtype),
-                                      _stream()), "avt_res2_x3")
+    # the kernel addresses both tensors through 32-bit byte offsets (planes below 2^32 - 64 bytes per launch) and clips do not see
+    # each other: a tensor with longer planes — the stage's last block writing into the next stage's widened concat buffer at the
+    # production batch — goes in even clip ranges, one launch each
+    clip_bytes = int(t) * int(h) * int(w) * max(int(ldi), int(ldo)) * 2
+    ranges = -(-int(batch) * clip_bytes // ((1 << 32) - 65)) if clip_bytes > 0 else 1
+    per = -(-int(batch) // max(ranges, 1))
+    for b0 in range(0, int(batch), max(per, 1)):
+        nb = min(per, int(batch) - b0)
+        xo, oo = b0 * t * h * w * int(ldi) * 2, b0 * t * h * w * int(ldo) * 2
+        _lib.check(_lib.lib().avt_res2_x3(C.c_void_p(x_ptrs[0] + xo), C.c_void_p(x_ptrs[1] + xo), C.c_void_p(out_ptrs[0] + oo),
+                                          C.c_void_p(out_ptrs[1] + oo), _p(wfrag), _p(coef), nb, int(t), int(h), int(w), int(ldi), int(ldo),
+                                          int(plane_dtype), _stream()), "avt_res2_x3")
 
 
 def bneck_x3_supported(cin, c, w):

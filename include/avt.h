@@ -331,7 +331,10 @@ int avt_bottleneck_fused_bf16(const void* x, void* out, const void* wa, const fl
  *                are stored pre-scaled by a power of two per output channel (wscale[n] undoes it on the accumulator)
  * and a product is three MFMA passes into one fp32 accumulator: wl*ah + wh*al + wh*ah (csrc/conv_x3.hip).
  * Arguments as avt_conv3d_igemm_rows_bf16, each tensor given as its two planes; res_hi/res_lo both NULL = no residual;
- * wscale [cout] fp32 or NULL.  * relu: 0 none, 1 ReLU, 2 LeakyReLU(0.1) (the SuperSloMo UNets, models/slowmo.py:69-71; this entry only). */
+ * wscale [cout] fp32 or NULL.  * relu: 0 none, 1 ReLU, 2 LeakyReLU(0.1) (the SuperSloMo UNets, models/slowmo.py:69-71; this entry only).
+ * Size limits: fewer than 2^31 output rows; an input plane of batch * t * h * w * ldi < 2^31 - 64 elements for layers with temporal taps;
+ * a layer with kt = 1, temporal stride 1 and no temporal padding may pass that (the launcher walks its frames in ranges, one launch
+ * each) as long as ONE frame's h * w * ldi stays below it.  Anything larger is AVT_ERR_ARG. */
 #define AVT_X3_BF16 0
 #define AVT_X3_F16  1
 int avt_conv3d_igemm_x3(const void* in_hi, const void* in_lo, const void* wt_hi, const void* wt_lo,
