@@ -59,6 +59,10 @@ def build_parser():
       help="1: train() captures the device side of a step (forward, loss, backward, optimizer) once per batch shape as a HIP graph and "
            "replays it (train_ops.GraphedStep) — for small batches whose launches the host issues slower than the device runs them; one "
            "process only; the first batch of a shape also serves the two warm-up steps (not in the reference)")
+    a("--train_optimizer", default="torch", choices=["torch", "hip"],
+      help="torch: torch.optim.SGD (the reference's, main.py:440); hip: train_ops.ArenaSGD — the same update as one HIP launch over all "
+           "parameters with --lr / --momentum / --weight_decay read from device memory: with --train_graph 1 the replayed step then "
+           "follows the StepLR schedule (torch's SGD keeps the rate it was captured with) and the first batch of a shape takes one step")
     a("--train_input", default="loader", choices=["loader", "device"],
       help="where train() gets its batches: loader = torch DataLoader over AudioVideoSegments (host preprocessing, the reference's "
            "path); device = dataset.DeviceSegmentBatcher: the video resident in HBM (SlowFast: uint8 frames; other encoders: the "
@@ -208,8 +212,13 @@ def main(args, video_name, itr=0):
         if rank == 0 or (world > 1 and args.stitch_mode == "aligned"):
             validate(model, args, video_name=video_name, tb_logger=tb_logger, model_type=args.model_type, itr=itr)
         return
-    optimizer = torch.optim.SGD(params=model.parameters(), lr=args.lr, momentum=args.momentum,
-                                weight_decay=args.weight_decay)
+    if getattr(args, "train_optimizer", "torch") == "hip":
+        from .train_ops import ArenaSGD
+
+        optimizer = ArenaSGD(model.parameters(), lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay)
+    else:
+        optimizer = torch.optim.SGD(params=model.parameters(), lr=args.lr, momentum=args.momentum,
+                                    weight_decay=args.weight_decay)
     scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=args.lr_steps)
     print("Training for {} epochs.".format(args.epochs - args.start_epoch))
     for epoch in range(args.start_epoch, args.epochs):

@@ -651,6 +651,26 @@ def weight_planes_multi(jobs, blk2job, nblocks):
     _lib.check(_lib.lib().avt_weight_planes_multi(_p(jobs), _p(blk2job), int(nblocks), _stream()), "avt_weight_planes_multi")
 
 
+def sgd_job_bytes():
+    return int(_lib.lib().avt_sgd_job_bytes())
+
+
+def sgd_multi(jobs, blk2job, nblocks, hyper):
+    """One SGD step over every job of a DEVICE table of AvtSgdJob (include/avt.h) in one launch, the hyper-parameters read from the
+    device tensor `hyper` [groups, 4] = lr, momentum, weight_decay, nesterov (train_ops.ArenaSGD builds the table)."""
+    assert jobs.is_cuda and blk2job.is_cuda and blk2job.dtype == torch.int32 and blk2job.numel() == nblocks
+    assert hyper.is_cuda and hyper.dtype == torch.float32 and hyper.is_contiguous() and hyper.shape[-1] == 4
+    _lib.check(_lib.lib().avt_sgd_multi(_p(jobs), _p(blk2job), int(nblocks), _p(hyper), _stream()), "avt_sgd_multi")
+
+
+def sgd_upload(dst, src_pinned, nbytes):
+    """The first `nbytes` of a PINNED host tensor into a device tensor, as one async copy on the current stream — under stream capture a
+    node of the graph, which re-reads the host tensor on every replay (the caller keeps it alive and unchanged)."""
+    assert dst.is_cuda and dst.is_contiguous() and not src_pinned.is_cuda and src_pinned.is_pinned() and src_pinned.is_contiguous()
+    assert 0 < nbytes <= min(dst.numel() * dst.element_size(), src_pinned.numel() * src_pinned.element_size())
+    _lib.check(_lib.lib().avt_sgd_upload(_p(dst), _p(src_pinned), int(nbytes), _stream()), "avt_sgd_upload")
+
+
 def weight_planes_t_f32(w3d, sel):
     """[cout, taps, cin] fp32 -> (hi, lo) bf16 planes [cin, len(sel) * cout] with out[ci][a][co] = w[co][sel[a]][ci]: the input
     gradient's filter (sel = all taps reversed) or one residue class of a strided layer's (csrc/stem_train.hip)."""

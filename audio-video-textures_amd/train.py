@@ -58,11 +58,27 @@ def train(train_loader, model, optimizer, args, epoch, tb_logger=None):
                     tf = static[max(nq, 1) : max(nq, 1) + nt] if nt else static[max(nq, 1)]
                     return _eager_step(model, optimizer, criterion, args, qf, tf, static[-2], static[-1], batch_size)
 
-                ent = graphed[key] = (static, train_ops.GraphedStep(device_step, static[0].device, warmup=2))
-                # (the warm-up steps and the capture consumed this batch: three optimizer steps on it, like a first batch seen thrice)
+                if isinstance(optimizer, train_ops.ArenaSGD):
+                    # the warm-up steps train on this batch; put the state back afterwards, so that the first replay is the ONE step the
+                    # batch takes (as in the eager loop and the reference).  The capture must start from stale weight planes — their
+                    # re-make launch is then part of the graph and every replay splits the weights it finds — which the step hook of the
+                    # last warm-up step leaves behind
+                    saved = _snapshot(model, optimizer)
+
+                    def stale_planes():
+                        assert train_ops.weight_cache_is_stale(), "the capture would start from current weight planes: no re-make in the graph"
+
+                    ent = graphed[key] = (static, train_ops.GraphedStep(device_step, static[0].device, warmup=2, before_capture=stale_planes))
+                    _restore(saved)
+                    train_ops.invalidate_weight_cache()
+                else:
+                    ent = graphed[key] = (static, train_ops.GraphedStep(device_step, static[0].device, warmup=2))
+                    # (the warm-up steps and the capture consumed this batch: three optimizer steps on it, like a first batch seen thrice)
             else:
                 for dst, src in zip(ent[0], flat):
                     dst.copy_(src, non_blocking=True)
+            if hasattr(optimizer, "sync_hyper"):
+                optimizer.sync_hyper()  # (the replay reads the learning rate from device memory: what the scheduler set since the last one)
             loss = ent[1]()
             losses.update(loss.item(), batch_size)
         else:
@@ -85,6 +101,24 @@ def train(train_loader, model, optimizer, args, epoch, tb_logger=None):
                 tb_logger.log_scalar(value, key, iter_count)
             tb_logger.flush()
     return losses.avg
+
+
+def _snapshot(model, optimizer):
+    """Clones of everything a training step changes: parameters, the model's buffers (BatchNorm statistics, num_batches_tracked) and the
+    optimizer's momentum buffers -> [(tensor, clone)]."""
+    seen, out = set(), []
+    tensors = list(model.parameters()) + list(model.buffers()) + [p for g in optimizer.param_groups for p in g["params"]] + \
+        [v for st in optimizer.state.values() for v in st.values() if isinstance(v, torch.Tensor)]
+    for t in tensors:
+        if id(t) not in seen:
+            seen.add(id(t))
+            out.append((t, t.detach().clone()))
+    return out
+
+
+def _restore(saved):
+    with torch.no_grad():
+        torch._foreach_copy_([t.detach() for t, _ in saved], [c for _, c in saved])
 
 
 def _eager_step(model, optimizer, criterion, args, q_frames, t_frames, q_audio_eg, t_audio_eg, batch_size):

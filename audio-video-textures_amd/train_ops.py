@@ -85,7 +85,7 @@ except ImportError:  # (torch < 2.0: callers invalidate by hand, as train() alwa
 # per-process launch counters of the hand-written training kernels (tests assert that the default path really runs them)
 CALLS = {"conv_fwd_x3": 0, "dgrad_x3": 0, "dgrad_strided_x3": 0, "wgrad_x3": 0, "wgrad_stem_x3": 0, "bn_fwd": 0, "bn_bwd": 0,
          "miopen_dgrad": 0, "miopen_wgrad": 0, "stem_fwd_patch": 0, "wgrad_stem_patch": 0, "maxpool_hip": 0, "pw_f32": 0,
-         "bn_fwd_pre": 0, "bn_bwd_pre": 0, "dgrad_bwdstats": 0, "planes_multi": 0, "maxpool3d_hip": 0}
+         "bn_fwd_pre": 0, "bn_bwd_pre": 0, "dgrad_bwdstats": 0, "planes_multi": 0, "maxpool3d_hip": 0, "sgd_multi": 0}
 
 
 def _p(t):
@@ -385,7 +385,7 @@ class GraphedStep:
     graph and returns the same (graph-owned) result tensor.  Inputs must be STATIC tensors that step_fn closes over (fill them with
     copy_ before each call); anything the host decides inside step_fn (branches, cache lookups, shapes) is frozen at capture."""
 
-    def __init__(self, step_fn, device, warmup=3):
+    def __init__(self, step_fn, device, warmup=3, before_capture=None):
         self.graph, self.out = None, None
         # warm-up and capture run on ONE stream of this object: the step's side streams are chosen per step stream
         # (models._side_stream), and a capture stream that differs from the warm-up's was handed the fast pathway's side stream for
@@ -406,6 +406,8 @@ class GraphedStep:
                 step_fn()
         torch.cuda.current_stream(device).wait_stream(self.stream)
         torch.cuda.synchronize(device)
+        if before_capture is not None:  # (the caller's checks of the state the capture starts from: train() with an ArenaSGD)
+            before_capture()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, stream=self.stream):
             self.out = step_fn()
@@ -414,6 +416,204 @@ class GraphedStep:
     def __call__(self):
         self.graph.replay()
         return self.out
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# SGD whose hyper-parameters live in device memory (csrc/sgd.hip): the optimizer of a step replayed as a HIP graph.  torch's SGD
+# (fused or multi-tensor) takes the learning rate as a kernel ARGUMENT, which a capture freezes: after scheduler.step() every replay
+# kept applying the first epoch's rate.  Here the rate is a load from `hyper`, which sync_hyper() rewrites outside the graph.
+_SGD_CHUNK = 4096  # elements per block (csrc/sgd.hip kChunk)
+
+
+def pack_sgd_jobs(recs):
+    """recs: (p, g, buf, numel, group) per parameter — addresses as ints, buf 0 without momentum -> (AvtSgdJob table as bytes,
+    blk2job int32 array, blocks): job n owns ceil(numel / 4096) consecutive blocks from its blk0 (include/avt.h)."""
+    import struct
+
+    raw, blk, b0 = [], [], 0
+    for n, (p, g, buf, numel, group) in enumerate(recs):
+        nb = (int(numel) + _SGD_CHUNK - 1) // _SGD_CHUNK
+        raw.append(struct.pack("<3Qq2i", p, g, buf, int(numel), int(group), b0))
+        blk.append(np.full(nb, n, dtype=np.int32))
+        b0 += nb
+    return b"".join(raw), (np.concatenate(blk) if blk else np.zeros(0, np.int32)), b0
+
+
+def _same_layout(a, b):
+    return a.shape == b.shape and all(sa == sb for n, sa, sb in zip(a.shape, a.stride(), b.stride()) if n > 1)
+
+
+class ArenaSGD(torch.optim.Optimizer):
+    """torch.optim.SGD's update (momentum, weight decay, Nesterov; dampening 0) as ONE launch over all parameters
+    (ops.sgd_multi: a device table of jobs, one per parameter with a gradient), its hyper-parameters read from a device tensor:
+    a step captured in a HIP graph follows `param_groups` — StepLR, a hand-set rate — once sync_hyper() has run (eager step()
+    calls it; train() does before every replay).  A torch.optim.Optimizer: schedulers, state_dict() (interchangeable with
+    torch.optim.SGD's: `momentum_buffer` per parameter) and the process-wide step hook of the weight-plane cache work unchanged.
+    Parameters: fp32, on the device, contiguous (in torch's default or the channels-last format), not sparse."""
+
+    def __init__(self, params, lr, momentum=0, weight_decay=0, nesterov=False, dampening=0, maximize=False):
+        self._hyper_dev, self._hyper_host = None, None
+        self._table = None     # {"key", "jobs", "blk2job", "blocks", "captured", "keep"} of the last launch
+        self._captured = []    # what a stream capture launched with: alive as long as the graphs that replay it may be
+        self._spare = None     # pinned staging buffer for the table of the next captured step
+        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov, maximize=maximize)
+        super().__init__(params, defaults)
+        self._check_groups()
+        with torch.no_grad():
+            for group in self.param_groups:
+                if group["momentum"] != 0:
+                    for p in group["params"]:
+                        self._buffer(p)
+        if self.param_groups[0]["params"][0].is_cuda:
+            self.sync_hyper()
+
+    @staticmethod
+    def _check_param(p):
+        if not isinstance(p, torch.Tensor) or not p.is_cuda:
+            raise _lib.AvtError("ArenaSGD: parameters must be device (HIP) tensors; the optimizer has no CPU path")
+        if p.is_sparse or p.layout != torch.strided:
+            raise _lib.AvtError("ArenaSGD: sparse parameters are not supported")
+        if p.dtype != torch.float32:
+            raise _lib.AvtError("ArenaSGD: parameters must be fp32, got %s" % p.dtype)
+        dense = p.is_contiguous() or (p.dim() == 4 and p.is_contiguous(memory_format=torch.channels_last)) or \
+            (p.dim() == 5 and p.is_contiguous(memory_format=torch.channels_last_3d))
+        if not dense:
+            raise _lib.AvtError("ArenaSGD: parameters must be contiguous (torch's default or the channels-last format); got shape %s "
+                                "strides %s" % (tuple(p.shape), tuple(p.stride())))
+
+    def _check_groups(self):
+        for group in self.param_groups:
+            if group.get("dampening", 0) != 0:
+                raise _lib.AvtError("ArenaSGD: dampening must be 0 (a zero-initialised buffer then gives torch's first-step rule)")
+            if group.get("maximize", False):
+                raise _lib.AvtError("ArenaSGD: maximize is not supported")
+            if group["nesterov"] and group["momentum"] <= 0:
+                raise _lib.AvtError("ArenaSGD: Nesterov momentum needs momentum > 0")
+            if group["lr"] < 0 or group["momentum"] < 0 or group["weight_decay"] < 0:
+                raise _lib.AvtError("ArenaSGD: lr, momentum and weight_decay must be >= 0")
+
+    def add_param_group(self, param_group):
+        super().add_param_group(param_group)
+        for p in self.param_groups[-1]["params"]:
+            self._check_param(p)
+        if self._hyper_host is not None:  # (after construction: the next sync_hyper() uploads a table with the new group's row)
+            self._check_groups()
+            self._captured.append(self._hyper_dev)
+            self._hyper_dev, self._hyper_host, self._spare = None, None, None
+
+    def _set_aside(self):
+        """A pinned buffer large enough for the table over ALL parameters, allocated outside any capture: what a captured step() stages
+        its table in (_build_table)."""
+        if self._spare is None:
+            ps = [p for g in self.param_groups for p in g["params"]]
+            nbytes = 40 * len(ps) + 4 * sum((p.numel() + _SGD_CHUNK - 1) // _SGD_CHUNK for p in ps)
+            self._spare = torch.empty(max(nbytes, 8), dtype=torch.uint8, pin_memory=True)
+
+    def _buffer(self, p):
+        buf = self.state[p].get("momentum_buffer")
+        if buf is None:
+            if p.is_cuda and torch.cuda.is_current_stream_capturing():
+                raise _lib.AvtError("ArenaSGD.step() under stream capture: a momentum buffer is missing (set the momentum before the capture)")
+            buf = self.state[p]["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        return buf
+
+    def sync_hyper(self):
+        """Make the device copy of (lr, momentum, weight_decay, nesterov) per group equal `param_groups`: one small host-to-device copy
+        on the current stream when they differ from what was last uploaded (after scheduler.step(), once per epoch), nothing otherwise.
+        -> True when it copied.  Not under stream capture: a replay must see the values the host set AFTER the capture."""
+        vals = tuple((float(g["lr"]), float(g["momentum"]), float(g["weight_decay"]), 1.0 if g["nesterov"] else 0.0)
+                     for g in self.param_groups)
+        if self._hyper_dev is not None and vals == self._hyper_host:
+            return False
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.AvtError("ArenaSGD.sync_hyper() under stream capture: call it before the capture / between replays")
+        self._check_groups()
+        self._set_aside()
+        device = self.param_groups[0]["params"][0].device
+        host = torch.tensor(vals, dtype=torch.float32).pin_memory()  # (a new pinned tensor per change: an earlier copy may be in flight)
+        if self._hyper_dev is None:
+            self._hyper_dev = torch.empty((len(vals), 4), dtype=torch.float32, device=device)
+        self._hyper_dev.copy_(host, non_blocking=True)
+        self._hyper_host = vals
+        return True
+
+    def _build_table(self, key, keep, capturing):
+        from . import ops
+        for p, g, buf in keep:
+            if g.dtype != torch.float32 or g.device != p.device or g.layout != torch.strided or not _same_layout(g, p):
+                raise _lib.AvtError("ArenaSGD.step(): a gradient must be an fp32 device tensor with its parameter's strides; got %s %s "
+                                    "strides %s for a parameter with strides %s" % (g.dtype, g.device, tuple(g.stride()), tuple(p.stride())))
+            if buf is not None and (buf.dtype != torch.float32 or buf.device != p.device or not _same_layout(buf, p)):
+                raise _lib.AvtError("ArenaSGD.step(): a momentum buffer must be an fp32 device tensor with its parameter's strides")
+        raw, blk, blocks = pack_sgd_jobs(key)
+        assert len(raw) == len(key) * ops.sgd_job_bytes(), "AvtSgdJob layout"
+        # jobs and blk2job in one pinned buffer, one copy
+        data = torch.from_numpy(np.frombuffer(raw + blk.tobytes(), dtype=np.uint8).copy())
+        dev = torch.empty(data.numel(), dtype=torch.uint8, device=keep[0][0].device)
+        if capturing:
+            # the gradients of a captured step live in the graph's own pool: their addresses are not known before the capture, so the
+            # table's copy is a node of the graph.  It re-reads `host` on every replay: the pinned buffer set aside before the capture
+            # (no pinned allocation inside one), which this table keeps from now on
+            host, self._spare = self._spare, None
+            if host is None or host.numel() < data.numel():
+                raise _lib.AvtError("ArenaSGD.step() under stream capture: no staging buffer is left (two captures in a row: call "
+                                    "sync_hyper() or step() outside a capture between them)")
+            host[:data.numel()].copy_(data)
+            ops.sgd_upload(dev, host, data.numel())
+        else:
+            host = data.pin_memory()  # (a new pinned tensor per table: an earlier copy may be in flight)
+            dev.copy_(host, non_blocking=True)
+        tab = {"key": key, "jobs": dev[:len(raw)], "blk2job": dev[len(raw):].view(torch.int32), "blocks": blocks, "captured": capturing,
+               "keep": (host, dev)}  # (not the gradients: held, they would never return to the allocator and move every step)
+        self._table = tab
+        return tab
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        from . import ops
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        capturing = torch.cuda.is_current_stream_capturing()
+        if not capturing:
+            self.sync_hyper()  # (while capturing no hyper-parameter is uploaded: the graph reads what the host copies between replays)
+            self._set_aside()
+        elif self._hyper_dev is None:
+            raise _lib.AvtError("ArenaSGD.step() under stream capture before any sync_hyper()")
+        key, keep = [], []
+        for gi, group in enumerate(self.param_groups):
+            mom = group["momentum"] != 0
+            for p in group["params"]:
+                g = p.grad
+                if g is None or p.numel() == 0:
+                    continue  # (torch's rule: no gradient, no update — the momentum buffer stays as it is)
+                buf = self._buffer(p) if mom else None
+                key.append((p.data_ptr(), g.data_ptr(), buf.data_ptr() if buf is not None else 0, p.numel(), gi))
+                keep.append((p, g, buf))
+        if not key:
+            return loss
+        key = tuple(key)
+        tab = self._table
+        # (the same tensors at the same addresses every step: built once.  A table made under capture is filled by its own graph's
+        #  replays only, so no later step launches with it)
+        if tab is None or tab["key"] != key or tab["captured"]:
+            tab = self._build_table(key, keep, capturing)
+        if capturing and not any(t is tab for t in self._captured):
+            self._captured.append(tab)  # a HIP graph holds this table's address: it outlives every later rebuild
+        ops.sgd_multi(tab["jobs"], tab["blk2job"], tab["blocks"], self._hyper_dev)
+        CALLS["sgd_multi"] += 1
+        return loss
+
+
+def weight_cache_is_stale():
+    """True when no cached set of weight planes is current (every lookup re-makes its planes): the state a capture must start from
+    for the re-make launch to be part of its graph."""
+    for ent in _PLANES.values():
+        owner = ent.ref()
+        if owner is not None and not ent.stale(owner):
+            return False
+    return True
 
 
 # ------------------------------------------------------------------------------------------------------------------------

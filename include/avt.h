@@ -726,6 +726,31 @@ typedef struct AvtPlaneJob {
 int avt_weight_planes_job_bytes(void);
 int avt_weight_planes_multi(const void* jobs, const int32_t* blk2job, int nblocks, void* stream);
 
+/* SGD with momentum / weight decay / Nesterov over ALL of an optimizer's parameters in one launch, hyper-parameters read from DEVICE
+ * memory (csrc/sgd.hip; the reference: torch.optim.SGD, main.py:440, stepped by train.py:141).  A step replayed as a HIP graph freezes
+ * kernel arguments at capture; `hyper` is a load, so a replay applies the rate the host last copied there.  The job-table pattern of
+ * avt_weight_planes_multi: `jobs` a DEVICE array of AvtSgdJob (one per parameter), `blk2job` a DEVICE int32 [nblocks]; job j owns blocks
+ * blk0 .. blk0 + ceil(numel / 4096), block b the elements [(b - blk0) * 4096, + 4096) of its tensor (64-bit offsets).
+ * `hyper`: DEVICE fp32 [n_groups][4] = lr, momentum, weight_decay, nesterov (0 / 1).  Per element, fp32, single-rounded a + alpha * b
+ * steps as the framework's multi-tensor form: g' = g + wd * p (wd == 0: g); buf = mu * buf + g'; d = nesterov ? g' + mu * buf : buf;
+ * p = p - lr * d.  buf NULL: no momentum (d = g').  Dampening is 0: a zero-initialised buf gives the first step's buf = g'.
+ * p / g / buf: fp32, dense, 4-byte aligned (16-byte aligned chunks take 16-byte accesses).  The caller validates the jobs;
+ * avt_sgd_job_bytes() = sizeof(AvtSgdJob).  Additive symbols: the ABI version stays 8. */
+typedef struct AvtSgdJob {
+  float* p;
+  const float* g;
+  float* buf;            /* momentum buffer, NULL when the group's momentum is 0 */
+  int64_t numel;
+  int32_t group;         /* row of `hyper` */
+  int32_t blk0;          /* first block of the job in the launch */
+} AvtSgdJob;
+int avt_sgd_job_bytes(void);
+int avt_sgd_multi(const void* jobs, const int32_t* blk2job, int nblocks, const float* hyper, void* stream);
+/* The table's upload as ONE async host-to-device copy on `stream`, for a step that is being captured (its gradients live in the graph's
+ * own pool: the table cannot be uploaded before the capture).  Captured, the copy is a node of the graph and re-reads `src_host` on every
+ * replay: PINNED host memory that stays alive and unchanged as long as the graph. */
+int avt_sgd_upload(void* dst, const void* src_host, int64_t nbytes, void* stream);
+
 /* MaxPool3d((1,3,3),(1,2,2),(0,1,1)) of the stems in the training step on fp32 NDHWC rows [bt, h, w, c] (csrc/stem_train.hip;
  * the reference: the third-party SlowFast stem under autograd, train.py:114-141).  fwd: y [bt, ho, wo, c] and `tap`
  * (bt*ho*wo*c/2 bytes: 4 bits per element = which of the 9 taps held the maximum; the first one on ties, a NaN wins — torch's
