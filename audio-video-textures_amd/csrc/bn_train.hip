@@ -23,6 +23,7 @@
 // blockIdx.y walks the groups in the streaming passes, a finalize wavefront walks them in order for its channel (so the running
 // statistics receive the groups' updates in item order, as a loop over the items would apply them).
 #include "avt_common.h"
+#include "mfma.h"
 
 namespace {
 
@@ -30,14 +31,8 @@ constexpr int kT = 256;
 
 // streamed once: non-temporal loads in every pass and non-temporal stores of the backward's outputs: +2.4 % on the training
 // step (profiles/r03/train_bn_nt_ab.log)
-typedef float f32x4n __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 ldg4(const float* p, int64_t i) {
-  const f32x4n v = __builtin_nontemporal_load(reinterpret_cast<const f32x4n*>(p) + i);
-  return make_float4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ void stg4(float* p, int64_t i, float4 v) {
-  __builtin_nontemporal_store(f32x4n{v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4n*>(p) + i);
-}
+using avt::ldg4;
+using avt::stg4;
 constexpr int kMaxBlocks = 1024;  // 4 workgroups per CU: enough 16-byte loads in flight for HBM, few enough rows of partials
 
 struct BnArgs {

@@ -31,30 +31,16 @@
 #include <type_traits>
 
 #include "avt_common.h"
+#include "mfma.h"
 #include "split_planes.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
+using avt::f32x4;
+using avt::i32x4;
+using avt::mfma16;
+using avt::mfma3;
 constexpr unsigned kOob = 0xFFFFFFF0u;
-
-template <bool F16>
-__device__ __forceinline__ f32x4 mfma16(i32x4 w, i32x4 x, f32x4 c) {
-  if constexpr (F16)
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, w), __builtin_bit_cast(f16x8, x), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), c, 0, 0, 0);
-}
-// one split-plane product, small terms first (conv_x3.hip's order)
-template <bool F16>
-__device__ __forceinline__ f32x4 mfma3(i32x4 wh, i32x4 wl, i32x4 xh, i32x4 xl, f32x4 c) {
-  c = mfma16<F16>(wl, xh, c);
-  c = mfma16<F16>(wh, xl, c);
-  return mfma16<F16>(wh, xh, c);
-}
 
 // two products into two accumulators, their passes interleaved: no MFMA reads the result of the one issued just before it (the
 // same three terms per accumulator in the same order: identical bits)
@@ -132,10 +118,10 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void bneck_x3_kernel(BxArgs 
   // both a strips start as zeros: border columns, rows outside the image and tile padding stay zero for the whole walk
   for (int i = tid * 16; i < (DB ? 4 : 2) * ABYTES; i += NW * 64 * 16) *reinterpret_cast<i32x4*>(aoh + i) = i32x4{0, 0, 0, 0};
 
-  const __amdgpu_buffer_rsrc_t rxh = __builtin_amdgcn_make_buffer_rsrc((void*)a.xh, 0, a.x_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rxl = __builtin_amdgcn_make_buffer_rsrc((void*)a.xl, 0, a.x_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t roh = __builtin_amdgcn_make_buffer_rsrc((void*)a.oh, 0, a.o_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rol = __builtin_amdgcn_make_buffer_rsrc((void*)a.ol, 0, a.o_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rxh = avt::buffer_rsrc(a.xh, a.x_bytes);
+  const __amdgpu_buffer_rsrc_t rxl = avt::buffer_rsrc(a.xl, a.x_bytes);
+  const __amdgpu_buffer_rsrc_t roh = avt::buffer_rsrc(a.oh, a.o_bytes);
+  const __amdgpu_buffer_rsrc_t rol = avt::buffer_rsrc(a.ol, a.o_bytes);
 
   // ---- geometry of this lane in every tile slot, computed once
   unsigned poff[AIT];  // byte offset inside a frame (one plane) of this lane's chunk of k-step 0, or out of bounds

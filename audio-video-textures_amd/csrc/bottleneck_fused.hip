@@ -25,12 +25,13 @@
 #include <stdlib.h>
 
 #include "avt_common.h"
+#include "mfma.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
+using avt::bf16x8;
+using avt::f32x4;
+using avt::i32x4;
 constexpr unsigned kOob = 0xFFFFFFF0u;
 
 struct BArgs {
@@ -149,7 +150,7 @@ __global__ __launch_bounds__(NW * 64, 1) void bottleneck_kernel(BArgs a) {
   for (int i = tid * 16; i < ABYTES; i += NW * 64 * 16) *reinterpret_cast<i32x4*>(ao + i) = i32x4{0, 0, 0, 0};
 
   // ---- x ring DMA: instruction d of a frame fills positions d*PPI + lane/CH, slot lane%CH (chunk = slot ^ swizzle)
-  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, a.x_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rx = avt::buffer_rsrc(a.x, a.x_bytes);
   auto swz = [&](int p) { return (CH == 4 ? (p >> 2) : CH == 8 ? (p >> 1) : p) & (CH - 1); };  // CH == 1: 0
   constexpr int NDW = (NDMA + NW - 1) / NW;  // DMA instructions per wave per frame
   unsigned poff[NDW];                  // byte offset of this lane's chunk inside a frame, or OOB

@@ -12,12 +12,13 @@
 #include <stdlib.h>
 
 #include "avt_common.h"
+#include "mfma.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
+using avt::bf16x8;
+using avt::f32x4;
+using avt::i32x4;
 constexpr unsigned kOob = 0xFFFFFFF0u;
 constexpr int CCH = 64;
 constexpr int NFB = 9 * 2 * 4;  // weight fragments: [tap][k half][N-tile]
@@ -64,7 +65,7 @@ __global__ __launch_bounds__(((HT * W + 15) / 16) * 64, 1) void c33_kernel(C33Ar
   }
   __syncthreads();  // the zeroing must not race the first DMA
 
-  const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc((void*)a.in, 0, a.in_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rm = avt::buffer_rsrc(a.in, a.in_bytes);
   unsigned poff[NDW];
   int pdst[NDW];
 #pragma unroll

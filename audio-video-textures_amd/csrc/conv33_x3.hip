@@ -18,23 +18,15 @@
 #include <type_traits>
 
 #include "avt_common.h"
+#include "mfma.h"
 #include "split_planes.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
+using avt::f32x16;
+using avt::i32x4;
+using avt::mfma32;
 constexpr unsigned kOob = 0xFFFFFFF0u;
-
-template <bool F16>
-__device__ __forceinline__ f32x16 mfma(i32x4 w, i32x4 x, f32x16 c) {
-  if constexpr (F16)
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, w), __builtin_bit_cast(f16x8, x), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), c, 0, 0, 0);
-}
 
 struct C33Args {
   const uint16_t* xh;
@@ -65,10 +57,10 @@ __global__ __launch_bounds__(NW * 64, 2) void conv33_x3_kernel(C33Args a) {
   for (int i = tid; i < 128; i += NW * 64) cf[i] = a.coef[i];
   __syncthreads();
 
-  const __amdgpu_buffer_rsrc_t rxh = __builtin_amdgcn_make_buffer_rsrc((void*)a.xh, 0, a.x_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rxl = __builtin_amdgcn_make_buffer_rsrc((void*)a.xl, 0, a.x_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t roh = __builtin_amdgcn_make_buffer_rsrc((void*)a.oh, 0, a.o_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rol = __builtin_amdgcn_make_buffer_rsrc((void*)a.ol, 0, a.o_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rxh = avt::buffer_rsrc(a.xh, a.x_bytes);
+  const __amdgpu_buffer_rsrc_t rxl = avt::buffer_rsrc(a.xl, a.x_bytes);
+  const __amdgpu_buffer_rsrc_t roh = avt::buffer_rsrc(a.oh, a.o_bytes);
+  const __amdgpu_buffer_rsrc_t rol = avt::buffer_rsrc(a.ol, a.o_bytes);
   const int HW = a.H * a.W;
   const int stride_t = gridDim.x * NW;
   const bool ledge = lr == 0, redge = lr == 31;
@@ -139,9 +131,9 @@ __global__ __launch_bounds__(NW * 64, 2) void conv33_x3_kernel(C33Args a) {
           const int f = ((tap * 4 + k) * 2 + n) * 2;
           const i32x4 wh = *reinterpret_cast<const i32x4*>(lds + f * 1024 + lofs);
           const i32x4 wl = *reinterpret_cast<const i32x4*>(lds + (f + 1) * 1024 + lofs);
-          acc[n] = mfma<F16>(wl, xo[0], acc[n]);  // small terms first
-          acc[n] = mfma<F16>(wh, xo[1], acc[n]);
-          acc[n] = mfma<F16>(wh, xo[0], acc[n]);
+          acc[n] = mfma32<F16>(wl, xo[0], acc[n]);  // small terms first
+          acc[n] = mfma32<F16>(wh, xo[1], acc[n]);
+          acc[n] = mfma32<F16>(wh, xo[0], acc[n]);
         }
       }
     }

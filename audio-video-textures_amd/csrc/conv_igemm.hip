@@ -35,12 +35,13 @@
 
 #include "avt_common.h"
 #include "conv_args.h"
+#include "mfma.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
+using avt::bf16x8;
+using avt::f32x16;
+using avt::i32x4;
 #ifdef AVT_CONV_STAMP
 // diagnostic build only (`make stamp` -> libavt_hip_stamp.so, never the shipped library): the hooks live in tools/diag
 #include "../../tools/diag/conv_stamp.h"
@@ -147,8 +148,8 @@ __global__ __launch_bounds__(256, AVT_CONV_MIN_WAVES(BM, BN, WTM)) void conv_ige
     }
   };
 
-  const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void*)a.in, 0, a.in_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rwt = __builtin_amdgcn_make_buffer_rsrc((void*)a.wt, 0, a.wt_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rin = avt::buffer_rsrc(a.in, a.in_bytes);
+  const __amdgpu_buffer_rsrc_t rwt = avt::buffer_rsrc(a.wt, a.wt_bytes);
   int2* ltab = reinterpret_cast<int2*>(lds + STAGE);  // [nk*8] behind the operand slabs
   if constexpr (TABLDS) {
     for (int i = tid; i < a.nk * 8; i += 256) ltab[i] = a.ktab[i];
@@ -398,8 +399,8 @@ __global__ __launch_bounds__(XT, 2) void conv_xl_kernel(ConvArgs a) {
   // instruction, no 64-bit address arithmetic.  The tap decode of a unit is wave-uniform (Cin % 32 == 0: the unit's 4
   // chunks share a tap), so it runs on the scalar unit; a lane adds its chunk.  Phase A is issue-bound (one wave,
   // ~140 instructions against the other group's 16 MFMAs), so every VALU instruction here is on the critical path.
-  const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void*)a.in, 0, a.in_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rwt = __builtin_amdgcn_make_buffer_rsrc((void*)a.wt, 0, a.wt_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rin = avt::buffer_rsrc(a.in, a.in_bytes);
+  const __amdgpu_buffer_rsrc_t rwt = avt::buffer_rsrc(a.wt, a.wt_bytes);
   const int nu = (a.K + 31) / 32;  // pipeline units
   const int swid = __builtin_amdgcn_readfirstlane(wid);  // wave-uniform in an SGPR: LDS destinations stay scalar
   unsigned rowb[AIW], wrowb[BIW];  // byte offsets of this lane's rows (+ its chunk within a unit), OOB when absent
@@ -673,8 +674,8 @@ __global__ __launch_bounds__(XT, 2) void conv_xb_kernel(ConvArgs a) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
 
-  const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void*)a.in, 0, a.in_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rwf = __builtin_amdgcn_make_buffer_rsrc((void*)a.wfrag, 0, a.wf_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rin = avt::buffer_rsrc(a.in, a.in_bytes);
+  const __amdgpu_buffer_rsrc_t rwf = avt::buffer_rsrc(a.wfrag, a.wf_bytes);
   const int nu = (a.K + 31) / 32;
   const int swid = __builtin_amdgcn_readfirstlane(wid);
   // this wave's weight fragments of unit i: tile (n0/32 + 2 wn + n), k-slice ks -> byte ((tile * nup + i) * 2 + ks) * 1024

@@ -36,6 +36,7 @@
 
 #include "avt_common.h"
 #include "conv_args.h"
+#include "mfma.h"
 #include "split_planes.h"
 
 #ifdef AVT_CONV_STAMP
@@ -72,19 +73,9 @@ namespace {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-template <bool F16>
-__device__ __forceinline__ f32x16 mfma(i32x4 w, i32x4 x, f32x16 c) {
-  if constexpr (F16)
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, w), __builtin_bit_cast(f16x8, x), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), c, 0, 0, 0);
-}
+using avt::f32x16;
+using avt::i32x4;
+using avt::mfma32;
 
 // IO32: the TRAINING form (train_ops.conv3d: forward and stride-1 dgrad of the SlowFast convolutions, train.py:114-141) —
 // activations are read as fp32 NDHWC rows and split into the two planes in registers on their way to the LDS (same number
@@ -209,9 +200,9 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(ConvArgs a) {
 #pragma unroll
       for (int j = 0; j < MT; ++j) {
         if (!DBG_SKIP(2)) {
-          acc[i][j] = mfma<F16>(f.wl[i], f.ah[j], acc[i][j]);
-          acc[i][j] = mfma<F16>(f.wh[i], f.al[j], acc[i][j]);
-          acc[i][j] = mfma<F16>(f.wh[i], f.ah[j], acc[i][j]);
+          acc[i][j] = mfma32<F16>(f.wl[i], f.ah[j], acc[i][j]);
+          acc[i][j] = mfma32<F16>(f.wh[i], f.al[j], acc[i][j]);
+          acc[i][j] = mfma32<F16>(f.wh[i], f.ah[j], acc[i][j]);
         }
         if (more && !DBG_SKIP(4)) {
 #pragma unroll
@@ -240,10 +231,10 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(ConvArgs a) {
     fmul(f1, 3 * NT * MT, more, piece);
   };
 
-  const __amdgpu_buffer_rsrc_t rih = __builtin_amdgcn_make_buffer_rsrc((void*)a.in, 0, a.in_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t ril = __builtin_amdgcn_make_buffer_rsrc((void*)a.in_lo, 0, a.in_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rwh = __builtin_amdgcn_make_buffer_rsrc((void*)a.wt, 0, a.wt_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rwl = __builtin_amdgcn_make_buffer_rsrc((void*)a.wt_lo, 0, a.wt_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rih = avt::buffer_rsrc(a.in, a.in_bytes);
+  const __amdgpu_buffer_rsrc_t ril = avt::buffer_rsrc(a.in_lo, a.in_bytes);
+  const __amdgpu_buffer_rsrc_t rwh = avt::buffer_rsrc(a.wt, a.wt_bytes);
+  const __amdgpu_buffer_rsrc_t rwl = avt::buffer_rsrc(a.wt_lo, a.wt_bytes);
   int2* ltab = reinterpret_cast<int2*>(lds + STAGE);
   const bool tab_lds = a.nk <= kMaxTabSteps;  // uniform
   if (tab_lds)
@@ -475,9 +466,8 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(ConvArgs a) {
         }
         float* of = reinterpret_cast<float*>(a.out) + o;
         // (whole 128-byte lines of a tensor far larger than the caches: non-temporal stores, +0.8 % on the training step)
-        typedef float f32x4n __attribute__((ext_vector_type(4)));
-        __builtin_nontemporal_store(f32x4n{x[0], x[1], x[2], x[3]}, reinterpret_cast<f32x4n*>(of));
-        __builtin_nontemporal_store(f32x4n{x[4], x[5], x[6], x[7]}, reinterpret_cast<f32x4n*>(of + 4));
+        avt::stg4(of, avt::f32x4{x[0], x[1], x[2], x[3]});
+        avt::stg4(of + 4, avt::f32x4{x[4], x[5], x[6], x[7]});
       } else {
         uint4 oh, ol;
         avt::split8<F16>(x, oh, ol);
@@ -587,10 +577,10 @@ __global__ __launch_bounds__(512, 2) void conv_x3_xl_kernel(ConvArgs a) {
     for (int j = 0; j < MT; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-  const __amdgpu_buffer_rsrc_t rih = __builtin_amdgcn_make_buffer_rsrc((void*)a.in, 0, a.in_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t ril = __builtin_amdgcn_make_buffer_rsrc((void*)a.in_lo, 0, a.in_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rwh = __builtin_amdgcn_make_buffer_rsrc((void*)a.wt, 0, a.wt_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rwl = __builtin_amdgcn_make_buffer_rsrc((void*)a.wt_lo, 0, a.wt_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rih = avt::buffer_rsrc(a.in, a.in_bytes);
+  const __amdgpu_buffer_rsrc_t ril = avt::buffer_rsrc(a.in_lo, a.in_bytes);
+  const __amdgpu_buffer_rsrc_t rwh = avt::buffer_rsrc(a.wt, a.wt_bytes);
+  const __amdgpu_buffer_rsrc_t rwl = avt::buffer_rsrc(a.wt_lo, a.wt_bytes);
   int2* ltab = reinterpret_cast<int2*>(lds + 2 * STG);
   // (the tap table always lives in the LDS here — the launcher routes longer K loops to the 128 x 128 tile: a table read
   //  that may be global or LDS compiles to a FLAT load, whose use waits for every fragment read issued before it)
@@ -690,9 +680,9 @@ __global__ __launch_bounds__(512, 2) void conv_x3_xl_kernel(ConvArgs a) {
     for (int i = 0; i < NT; ++i)
 #pragma unroll
       for (int j = 0; j < MT; ++j) {
-        acc[i][j] = mfma<F16>(f.wl[i], f.ah[j], acc[i][j]);
-        acc[i][j] = mfma<F16>(f.wh[i], f.al[j], acc[i][j]);
-        acc[i][j] = mfma<F16>(f.wh[i], f.ah[j], acc[i][j]);
+        acc[i][j] = mfma32<F16>(f.wl[i], f.ah[j], acc[i][j]);
+        acc[i][j] = mfma32<F16>(f.wh[i], f.al[j], acc[i][j]);
+        acc[i][j] = mfma32<F16>(f.wh[i], f.ah[j], acc[i][j]);
         const int pc = g0 + i * MT + j + (IO32 ? 2 * AU : 0);  // (IO32: the weight pieces only)
         if (more && pc < NPIECE) gpiece(pc, nst);  // the next step's DMA, one piece per MFMA triple of the first k-slice
         __builtin_amdgcn_sched_barrier(0);
@@ -913,9 +903,8 @@ __global__ __launch_bounds__(512, 2) void conv_x3_xl_kernel(ConvArgs a) {
             }
           }
           float* of = reinterpret_cast<float*>(a.out) + o;
-          typedef float f32x4n __attribute__((ext_vector_type(4)));
-          __builtin_nontemporal_store(f32x4n{x[0], x[1], x[2], x[3]}, reinterpret_cast<f32x4n*>(of));
-          __builtin_nontemporal_store(f32x4n{x[4], x[5], x[6], x[7]}, reinterpret_cast<f32x4n*>(of + 4));
+          avt::stg4(of, avt::f32x4{x[0], x[1], x[2], x[3]});
+          avt::stg4(of + 4, avt::f32x4{x[4], x[5], x[6], x[7]});
         } else {
           uint4 oh, ol;
           avt::split8<F16>(x, oh, ol);

@@ -18,12 +18,13 @@
 #include <stdlib.h>
 
 #include "avt_common.h"
+#include "mfma.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
+using avt::bf16x8;
+using avt::f32x4;
+using avt::i32x4;
 
 struct PwArgs {
   const uint16_t* x1;   // [M, ldx]   first layer's input rows (k1c valid 16-byte chunks each)

@@ -19,14 +19,14 @@
 #include <type_traits>
 
 #include "avt_common.h"
+#include "mfma.h"
 #include "split_planes.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
+using avt::f32x4;
+using avt::i32x4;
+using avt::mfma16;
 
 struct PxArgs {
   const uint16_t* xh;  // [M, ldx] input planes
@@ -49,14 +49,6 @@ struct PxArgs {
   int taps, cin8, T, To, HW, tst, tpad;
   int n_valid;  // output channels that exist (the last 16-channel tile pair may be padding: cout 16 runs as one pair)
 };
-
-template <bool F16>
-__device__ __forceinline__ f32x4 mfma16(i32x4 w, i32x4 x, f32x4 c) {
-  if constexpr (F16)
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, w), __builtin_bit_cast(f16x8, x), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), c, 0, 0, 0);
-}
 
 constexpr int PX_NW = 8;
 // phase-skip diagnostic (tools/probe_pw_phases.sh builds one library per -DAVT_PW_DBG_CONST=n: 1 no stores, 2 no MFMAs,
@@ -550,26 +542,25 @@ __global__ __launch_bounds__(PX_NW * 64) void pw_x3_f32_kernel(PfArgs a) {
         }
       }
     };
-    typedef float f32x4n __attribute__((ext_vector_type(4)));
-    f32x4n hv[4];  // (STATS = 2: the second statistic's addends of one pass)
+    f32x4 hv[4];  // (STATS = 2: the second statistic's addends of one pass)
     auto epilogue = [&](auto j0_, auto j1_) {
 #pragma unroll
     for (int jj = decltype(j0_)::value; jj < decltype(j1_)::value; ++jj) {  // tiles 2jj, 2jj+1 -> channels c0 + 32 jj + 8 q .. + 7
       const int cl = 32 * jj + 8 * q;
-      f32x4n o0, o1;
+      f32x4 o0, o1;
       if constexpr (STATS == 2) {  // (gradients: bf16 planes, no row scales — and no 4 NT1 scale registers held across the tile loop)
-        o0 = f32x4n{acc[2 * jj][0], acc[2 * jj][1], acc[2 * jj][2], acc[2 * jj][3]};
-        o1 = f32x4n{acc[2 * jj + 1][0], acc[2 * jj + 1][1], acc[2 * jj + 1][2], acc[2 * jj + 1][3]};
+        o0 = f32x4{acc[2 * jj][0], acc[2 * jj][1], acc[2 * jj][2], acc[2 * jj][3]};
+        o1 = f32x4{acc[2 * jj + 1][0], acc[2 * jj + 1][1], acc[2 * jj + 1][2], acc[2 * jj + 1][3]};
       } else {
         const float4 sa = *reinterpret_cast<const float4*>(sl + cl), sb = *reinterpret_cast<const float4*>(sl + cl + 4);
-        o0 = f32x4n{acc[2 * jj][0] * sa.x, acc[2 * jj][1] * sa.y, acc[2 * jj][2] * sa.z, acc[2 * jj][3] * sa.w};
-        o1 = f32x4n{acc[2 * jj + 1][0] * sb.x, acc[2 * jj + 1][1] * sb.y, acc[2 * jj + 1][2] * sb.z, acc[2 * jj + 1][3] * sb.w};
+        o0 = f32x4{acc[2 * jj][0] * sa.x, acc[2 * jj][1] * sa.y, acc[2 * jj][2] * sa.z, acc[2 * jj][3] * sa.w};
+        o1 = f32x4{acc[2 * jj + 1][0] * sb.x, acc[2 * jj + 1][1] * sb.y, acc[2 * jj + 1][2] * sb.z, acc[2 * jj + 1][3] * sb.w};
       }
       if (has_add) {
-        o0 += f32x4n{ra[jj].x, ra[jj].y, ra[jj].z, ra[jj].w};
-        o1 += f32x4n{rb[jj].x, rb[jj].y, rb[jj].z, rb[jj].w};
+        o0 += f32x4{ra[jj].x, ra[jj].y, ra[jj].z, ra[jj].w};
+        o1 += f32x4{rb[jj].x, rb[jj].y, rb[jj].z, rb[jj].w};
       }
-      f32x4n v0 = {0.f, 0.f, 0.f, 0.f}, v1 = v0;  // STATS = 2: g * (x - mean), the second statistic's addends
+      f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = v0;  // STATS = 2: g * (x - mean), the second statistic's addends
       if constexpr (STATS == 2) {  // o becomes g = mask * dz (what is stored)
         // (coefficients through an offset that is opaque per tile: read at constant addresses they are loop-invariant, and the
         //  compiler kept all 24 x NT1 / 2 of them in registers across the tile loop — 54-108 spilled registers)
@@ -591,25 +582,25 @@ __global__ __launch_bounds__(PX_NW * 64) void pw_x3_f32_kernel(PfArgs a) {
           gg[e] = sel != 0.0f ? gg[e] : 0.0f;
           vv[e] = gg[e] * xc[e];
         }
-        o0 = f32x4n{gg[0], gg[1], gg[2], gg[3]};
-        o1 = f32x4n{gg[4], gg[5], gg[6], gg[7]};
-        v0 = f32x4n{vv[0], vv[1], vv[2], vv[3]};
-        v1 = f32x4n{vv[4], vv[5], vv[6], vv[7]};
+        o0 = f32x4{gg[0], gg[1], gg[2], gg[3]};
+        o1 = f32x4{gg[4], gg[5], gg[6], gg[7]};
+        v0 = f32x4{vv[0], vv[1], vv[2], vv[3]};
+        v1 = f32x4{vv[4], vv[5], vv[6], vv[7]};
       }
       if (ok) {
         float* po = a.y + pc * a.ldy + c0 + cl;
-        __builtin_nontemporal_store(o0, reinterpret_cast<f32x4n*>(po));
-        __builtin_nontemporal_store(o1, reinterpret_cast<f32x4n*>(po + 4));
+        avt::stg4(po, o0);
+        avt::stg4(po + 4, o1);
       }
       if constexpr (STATS == 2) {
         // as below, with two blocks per pass: g for the first statistic, g * (x - mean) for the second (held in registers — at
         // most two octets — until the first block has been read back)
         constexpr int JPP = PS::PW / 32;
         const int jl = jj % JPP;
-        if (!ok) o0 = o1 = v0 = v1 = f32x4n{0.f, 0.f, 0.f, 0.f};
+        if (!ok) o0 = o1 = v0 = v1 = f32x4{0.f, 0.f, 0.f, 0.f};
         float* pw_ = scr + l15 * PS::RS + 32 * jl + 8 * q;
-        *reinterpret_cast<f32x4n*>(pw_) = o0;
-        *reinterpret_cast<f32x4n*>(pw_ + 4) = o1;
+        *reinterpret_cast<f32x4*>(pw_) = o0;
+        *reinterpret_cast<f32x4*>(pw_ + 4) = o1;
         if (jl == 0) { hv[0] = v0; hv[1] = v1; } else { hv[2] = v0; hv[3] = v1; }
         if (jl == JPP - 1) {
           constexpr int NR = PS::PW == 64 ? 16 : 8;
@@ -624,8 +615,8 @@ __global__ __launch_bounds__(PX_NW * 64) void pw_x3_f32_kernel(PfArgs a) {
 #pragma unroll
           for (int k = 0; k < JPP; ++k) {
             float* pv = scr + l15 * PS::RS + 32 * k + 8 * q;
-            *reinterpret_cast<f32x4n*>(pv) = hv[2 * k];
-            *reinterpret_cast<f32x4n*>(pv + 4) = hv[2 * k + 1];
+            *reinterpret_cast<f32x4*>(pv) = hv[2 * k];
+            *reinterpret_cast<f32x4*>(pv + 4) = hv[2 * k + 1];
           }
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
           if (PS::PW >= 32 || lane < PS::PW) {
@@ -643,10 +634,10 @@ __global__ __launch_bounds__(PX_NW * 64) void pw_x3_f32_kernel(PfArgs a) {
         // order, so a wait on the counter is the only synchronisation; no cross-lane traffic, 8 accumulator registers per pass
         constexpr int JPP = PS::PW / 32;  // jj's per pass
         const int jl = jj % JPP;
-        if (!ok) o0 = o1 = f32x4n{0.f, 0.f, 0.f, 0.f};
+        if (!ok) o0 = o1 = f32x4{0.f, 0.f, 0.f, 0.f};
         float* pw_ = scr + l15 * PS::RS + 32 * jl + 8 * q;
-        *reinterpret_cast<f32x4n*>(pw_) = o0;
-        *reinterpret_cast<f32x4n*>(pw_ + 4) = o1;
+        *reinterpret_cast<f32x4*>(pw_) = o0;
+        *reinterpret_cast<f32x4*>(pw_ + 4) = o1;
         if (jl == JPP - 1) {
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
           constexpr int NR = PS::PW == 64 ? 16 : 8;

@@ -38,6 +38,7 @@
 #include <type_traits>
 
 #include "avt_common.h"
+#include "mfma.h"
 #include "split_planes.h"
 
 namespace {
@@ -80,29 +81,18 @@ __device__ unsigned long long g_r2_stamp[10];
 #define R2_ST(i)
 #define R2_ST_END()
 #endif
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
+using avt::f32x4;
+using avt::i32x4;
 constexpr unsigned kOob = 0xFFFFFFF0u;
 
-template <bool F16>
-__device__ __forceinline__ f32x4 mfma(i32x4 w, i32x4 x, f32x4 c) {
-  if constexpr (F16)
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, w), __builtin_bit_cast(f16x8, x), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), c, 0, 0, 0);
-}
-// one split-plane product, small terms first (conv_x3.hip's order)
+// avt::mfma3 behind the phase-skip diagnostic
 template <bool F16>
 __device__ __forceinline__ f32x4 mfma3(i32x4 wh, i32x4 wl, i32x4 xh, i32x4 xl, f32x4 c) {
   if (R2_SKIP(16)) {  // diagnostic: the operands stay live (one VALU op each), no matrix instruction
     c[0] += __builtin_bit_cast(float, wh[0] ^ wl[1] ^ xh[2] ^ xl[3]);
     return c;
   }
-  c = mfma<F16>(wl, xh, c);
-  c = mfma<F16>(wh, xl, c);
-  return mfma<F16>(wh, xh, c);
+  return avt::mfma3<F16>(wh, wl, xh, xl, c);
 }
 
 constexpr int C = 256, CM = 64;
@@ -190,11 +180,11 @@ __global__ __launch_bounds__(NWV * 64) void res2_x3_kernel(R2Args a) {
   const int s1 = s0 + a.spw < a.nsteps ? s0 + a.spw : a.nsteps;
   if (s0 >= s1) return;
 
-  const __amdgpu_buffer_rsrc_t rxh = __builtin_amdgcn_make_buffer_rsrc((void*)a.xh, 0, a.x_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rxl = __builtin_amdgcn_make_buffer_rsrc((void*)a.xl, 0, a.x_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t roh = __builtin_amdgcn_make_buffer_rsrc((void*)a.oh, 0, a.o_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rol = __builtin_amdgcn_make_buffer_rsrc((void*)a.ol, 0, a.o_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rwf = __builtin_amdgcn_make_buffer_rsrc((void*)a.wf, 0, a.w_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rxh = avt::buffer_rsrc(a.xh, a.x_bytes);
+  const __amdgpu_buffer_rsrc_t rxl = avt::buffer_rsrc(a.xl, a.x_bytes);
+  const __amdgpu_buffer_rsrc_t roh = avt::buffer_rsrc(a.oh, a.o_bytes);
+  const __amdgpu_buffer_rsrc_t rol = avt::buffer_rsrc(a.ol, a.o_bytes);
+  const __amdgpu_buffer_rsrc_t rwf = avt::buffer_rsrc(a.wf, a.w_bytes);
 
   // weight chunk `cc` (0 .. NCH-1, the same stream every step) -> rotation buffer `buf`: this wave's 1 KB pieces
   auto dma_chunk = [&](int cc, int buf) {

@@ -23,11 +23,13 @@
 // rows padded to 144 B so each 16-lane ds_read_b128 group (16 distinct rows at
 // one k-offset) touches all 64 banks once.  Roofline: MFMA (2*nq*nt*d flop).
 #include "avt_common.h"
+#include "mfma.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+using avt::bf16x8;
+using avt::f32x16;
+using avt::i32x4;
 
 constexpr int BM = 128;
 constexpr int ROWB = 128;        // data bytes per row per K-step
@@ -280,8 +282,8 @@ __global__ __launch_bounds__(256, 4) void sim_f32_v2_kernel(Args a, unsigned q_b
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.0f;
 
-  const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void*)a.q[0], 0, q_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc((void*)a.t[0], 0, t_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rq = avt::buffer_rsrc(a.q[0], q_bytes);
+  const __amdgpu_buffer_rsrc_t rt = avt::buffer_rsrc(a.t[0], t_bytes);
   // this thread's two chunks of each operand: rows r, r + 64 of the tile, 16-byte chunk c4 of the 64-byte row
   const int r = tid >> 2, c4 = tid & 3;
   unsigned qo[2], to_[2];
@@ -292,7 +294,6 @@ __global__ __launch_bounds__(256, 4) void sim_f32_v2_kernel(Args a, unsigned q_b
     to_[u] = tr < a.nt ? (unsigned)((tr * a.d + c4 * 4) * 4) : kOobS;
   }
   const int kc = c4 * 4;  // first k of this thread's chunk inside a K-step
-  typedef int i32x4 __attribute__((ext_vector_type(4)));
   i32x4 ra[2], rb[2];
   auto gpiece = [&](int kt, int p) {
     const int k0 = kt * 16;

@@ -5,9 +5,6 @@
 
 namespace avt {
 
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 // fp32 pair -> packed (hi, lo) planes, both round-to-nearest-even; x - hi is exact in fp32.
 // F16 = false: bf16 planes (8 + 8 significant bits, |x - hi - lo| <= 2^-16 |x| at every magnitude; 2^-17 observed).
 // F16 = true : fp16 planes (11 + 11 bits, <= 2^-22 |x| while lo stays a normal fp16, i.e. |x| >= 2^-3; below that the

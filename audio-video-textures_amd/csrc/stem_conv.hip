@@ -25,26 +25,18 @@
 #include <stdlib.h>
 
 #include "avt_common.h"
+#include "mfma.h"
 #include "split_planes.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+using avt::f32x4;
+using avt::i32x4;
+using avt::mfma16;
 constexpr unsigned kOob = 0xFFFFFFF0u;
 
 // PL = 0: bf16 (one plane per tensor).  PL = 1 / 2: the contract-grade split-plane arithmetic (conv_x3.hip) with bf16 /
 // fp16 planes: the patch and the weight slab are staged for both planes and every product is three MFMAs.
-template <int PL>
-__device__ __forceinline__ f32x4 mfma16(i32x4 w, i32x4 x, f32x4 c) {
-  if constexpr (PL == 2)
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, w), __builtin_bit_cast(f16x8, x), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), c, 0, 0, 0);
-}
-
 struct StemArgs {
   const uint16_t* in;
   const uint16_t* wt;
@@ -145,10 +137,10 @@ __global__ __launch_bounds__(POOL ? 512 : 256, POOL ? 4 : (PL ? 2 : 3)) void ste
   const int ho0 = hg * OWN - (POOL ? 1 : 0);  // first conv row computed (may be -1: its result is unused)
   const int n_base = cgi * (NT * 16);
 
-  const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void*)a.in, 0, a.in_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rwt = __builtin_amdgcn_make_buffer_rsrc((void*)a.wt, 0, a.wt_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rinl = __builtin_amdgcn_make_buffer_rsrc((void*)(PL ? a.in_lo : a.in), 0, a.in_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rwtl = __builtin_amdgcn_make_buffer_rsrc((void*)(PL ? a.wt_lo : a.wt), 0, a.wt_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rin = avt::buffer_rsrc(a.in, a.in_bytes);
+  const __amdgpu_buffer_rsrc_t rwt = avt::buffer_rsrc(a.wt, a.wt_bytes);
+  const __amdgpu_buffer_rsrc_t rinl = avt::buffer_rsrc(PL ? a.in_lo : a.in, a.in_bytes);
+  const __amdgpu_buffer_rsrc_t rwtl = avt::buffer_rsrc(PL ? a.wt_lo : a.wt, a.wt_bytes);
 
   // per-thread patch chunks: byte offset inside a frame, or out of bounds (padding rows / pairs)
   unsigned poff[PU];
@@ -263,13 +255,13 @@ __global__ __launch_bounds__(POOL ? 512 : 256, POOL ? 4 : (PL ? 2 : 3)) void ste
 #pragma unroll
           for (int n = 0; n < NT; ++n) {  // small terms first: wl*ah + wh*al + wh*ah
             if (!act[n]) continue;
-            acc[i][n] = mfma16<PL>(bfl[n], af, acc[i][n]);
-            acc[i][n] = mfma16<PL>(bf[n], afl, acc[i][n]);
-            acc[i][n] = mfma16<PL>(bf[n], af, acc[i][n]);
+            acc[i][n] = mfma16<PL == 2>(bfl[n], af, acc[i][n]);
+            acc[i][n] = mfma16<PL == 2>(bf[n], afl, acc[i][n]);
+            acc[i][n] = mfma16<PL == 2>(bf[n], af, acc[i][n]);
           }
         } else {
 #pragma unroll
-          for (int n = 0; n < NT; ++n) acc[i][n] = mfma16<0>(bf[n], af, acc[i][n]);  // D[channel][position]
+          for (int n = 0; n < NT; ++n) acc[i][n] = mfma16<false>(bf[n], af, acc[i][n]);  // D[channel][position]
         }
       }
     }

@@ -24,14 +24,15 @@
 // is read once per step and used by every (output row r, row tap dh) with 2 r + dh = j.
 // Roofline: MFMA (3 x the bf16 work; the padded columns 112 -> 128 and the sixth frame tap are issued work, not algorithmic).
 #include "avt_common.h"
+#include "mfma.h"
 #include "split_planes.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
+using avt::f32x4;
+using avt::i32x4;
+using avt::lds_tr_frag;
+using avt::mfma16;
 
 // ---- clip -> pixel-pair planes -------------------------------------------------------------------------------------------
 struct CpArgs {
@@ -79,17 +80,6 @@ struct SwArgs {
   unsigned x_bytes;
 };
 
-__device__ __forceinline__ f32x4 mfma(i32x4 a, i32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
-__device__ __forceinline__ i32x4 tr_frag(const char* lds, int a0, int a1) {
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  const uint2 u = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(lds + a0)));
-  const uint2 v = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(lds + a1)));
-  return i32x4{(int)u.x, (int)u.y, (int)v.x, (int)v.y};
-}
-
 // KT frame taps; CO = output channels a workgroup owns per position row in the LDS (8: the fast stem; 16: a 16-channel slice
 // of the slow stem's 64, blockIdx.y walks the slices)
 template <int KT, int CO>
@@ -129,8 +119,8 @@ __global__ __launch_bounds__(NTHR, 2) void stem_wgrad_kernel(SwArgs a) {
   // inside a dY row: channel chunk tp of the 16 columns = (frame tap tp >> 1 of the pair, channels 4 (tp & 1) ..) for CO = 8
   const int ya = CO == 8 ? (tp >> 1) * (RB * YROW) + pos0 * 16 + 8 * (tp & 1) : pos0 * 32 + 8 * tp;
 
-  const __amdgpu_buffer_rsrc_t rxh = __builtin_amdgcn_make_buffer_rsrc((void*)a.x_hi, 0, a.x_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rxl = __builtin_amdgcn_make_buffer_rsrc((void*)a.x_lo, 0, a.x_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rxh = avt::buffer_rsrc(a.x_hi, a.x_bytes);
+  const __amdgpu_buffer_rsrc_t rxl = avt::buffer_rsrc(a.x_lo, a.x_bytes);
   const int pcols = a.PW + 4;                   // chunks of a row that can hold pixels (pairs -2 .. PW + 1)
 
   for (int unit = blockIdx.x; unit < a.nunit; unit += gridDim.x) {
@@ -181,20 +171,20 @@ __global__ __launch_bounds__(NTHR, 2) void stem_wgrad_kernel(SwArgs a) {
 #pragma unroll
         for (int r = 0; r < RB; ++r) {
           const int a0 = 2 * PPL + (pp * FP * RB + r) * YROW + ya, a1 = a0 + 4 * (CO * 2);
-          yh[r] = tr_frag(lds, a0, a1);
-          yl[r] = tr_frag(lds, a0 + YPL, a1 + YPL);
+          yh[r] = lds_tr_frag(lds, a0, a1);
+          yl[r] = lds_tr_frag(lds, a0 + YPL, a1 + YPL);
         }
 #pragma unroll
         for (int j = 0; j < PROWS; ++j) {
           const int o = j * (PWP * 16) + xa;
-          const i32x4 xh = tr_frag(lds, o, o + 64), xl = tr_frag(lds, PPL + o, PPL + o + 64);
+          const i32x4 xh = lds_tr_frag(lds, o, o + 64), xl = lds_tr_frag(lds, PPL + o, PPL + o + 64);
 #pragma unroll
           for (int r = 0; r < RB; ++r) {
             const int dh = j - 2 * r;
             if (dh < 0 || dh >= 7) continue;  // compile-time
-            acc[pp][dh] = mfma(xl, yh[r], acc[pp][dh]);  // small terms first
-            acc[pp][dh] = mfma(xh, yl[r], acc[pp][dh]);
-            acc[pp][dh] = mfma(xh, yh[r], acc[pp][dh]);
+            acc[pp][dh] = mfma16<false>(xl, yh[r], acc[pp][dh]);  // small terms first
+            acc[pp][dh] = mfma16<false>(xh, yl[r], acc[pp][dh]);
+            acc[pp][dh] = mfma16<false>(xh, yh[r], acc[pp][dh]);
           }
         }
       }

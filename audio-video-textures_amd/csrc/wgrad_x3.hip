@@ -28,6 +28,7 @@
 
 #include "avt_common.h"
 #include "conv_args.h"
+#include "mfma.h"
 
 // phase-skip diagnostic (tools/probe_wgrad_phases.py against a library built with -DAVT_WGRAD_DBG_CONST=n: 1 skip the LDS
 // stage, 2 the MFMAs, 4 the global loads): compile-time, the shipped library carries no switch
@@ -38,9 +39,12 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
+using avt::bf16x2;
+using avt::f32x16;
+using avt::f32x2;
+using avt::i32x4;
+using avt::lds_tr_frag;
+using avt::mfma32;
 
 constexpr int kMaxTaps = 28;   // taps the position table holds with two workgroups per CU (3x3x3 = 27; the 7x1x1 lateral ones = 7)
 constexpr int kMaxTapsBig = 49;  // ... with one workgroup per CU ([1,7,7]: the stems)
@@ -59,14 +63,6 @@ struct WgArgs {
   int pointwise;               // 1x1x1 / stride 1 / no padding: input row = output position
   unsigned x_bytes, dy_bytes;  // the pipelined tile's buffer loads (tensors below kRowOob bytes, or the phase-serial tile runs)
 };
-
-__device__ __forceinline__ f32x16 mfma(i32x4 a, i32x4 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kPlane = 64 * 256;  // one plane of one operand: [64 positions][128 channels x 2 B]
 // BUF forms (tensors below 4 GB): the position tables hold BYTE offsets of rows, kRowOob for "no row"; a thread adds its channel's
@@ -165,8 +161,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_x3_kernel(WgArgs a) {
       xtab[(buf * 64 + p) * a.tapcap + tap] = in ? enc((((bb * a.T + ti) * a.H + hi) * a.W + wi) * a.ldx) : none;
     }
   };
-  const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, a.x_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsy = __builtin_amdgcn_make_buffer_rsrc((void*)a.dy, 0, a.dy_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsx = avt::buffer_rsrc(a.x, a.x_bytes);
+  const __amdgpu_buffer_rsrc_t rsy = avt::buffer_rsrc(a.dy, a.dy_bytes);
   float4 rq[RQ], sq[SQ];
   unsigned rmask = 0u, smask = 0u;  // which pieces are real (the others are zeroed when they are staged, not when they are loaded)
   // Table reads first, all of them, then the 16-byte loads, all unconditional (an out-of-range piece reads the tensor's
@@ -265,33 +261,27 @@ __global__ __launch_bounds__(256, 2) void wgrad_x3_kernel(WgArgs a) {
 #pragma unroll
     for (int h2 = 0; h2 < 2; ++h2)
       saddr[i][h2] = S_HI + swz(8 * (g >> 1) + 4 * h2 + tq, (wn * WN + i * 32 + 16 * (g & 1)) / 8 + (tp >> 1)) + 8 * (tp & 1);
-  auto frag = [&](int a0, int a1) {
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    const uint2 u = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(lds + a0)));
-    const uint2 v = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(lds + a1)));
-    return i32x4{(int)u.x, (int)u.y, (int)v.x, (int)v.y};
-  };
   auto compute = [&]() {
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       i32x4 rh[MT], rl[MT], sh_[NT], sl[NT];
 #pragma unroll
       for (int j = 0; j < MT; ++j) {
-        rh[j] = frag(raddr[j][0] + 4096 * ks, raddr[j][1] + 4096 * ks);
-        rl[j] = frag(raddr[j][0] + kPlane + 4096 * ks, raddr[j][1] + kPlane + 4096 * ks);
+        rh[j] = lds_tr_frag(lds, raddr[j][0] + 4096 * ks, raddr[j][1] + 4096 * ks);
+        rl[j] = lds_tr_frag(lds, raddr[j][0] + kPlane + 4096 * ks, raddr[j][1] + kPlane + 4096 * ks);
       }
 #pragma unroll
       for (int i = 0; i < NT; ++i) {
-        sh_[i] = frag(saddr[i][0] + 4096 * ks, saddr[i][1] + 4096 * ks);
-        sl[i] = frag(saddr[i][0] + kPlane + 4096 * ks, saddr[i][1] + kPlane + 4096 * ks);
+        sh_[i] = lds_tr_frag(lds, saddr[i][0] + 4096 * ks, saddr[i][1] + 4096 * ks);
+        sl[i] = lds_tr_frag(lds, saddr[i][0] + kPlane + 4096 * ks, saddr[i][1] + kPlane + 4096 * ks);
       }
 #pragma unroll
       for (int i = 0; i < NT; ++i)
 #pragma unroll
         for (int j = 0; j < MT; ++j) {
-          acc[i][j] = mfma(sl[i], rh[j], acc[i][j]);  // small terms first
-          acc[i][j] = mfma(sh_[i], rl[j], acc[i][j]);
-          acc[i][j] = mfma(sh_[i], rh[j], acc[i][j]);
+          acc[i][j] = mfma32<false>(sl[i], rh[j], acc[i][j]);  // small terms first
+          acc[i][j] = mfma32<false>(sh_[i], rl[j], acc[i][j]);
+          acc[i][j] = mfma32<false>(sh_[i], rh[j], acc[i][j]);
         }
     }
   };
@@ -467,8 +457,8 @@ __global__ __launch_bounds__(512, 1) void wgrad_x3_xl_kernel(WgArgs a) {
   unsigned* const ytab = reinterpret_cast<unsigned*>(lds + XTABS);   // [4][32] byte offsets of dy rows
   unsigned* const xtab = ytab + 4 * XP;                              // [4][32][tapcap] ... of x rows under every tap
   int* const ttab = reinterpret_cast<int*>(xtab + 4 * XP * kMaxTaps); // [taps]: dt | dh << 8 | dw << 16 (see the 128-wide tile)
-  const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, a.x_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsy = __builtin_amdgcn_make_buffer_rsrc((void*)a.dy, 0, a.dy_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsx = avt::buffer_rsrc(a.x, a.x_bytes);
+  const __amdgpu_buffer_rsrc_t rsy = avt::buffer_rsrc(a.dy, a.dy_bytes);
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid / WS, wn = wid % WS;
@@ -595,21 +585,15 @@ __global__ __launch_bounds__(512, 1) void wgrad_x3_xl_kernel(WgArgs a) {
     const char* const stg = lds;
     auto& raddr = *(P ? &raddr1 : &raddr0_);
     auto& saddr = *(P ? &saddr1 : &saddr0_);
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    auto frag = [&](int a0, int a1) {
-      const uint2 u = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(stg + a0)));
-      const uint2 v = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(stg + a1)));
-      return i32x4{(int)u.x, (int)u.y, (int)v.x, (int)v.y};
-    };
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-      f.rh[j] = frag(raddr[j][0] + 4096 * ks, raddr[j][1] + 4096 * ks);
-      f.rl[j] = frag(raddr[j][0] + XPL + 4096 * ks, raddr[j][1] + XPL + 4096 * ks);
+      f.rh[j] = lds_tr_frag(stg, raddr[j][0] + 4096 * ks, raddr[j][1] + 4096 * ks);
+      f.rl[j] = lds_tr_frag(stg, raddr[j][0] + XPL + 4096 * ks, raddr[j][1] + XPL + 4096 * ks);
     }
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
-      f.sh[i] = frag(saddr[i][0] + 4096 * ks, saddr[i][1] + 4096 * ks);
-      f.sl[i] = frag(saddr[i][0] + XPL + 4096 * ks, saddr[i][1] + XPL + 4096 * ks);
+      f.sh[i] = lds_tr_frag(stg, saddr[i][0] + 4096 * ks, saddr[i][1] + 4096 * ks);
+      f.sl[i] = lds_tr_frag(stg, saddr[i][0] + XPL + 4096 * ks, saddr[i][1] + XPL + 4096 * ks);
     }
   };
   auto fmul = [&](const Frags& f) {
@@ -617,9 +601,9 @@ __global__ __launch_bounds__(512, 1) void wgrad_x3_xl_kernel(WgArgs a) {
     for (int i = 0; i < NI; ++i)
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
-        acc[i][j] = mfma(f.sl[i], f.rh[j], acc[i][j]);  // small terms first
-        acc[i][j] = mfma(f.sh[i], f.rl[j], acc[i][j]);
-        acc[i][j] = mfma(f.sh[i], f.rh[j], acc[i][j]);
+        acc[i][j] = mfma32<false>(f.sl[i], f.rh[j], acc[i][j]);  // small terms first
+        acc[i][j] = mfma32<false>(f.sh[i], f.rl[j], acc[i][j]);
+        acc[i][j] = mfma32<false>(f.sh[i], f.rh[j], acc[i][j]);
       }
   };
   typedef std::integral_constant<int, 0> S0;
