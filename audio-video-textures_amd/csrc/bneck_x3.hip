@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "avt_common.h"
+#include "launch.h"
 #include "mfma.h"
 #include "split_planes.h"
 
@@ -472,15 +473,8 @@ int launch(BxArgs& a, int batch, int h, hipStream_t st) {
   static_assert(lds_bytes <= 160 * 1024, "strips do not fit the LDS");
   a.strips = (h / ST + HT - 1) / HT;
   a.swz = 1;  // XCD-contiguous work order
-  static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(bneck_x3_kernel<C, W, HT, CMP, CIN, ST, NW, F16>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  if (e != hipSuccess) {
-    avt::set_error("avt_bneck_x3: hipFuncSetAttribute(%d B LDS): %s", lds_bytes, hipGetErrorString(e));
-    return AVT_ERR_LAUNCH;
-  }
-  hipLaunchKernelGGL((bneck_x3_kernel<C, W, HT, CMP, CIN, ST, NW, F16>), dim3((unsigned)(batch * a.strips * a.tchunks)), dim3(NW * 64),
-                     lds_bytes, st, a);
-  return avt::check_launch("avt_bneck_x3");
+  return avt::launch<bneck_x3_kernel<C, W, HT, CMP, CIN, ST, NW, F16>>("avt_bneck_x3", dim3((unsigned)(batch * a.strips * a.tchunks)),
+                                                                       dim3(NW * 64), lds_bytes, lds_bytes, st, a);
 }
 
 template <bool F16>

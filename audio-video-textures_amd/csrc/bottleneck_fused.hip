@@ -25,6 +25,7 @@
 #include <stdlib.h>
 
 #include "avt_common.h"
+#include "launch.h"
 #include "mfma.h"
 
 namespace {
@@ -353,15 +354,8 @@ int launch(BArgs& a, int batch, int h, hipStream_t st) {
   static_assert(lds_bytes <= 160 * 1024, "strip does not fit the LDS");
   a.strips = (h / ST + HT - 1) / HT;
   a.swz = 1;
-  static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(bottleneck_kernel<C, W, HT, CMP, CIN, ST, NW>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  if (e != hipSuccess) {
-    avt::set_error("avt_bottleneck_fused_bf16: hipFuncSetAttribute(%d B LDS): %s", lds_bytes, hipGetErrorString(e));
-    return AVT_ERR_LAUNCH;
-  }
-  hipLaunchKernelGGL((bottleneck_kernel<C, W, HT, CMP, CIN, ST, NW>), dim3((unsigned)(batch * a.strips * a.tchunks)), dim3(NW * 64),
-                     lds_bytes, st, a);
-  return avt::check_launch("avt_bottleneck_fused_bf16");
+  return avt::launch<bottleneck_kernel<C, W, HT, CMP, CIN, ST, NW>>("avt_bottleneck_fused_bf16", dim3((unsigned)(batch * a.strips * a.tchunks)),
+                                                                    dim3(NW * 64), lds_bytes, lds_bytes, st, a);
 }
 
 }  // namespace

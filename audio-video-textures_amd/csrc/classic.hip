@@ -9,6 +9,7 @@
 //                runs every sweep without leaving the kernel: wave-per-row minima, barrier, update + fp64 residual, barrier.
 //                Same fp32 arithmetic as the reference (one rounded multiply, one rounded add per element).
 #include "avt_common.h"
+#include "launch.h"
 
 namespace {
 
@@ -106,13 +107,6 @@ extern "C" int avt_q_learning_f32(const float* d3, int n, float alpha, float tol
   AVT_REQUIRE(avt_q_learning_supported(n), "avt_q_learning_f32: the matrix must be 2..200 rows square (LDS-resident), got %d", n);
   AVT_REQUIRE(max_iter > 0, "avt_q_learning_f32: max_iter must be positive");
   const int lds_bytes = n * n * 4;
-  static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(q_learning_kernel),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, 200 * 200 * 4);
-  if (e != hipSuccess) {
-    avt::set_error("avt_q_learning_f32: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    return AVT_ERR_LAUNCH;
-  }
-  hipLaunchKernelGGL(q_learning_kernel, dim3(1), dim3(QT), lds_bytes, static_cast<hipStream_t>(stream), d3, n, alpha, tol, max_iter,
-                     out, iters);
-  return avt::check_launch("avt_q_learning_f32");
+  return avt::launch<q_learning_kernel>("avt_q_learning_f32", dim3(1), dim3(QT), 200 * 200 * 4, lds_bytes, static_cast<hipStream_t>(stream),
+                                        d3, n, alpha, tol, max_iter, out, iters);
 }

@@ -12,6 +12,7 @@
 #include <stdlib.h>
 
 #include "avt_common.h"
+#include "launch.h"
 #include "mfma.h"
 
 namespace {
@@ -162,14 +163,7 @@ int launch(C33Args& a, int batch, int h, hipStream_t st) {
   a.strips = (h + HT - 1) / HT;
   constexpr int swz = 1;  // XCD-contiguous work order
   a.swz = swz;
-  static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(c33_kernel<W, HT>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  if (e != hipSuccess) {
-    avt::set_error("avt_conv33_c64_bf16: hipFuncSetAttribute(%d B LDS): %s", lds_bytes, hipGetErrorString(e));
-    return AVT_ERR_LAUNCH;
-  }
-  hipLaunchKernelGGL((c33_kernel<W, HT>), dim3((unsigned)(batch * a.strips)), dim3(NWV * 64), lds_bytes, st, a);
-  return avt::check_launch("avt_conv33_c64_bf16");
+  return avt::launch<c33_kernel<W, HT>>("avt_conv33_c64_bf16", dim3((unsigned)(batch * a.strips)), dim3(NWV * 64), lds_bytes, lds_bytes, st, a);
 }
 
 }  // namespace

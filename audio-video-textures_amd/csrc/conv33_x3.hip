@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "avt_common.h"
+#include "launch.h"
 #include "mfma.h"
 #include "split_planes.h"
 
@@ -237,17 +238,9 @@ extern "C" int avt_conv33_x3(const void* x_hi, const void* x_lo, const void* wfr
   a.o_bytes = (unsigned)(m * ldo * 2);
   constexpr int lds_bytes = NFR * 1024 + 128 * 4;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  auto kern = plane_dtype == AVT_X3_F16 ? conv33_x3_kernel<true> : conv33_x3_kernel<false>;
-  static const hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(conv33_x3_kernel<true>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  static const hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(conv33_x3_kernel<false>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  if (e1 != hipSuccess || e2 != hipSuccess) {
-    avt::set_error("avt_conv33_x3: hipFuncSetAttribute(%d B LDS) failed", lds_bytes);
-    return AVT_ERR_LAUNCH;
-  }
   int grid = (a.ntiles + NW - 1) / NW;
   if (grid > 256) grid = 256;  // persistent: one workgroup per CU (147 KB of weights each)
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NW * 64), lds_bytes, st, a);
-  return avt::check_launch("avt_conv33_x3");
+  if (plane_dtype == AVT_X3_F16)
+    return avt::launch<conv33_x3_kernel<true>>("avt_conv33_x3", dim3((unsigned)grid), dim3(NW * 64), lds_bytes, lds_bytes, st, a);
+  return avt::launch<conv33_x3_kernel<false>>("avt_conv33_x3", dim3((unsigned)grid), dim3(NW * 64), lds_bytes, lds_bytes, st, a);
 }

@@ -173,16 +173,25 @@ __device__ __forceinline__ int out_row(const ConvArgs& a, int m) {
 }
 
 
+// The geometry arguments of the convolution entry points (everything between `ktab` and `stream` in include/avt.h), by name:
+// each extern "C" entry fills one from its own parameters and everything below takes it by reference.
+struct ConvGeom {
+  int batch, t, h, w, cin, cout;
+  int kt, kh, kw, st, sh, sw, pt, ph, pw;
+  int to, ho, wo;  // output extent, 0 = the symmetric-padding formula
+  int ldi, ldo, ldr;
+  int relu;
+  int out_row_stride, out_h, out_w;  // output row remap (1, 0, 0: none)
+};
+
 // Validates the C-ABI arguments and fills the launch-independent part of ConvArgs (one bf16 plane per tensor; the x3
 // entry adds its low-order planes afterwards).  `who` names the entry point in error messages.
 inline int conv_args_fill(ConvArgs& a, const char* who, const void* in, const void* wt, const float* bias,
-                          const void* res, void* out, const int32_t* ktab, int batch, int t, int h, int w, int cin,
-                          int cout, int kt, int kh, int kw, int st, int sh, int sw, int pt, int ph, int pw, int to, int ho,
-                          int wo, int ldi, int ldo, int ldr, int relu, int out_row_stride, int out_h, int out_w) {
+                          const void* res, void* out, const int32_t* ktab, const ConvGeom& g) {
   AVT_REQUIRE(in && wt && out && ktab, "%s: NULL pointer", who);
-  AVT_REQUIRE(cin > 0 && cin % 8 == 0 && cout > 0 && cout % 8 == 0, "%s: Cin/Cout must be multiples of 8", who);
-  AVT_REQUIRE(kt >= 1 && kh >= 1 && kw >= 1 && kt <= 8 && kh <= 8 && kw <= 8, "%s: kernel extents must be 1..8", who);
-  AVT_REQUIRE(ldi % 8 == 0 && ldo % 8 == 0 && (!res || ldr % 8 == 0) && ldi >= cin && ldo >= cout,
+  AVT_REQUIRE(g.cin > 0 && g.cin % 8 == 0 && g.cout > 0 && g.cout % 8 == 0, "%s: Cin/Cout must be multiples of 8", who);
+  AVT_REQUIRE(g.kt >= 1 && g.kh >= 1 && g.kw >= 1 && g.kt <= 8 && g.kh <= 8 && g.kw <= 8, "%s: kernel extents must be 1..8", who);
+  AVT_REQUIRE(g.ldi % 8 == 0 && g.ldo % 8 == 0 && (!res || g.ldr % 8 == 0) && g.ldi >= g.cin && g.ldo >= g.cout,
               "%s: leading dimensions must be multiples of 8 and cover the channels", who);
   AVT_REQUIRE(avt::aligned16(in) && avt::aligned16(wt) && avt::aligned16(out) && (!res || avt::aligned16(res)) &&
                   (!bias || avt::aligned16(bias)),
@@ -193,61 +202,61 @@ inline int conv_args_fill(ConvArgs& a, const char* who, const void* in, const vo
   a.res = static_cast<const uint16_t*>(res);
   a.out = static_cast<uint16_t*>(out);
   a.ktab = reinterpret_cast<const int2*>(ktab);
-  a.T = t;
-  a.H = h;
-  a.W = w;
+  a.T = g.t;
+  a.H = g.h;
+  a.W = g.w;
   // output extent: 0 = the symmetric-padding formula; a smaller explicit extent crops the far edge
   // (used by the stem, whose pixel-pair form needs padding 2 on the left and 1 on the right)
-  const int fto = (t + 2 * pt - kt) / st + 1, fho = (h + 2 * ph - kh) / sh + 1, fwo = (w + 2 * pw - kw) / sw + 1;
-  a.To = to > 0 ? to : fto;
-  a.Ho = ho > 0 ? ho : fho;
-  a.Wo = wo > 0 ? wo : fwo;
+  const int fto = (g.t + 2 * g.pt - g.kt) / g.st + 1, fho = (g.h + 2 * g.ph - g.kh) / g.sh + 1, fwo = (g.w + 2 * g.pw - g.kw) / g.sw + 1;
+  a.To = g.to > 0 ? g.to : fto;
+  a.Ho = g.ho > 0 ? g.ho : fho;
+  a.Wo = g.wo > 0 ? g.wo : fwo;
   // (an explicit extent may also reach past the formula's by up to k - 1 positions: padding on the far side only — every tap is
   //  bounds-checked against the input by the kernels; avt_conv3d_igemm_x3_f32_ex)
-  AVT_REQUIRE(a.To > 0 && a.Ho > 0 && a.Wo > 0 && batch > 0 && a.To <= fto + (kt - 1) / st && a.Ho <= fho + (kh - 1) / sh &&
-                  a.Wo <= fwo + (kw - 1) / sw,
-              "%s: bad output extent %dx%dx%d (max %dx%dx%d)", who, a.To, a.Ho, a.Wo, fto + (kt - 1) / st, fho + (kh - 1) / sh,
-              fwo + (kw - 1) / sw);
-  a.Cout = cout;
-  a.K = kt * kh * kw * cin;
-  a.KT = kt;
-  a.KH = kh;
-  a.KW = kw;
-  a.st = st;
-  a.sh = sh;
-  a.sw = sw;
-  a.pt = pt;
-  a.ph = ph;
-  a.pw = pw;
-  a.ldi = ldi;
-  a.ldo = ldo;
-  a.ldr = ldr;
-  a.relu = relu;
-  const int64_t M = (int64_t)batch * a.To * a.Ho * a.Wo;
-  AVT_REQUIRE(M < (1ll << 31) && (int64_t)batch * t * h * w * ldi < (1ll << 31) - 64 && M * (int64_t)ldo < (1ll << 62) &&
-                  (int64_t)cout * a.K < (1ll << 31) - 64,
+  AVT_REQUIRE(a.To > 0 && a.Ho > 0 && a.Wo > 0 && g.batch > 0 && a.To <= fto + (g.kt - 1) / g.st && a.Ho <= fho + (g.kh - 1) / g.sh &&
+                  a.Wo <= fwo + (g.kw - 1) / g.sw,
+              "%s: bad output extent %dx%dx%d (max %dx%dx%d)", who, a.To, a.Ho, a.Wo, fto + (g.kt - 1) / g.st, fho + (g.kh - 1) / g.sh,
+              fwo + (g.kw - 1) / g.sw);
+  a.Cout = g.cout;
+  a.K = g.kt * g.kh * g.kw * g.cin;
+  a.KT = g.kt;
+  a.KH = g.kh;
+  a.KW = g.kw;
+  a.st = g.st;
+  a.sh = g.sh;
+  a.sw = g.sw;
+  a.pt = g.pt;
+  a.ph = g.ph;
+  a.pw = g.pw;
+  a.ldi = g.ldi;
+  a.ldo = g.ldo;
+  a.ldr = g.ldr;
+  a.relu = g.relu;
+  const int64_t M = (int64_t)g.batch * a.To * a.Ho * a.Wo;
+  AVT_REQUIRE(M < (1ll << 31) && (int64_t)g.batch * g.t * g.h * g.w * g.ldi < (1ll << 31) - 64 && M * (int64_t)g.ldo < (1ll << 62) &&
+                  (int64_t)g.cout * a.K < (1ll << 31) - 64,
               "%s: tensor too large for 32-bit offsets", who);
-  a.in_bytes = (unsigned)((int64_t)batch * t * h * w * ldi * 2);
-  a.wt_bytes = (unsigned)((int64_t)cout * a.K * 2);
+  a.in_bytes = (unsigned)((int64_t)g.batch * g.t * g.h * g.w * g.ldi * 2);
+  a.wt_bytes = (unsigned)((int64_t)g.cout * a.K * 2);
   a.M = (int)M;
   a.nk = (a.K + BK - 1) / BK;
-  a.pointwise = (kt == 1 && kh == 1 && kw == 1 && st == 1 && sh == 1 && sw == 1 && pt == 0 && ph == 0 && pw == 0 &&
-                 a.To == t && a.Ho == h && a.Wo == w) ? 1 : 0;
+  a.pointwise = (g.kt == 1 && g.kh == 1 && g.kw == 1 && g.st == 1 && g.sh == 1 && g.sw == 1 && g.pt == 0 && g.ph == 0 && g.pw == 0 &&
+                 a.To == g.t && a.Ho == g.h && a.Wo == g.w) ? 1 : 0;
   a.dWo = make_fastdiv((uint32_t)a.Wo);
   a.dHo = make_fastdiv((uint32_t)a.Ho);
   a.dTo = make_fastdiv((uint32_t)a.To);
   // (out_row_stride 1 with an out_h x out_w grid: the frame's rows land at the top-left of a larger frame — one temporal class
   //  of a strided transposed convolution, train_ops._dgrad_strided)
-  const bool remap = out_row_stride > 1 || (out_h > 0 && out_w > 0);
-  AVT_REQUIRE(out_row_stride >= 1 && (!remap || (!res && out_h >= out_row_stride * (a.Ho - 1) + 1 &&
-                                                 out_w >= out_row_stride * (a.Wo - 1) + 1)),
+  const bool remap = g.out_row_stride > 1 || (g.out_h > 0 && g.out_w > 0);
+  AVT_REQUIRE(g.out_row_stride >= 1 && (!remap || (!res && g.out_h >= g.out_row_stride * (a.Ho - 1) + 1 &&
+                                                   g.out_w >= g.out_row_stride * (a.Wo - 1) + 1)),
               "%s: the remapped rows need an out_h x out_w grid that holds %d x (%d x %d), no residual", who,
-              out_row_stride, a.Ho, a.Wo);
-  AVT_REQUIRE(!remap || (int64_t)batch * a.To * out_h * out_w < (1ll << 31),
+              g.out_row_stride, a.Ho, a.Wo);
+  AVT_REQUIRE(!remap || (int64_t)g.batch * a.To * g.out_h * g.out_w < (1ll << 31),
               "%s: output buffer too large for 32-bit rows", who);
-  a.ors = out_row_stride;
-  a.oH = remap ? out_h : 0;
-  a.oW = remap ? out_w : 0;
+  a.ors = g.out_row_stride;
+  a.oH = remap ? g.out_h : 0;
+  a.oW = remap ? g.out_w : 0;
   a.stat_part = nullptr;
   a.odiv = 0.0f;
   a.stat_groups = a.stat_mg = a.stat_tpg = a.stat_c = 0;

@@ -35,6 +35,7 @@
 
 #include "avt_common.h"
 #include "conv_args.h"
+#include "launch.h"
 #include "mfma.h"
 
 namespace {
@@ -287,16 +288,8 @@ int launch(ConvArgs& a, hipStream_t st) {
   constexpr int epass = (BM * (BN * 2 + 16) <= lds_main) ? 1 : BM / WTM;
   constexpr int lds_epi = (BM / epass) * (BN * 2 + 16);
   constexpr int lds_bytes = lds_main > lds_epi ? lds_main : lds_epi;
-  if (lds_bytes > 64 * 1024) {  // above the default dynamic-LDS limit: opt in once per kernel
-    static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_igemm_kernel<BM, BN, WTM, TABLDS>),
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    if (e != hipSuccess) {
-      avt::set_error("avt_conv3d_igemm_bf16: hipFuncSetAttribute(%d B LDS): %s", lds_bytes, hipGetErrorString(e));
-      return AVT_ERR_LAUNCH;
-    }
-  }
-  hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WTM, TABLDS>), dim3((unsigned)a.nblk), dim3(256), lds_bytes, st, a);
-  return avt::check_launch("avt_conv3d_igemm_bf16");
+  return avt::launch<conv_igemm_kernel<BM, BN, WTM, TABLDS>>("avt_conv3d_igemm_bf16", dim3((unsigned)a.nblk), dim3(256), lds_bytes, lds_bytes,
+                                                             st, a);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -875,14 +868,7 @@ int launch_xb(ConvArgs& a, hipStream_t st) {
   a.tapinner = 1;
   // (conv_xb_kernel<true>: the activation DMA issued in the fragment-read phase, +1-5 % per layer, profiles/r01/probe_ab_chain.log)
   constexpr int lds_bytes = 128 * (256 * 2 + 16) > 4 * 256 * 64 ? 128 * (256 * 2 + 16) : 4 * 256 * 64;
-  static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_xb_kernel<true>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  if (e != hipSuccess) {
-    avt::set_error("avt_conv3d_igemm_bf16: hipFuncSetAttribute(%d B LDS): %s", lds_bytes, hipGetErrorString(e));
-    return AVT_ERR_LAUNCH;
-  }
-  hipLaunchKernelGGL((conv_xb_kernel<true>), dim3((unsigned)a.nblk), dim3(XT), lds_bytes, st, a);
-  return avt::check_launch("avt_conv3d_igemm_bf16");
+  return avt::launch<conv_xb_kernel<true>>("avt_conv3d_igemm_bf16", dim3((unsigned)a.nblk), dim3(XT), lds_bytes, lds_bytes, st, a);
 }
 
 
@@ -897,14 +883,7 @@ int launch_xl(ConvArgs& a, hipStream_t st) {
   a.dNT = make_fastdiv((uint32_t)(a.KT * a.KH * a.KW));
   a.tapinner = a.KT * a.KH * a.KW > 1 ? 1 : 0;  // taps innermost: a chunk's per-tap re-reads meet in L2 (+3-5 %, round 1)
   constexpr int lds_bytes = XRING * (XBM + XBN) * 64;
-  static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_xl_kernel<XBM, XBN, WM>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  if (e != hipSuccess) {
-    avt::set_error("avt_conv3d_igemm_bf16: hipFuncSetAttribute(%d B LDS): %s", lds_bytes, hipGetErrorString(e));
-    return AVT_ERR_LAUNCH;
-  }
-  hipLaunchKernelGGL((conv_xl_kernel<XBM, XBN, WM>), dim3((unsigned)a.nblk), dim3(XT), lds_bytes, st, a);
-  return avt::check_launch("avt_conv3d_igemm_bf16");
+  return avt::launch<conv_xl_kernel<XBM, XBN, WM>>("avt_conv3d_igemm_bf16", dim3((unsigned)a.nblk), dim3(XT), lds_bytes, lds_bytes, st, a);
 }
 
 }  // namespace
@@ -959,9 +938,11 @@ extern "C" int avt_conv3d_igemm_wfrag_bf16(const void* in, const void* wt, const
                                            int kh, int kw, int st, int sh, int sw, int pt, int ph, int pw, int to, int ho,
                                            int wo, int ldi, int ldo, int ldr, int relu, int out_row_stride, int out_h,
                                            int out_w, const void* wfrag, int nup, void* stream) {
+  const ConvGeom g = {.batch = batch, .t = t, .h = h, .w = w, .cin = cin, .cout = cout, .kt = kt, .kh = kh, .kw = kw,
+                      .st = st, .sh = sh, .sw = sw, .pt = pt, .ph = ph, .pw = pw, .to = to, .ho = ho, .wo = wo,
+                      .ldi = ldi, .ldo = ldo, .ldr = ldr, .relu = relu, .out_row_stride = out_row_stride, .out_h = out_h, .out_w = out_w};
   ConvArgs a;
-  const int rc = conv_args_fill(a, "avt_conv3d_igemm_bf16", in, wt, bias, res, out, ktab, batch, t, h, w, cin, cout, kt, kh, kw,
-                                st, sh, sw, pt, ph, pw, to, ho, wo, ldi, ldo, ldr, relu, out_row_stride, out_h, out_w);
+  const int rc = conv_args_fill(a, "avt_conv3d_igemm_bf16", in, wt, bias, res, out, ktab, g);
   if (rc != AVT_OK) return rc;
   a.wfrag = static_cast<const uint16_t*>(wfrag);
   a.nup = nup;

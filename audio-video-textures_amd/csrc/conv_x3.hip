@@ -36,6 +36,7 @@
 
 #include "avt_common.h"
 #include "conv_args.h"
+#include "launch.h"
 #include "mfma.h"
 #include "split_planes.h"
 
@@ -939,17 +940,11 @@ int launch_x3_xl(ConvArgs& a, hipStream_t st) {
   const int tiles_m = a.stat_part ? a.stat_groups * a.stat_tpg : (a.M + 255) / 256;
   a.tiles_n = (a.Cout + 255) / 256;
   a.nblk = tiles_m * a.tiles_n;
-  constexpr int lds_max = 2 * 4 * 256 * 64 + kMaxTabSteps * 64 + 2 * 256 * 4;
-  const int lds_bytes = lds_max;  // (the epilogue's second staging buffer reaches into the table area; then bias | scale)
-  a.cf_ofs = lds_max - 2 * 256 * 4;
-  static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_x3_xl_kernel<F16, IO32, OUT32>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-  if (e != hipSuccess) {
-    avt::set_error("avt_conv3d_igemm_x3: hipFuncSetAttribute(%d B LDS): %s", lds_max, hipGetErrorString(e));
-    return AVT_ERR_LAUNCH;
-  }
-  hipLaunchKernelGGL((conv_x3_xl_kernel<F16, IO32, OUT32>), dim3((unsigned)a.nblk), dim3(512), lds_bytes, st, a);
-  return avt::check_launch("avt_conv3d_igemm_x3");
+  // (the epilogue's second staging buffer reaches into the table area; then bias | scale)
+  constexpr int lds_bytes = 2 * 4 * 256 * 64 + kMaxTabSteps * 64 + 2 * 256 * 4;
+  a.cf_ofs = lds_bytes - 2 * 256 * 4;
+  return avt::launch<conv_x3_xl_kernel<F16, IO32, OUT32>>("avt_conv3d_igemm_x3", dim3((unsigned)a.nblk), dim3(512), lds_bytes, lds_bytes,
+                                                          st, a);
 }
 
 template <int BM, int BN, int WTM, bool F16, bool IO32 = false, bool BST = false>
@@ -968,15 +963,28 @@ int launch_x3(ConvArgs& a, hipStream_t st) {
   if (lds_bytes < epi_bytes) lds_bytes = epi_bytes;
   a.cf_ofs = lds_bytes;       // the tile's bias | scale floats behind the operand slabs / the table / the epilogue staging
   lds_bytes += 2 * BN * 4;
-  static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_x3_kernel<BM, BN, WTM, F16, IO32, BST>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-  if (e != hipSuccess) {
-    avt::set_error("avt_conv3d_igemm_x3: hipFuncSetAttribute(%d B LDS): %s", lds_max, hipGetErrorString(e));
-    return AVT_ERR_LAUNCH;
-  }
-  hipLaunchKernelGGL((conv_x3_kernel<BM, BN, WTM, F16, IO32, BST>), dim3((unsigned)a.nblk), dim3(256), lds_bytes, st, a);
-  return avt::check_launch("avt_conv3d_igemm_x3");
+  return avt::launch<conv_x3_kernel<BM, BN, WTM, F16, IO32, BST>>("avt_conv3d_igemm_x3", dim3((unsigned)a.nblk), dim3(256), lds_max,
+                                                                  lds_bytes, st, a);
 }
+
+// The 128-row tiles by output width; `small`: the 64-row tile for the wide layers (io32_tile_rows; the IO32 forms only)
+template <bool F16, bool IO32 = false, bool BST = false>
+int launch_x3_by_cout(ConvArgs& a, hipStream_t st, bool small = false) {
+  if (a.Cout <= 32) return launch_x3<128, 32, 32, F16, IO32, BST>(a, st);
+  if (a.Cout <= 64) return launch_x3<128, 64, 64, F16, IO32, BST>(a, st);
+  if constexpr (IO32) {
+    if (small) return launch_x3<64, 128, 32, F16, IO32, BST>(a, st);
+  }
+  return launch_x3<128, 128, 64, F16, IO32, BST>(a, st);
+}
+
+// the two planes of every tensor of avt_conv3d_igemm_x3
+struct X3Planes {
+  const void *in_hi, *in_lo, *wt_hi, *wt_lo;
+  const float* bias;
+  const void *res_hi, *res_lo;
+  void *out_hi, *out_lo;
+};
 
 }  // namespace
 
@@ -987,26 +995,20 @@ extern "C" int avt_conv3d_igemm_x3_xl_picked(int cout, int k, int m) {
 
 // one launch: every plane of the input within 32-bit byte offsets (conv_args_fill).  xl = the tile the WHOLE layer runs on
 // (avt_conv3d_igemm_x3_xl_picked of all its rows): the frame ranges of a split layer stay on one tile and one weight order
-static int igemm_x3_one(const void* in_hi, const void* in_lo, const void* wt_hi, const void* wt_lo,
-                        const float* bias, const void* res_hi, const void* res_lo, void* out_hi, void* out_lo,
-                        const int32_t* ktab, int batch, int t, int h, int w, int cin, int cout, int kt, int kh,
-                        int kw, int st, int sh, int sw, int pt, int ph, int pw, int to, int ho, int wo, int ldi,
-                        int ldo, int ldr, int relu, int out_row_stride, int out_h, int out_w, int plane_dtype,
-                        const float* wscale, void* stream, int wblk, int xl) {
+static int igemm_x3_one(const X3Planes& p, const int32_t* ktab, const ConvGeom& g, int plane_dtype, const float* wscale, void* stream,
+                        int wblk, int xl) {
   AVT_REQUIRE(plane_dtype == AVT_X3_BF16 || plane_dtype == AVT_X3_F16, "avt_conv3d_igemm_x3: plane_dtype must be 0 (bf16) or 1 (fp16)");
   AVT_REQUIRE(!wscale || avt::aligned16(wscale), "avt_conv3d_igemm_x3: wscale must be 16-byte aligned");
-  AVT_REQUIRE(in_lo && wt_lo && out_lo && (!res_hi == !res_lo), "avt_conv3d_igemm_x3: every tensor needs both planes");
-  AVT_REQUIRE(avt::aligned16(in_lo) && avt::aligned16(wt_lo) && avt::aligned16(out_lo) && (!res_lo || avt::aligned16(res_lo)),
+  AVT_REQUIRE(p.in_lo && p.wt_lo && p.out_lo && (!p.res_hi == !p.res_lo), "avt_conv3d_igemm_x3: every tensor needs both planes");
+  AVT_REQUIRE(avt::aligned16(p.in_lo) && avt::aligned16(p.wt_lo) && avt::aligned16(p.out_lo) && (!p.res_lo || avt::aligned16(p.res_lo)),
               "avt_conv3d_igemm_x3: pointers must be 16-byte aligned");
   ConvArgs a;
-  const int rc = conv_args_fill(a, "avt_conv3d_igemm_x3", in_hi, wt_hi, bias, res_hi, out_hi, ktab, batch, t, h, w, cin, cout,
-                                kt, kh, kw, st, sh, sw, pt, ph, pw, to, ho, wo, ldi, ldo, ldr, relu, out_row_stride, out_h,
-                                out_w);
+  const int rc = conv_args_fill(a, "avt_conv3d_igemm_x3", p.in_hi, p.wt_hi, p.bias, p.res_hi, p.out_hi, ktab, g);
   if (rc != AVT_OK) return rc;
-  a.in_lo = static_cast<const uint16_t*>(in_lo);
-  a.wt_lo = static_cast<const uint16_t*>(wt_lo);
-  a.res_lo = static_cast<const uint16_t*>(res_lo);
-  a.out_lo = static_cast<uint16_t*>(out_lo);
+  a.in_lo = static_cast<const uint16_t*>(p.in_lo);
+  a.wt_lo = static_cast<const uint16_t*>(p.wt_lo);
+  a.res_lo = static_cast<const uint16_t*>(p.res_lo);
+  a.out_lo = static_cast<uint16_t*>(p.out_lo);
   a.wscale = wscale;
   a.wfrag = nullptr;
   a.nup = 0;
@@ -1016,14 +1018,7 @@ static int igemm_x3_one(const void* in_hi, const void* in_lo, const void* wt_hi,
   AVT_REQUIRE(!wblk || (xl && a.K % 32 == 0),
               "avt_conv3d_igemm_x3_wblk: K-blocked weights are the 256 x 256 tile's (avt_conv3d_igemm_x3_xl_picked, K %% 32 == 0)");
   if (xl) return plane_dtype == AVT_X3_F16 ? launch_x3_xl<true>(a, s) : launch_x3_xl<false>(a, s);
-  if (plane_dtype == AVT_X3_F16) {
-    if (cout <= 32) return launch_x3<128, 32, 32, true>(a, s);
-    if (cout <= 64) return launch_x3<128, 64, 64, true>(a, s);
-    return launch_x3<128, 128, 64, true>(a, s);
-  }
-  if (cout <= 32) return launch_x3<128, 32, 32, false>(a, s);
-  if (cout <= 64) return launch_x3<128, 64, 64, false>(a, s);
-  return launch_x3<128, 128, 64, false>(a, s);
+  return plane_dtype == AVT_X3_F16 ? launch_x3_by_cout<true>(a, s) : launch_x3_by_cout<false>(a, s);
 }
 
 // Both tiles address the activations through 32-bit byte offsets into a buffer resource (rowoff = m * ldi, aoffs = (rowoff + tap) * 2),
@@ -1035,52 +1030,51 @@ static int igemm_x3_one(const void* in_hi, const void* in_lo, const void* wt_hi,
 // 32-bit, their byte offsets 64-bit (out_row).  The limit NOW: one frame's plane h * w * ldi < 2^31 - 64 elements for kt = 1 layers
 // (all frames together as before for layers with temporal taps), and fewer than 2^31 output rows (and remapped rows) per layer;
 // anything past it is rejected with AVT_ERR_ARG.
-static int igemm_x3_impl(const void* in_hi, const void* in_lo, const void* wt_hi, const void* wt_lo,
-                         const float* bias, const void* res_hi, const void* res_lo, void* out_hi, void* out_lo,
-                         const int32_t* ktab, int batch, int t, int h, int w, int cin, int cout, int kt, int kh,
-                         int kw, int st, int sh, int sw, int pt, int ph, int pw, int to, int ho, int wo, int ldi,
-                         int ldo, int ldr, int relu, int out_row_stride, int out_h, int out_w, int plane_dtype,
-                         const float* wscale, void* stream, int wblk) {
+static int igemm_x3_impl(const X3Planes& p, const int32_t* ktab, const ConvGeom& g, int plane_dtype, const float* wscale, void* stream,
+                         int wblk) {
   constexpr int64_t kMaxPlane = (1ll << 31) - 64;  // elements of one input plane per launch
-  const bool sane = batch > 0 && t > 0 && h > 0 && w > 0 && ldi > 0 && ldo > 0 && cin > 0 && cout > 0 && kt >= 1 && kh >= 1 && kw >= 1 &&
-                    st >= 1 && sh >= 1 && sw >= 1 && ph >= 0 && pw >= 0 && ho >= 0 && wo >= 0 && out_row_stride >= 1 && out_h >= 0 && out_w >= 0;
-  const int64_t frame = sane ? (int64_t)h * w * ldi : 0, frames = sane ? (int64_t)batch * t : 0;
-  if (!sane || frame * frames < kMaxPlane || kt != 1 || st != 1 || pt != 0 || (to != 0 && to != t)) {
+  const bool sane = g.batch > 0 && g.t > 0 && g.h > 0 && g.w > 0 && g.ldi > 0 && g.ldo > 0 && g.cin > 0 && g.cout > 0 && g.kt >= 1 &&
+                    g.kh >= 1 && g.kw >= 1 && g.st >= 1 && g.sh >= 1 && g.sw >= 1 && g.ph >= 0 && g.pw >= 0 && g.ho >= 0 && g.wo >= 0 &&
+                    g.out_row_stride >= 1 && g.out_h >= 0 && g.out_w >= 0;
+  const int64_t frame = sane ? (int64_t)g.h * g.w * g.ldi : 0, frames = sane ? (int64_t)g.batch * g.t : 0;
+  if (!sane || frame * frames < kMaxPlane || g.kt != 1 || g.st != 1 || g.pt != 0 || (g.to != 0 && g.to != g.t)) {
     // one launch (or conv_args_fill's rejection: bad arguments, or temporal taps over a plane past the limit)
-    const int64_t k_all = (int64_t)kt * kh * kw * cin;
+    const int64_t k_all = (int64_t)g.kt * g.kh * g.kw * g.cin;
     int xl = 0;
     if (sane && k_all < (1ll << 31)) {
-      const int64_t fho = ho > 0 ? ho : (h + 2 * ph - kh) / sh + 1, fwo = wo > 0 ? wo : (w + 2 * pw - kw) / sw + 1;
-      const int64_t fto = to > 0 ? to : (t + 2 * pt - kt) / st + 1;
-      const int64_t m = (int64_t)batch * fto * fho * fwo;
-      xl = (m > 0 && m < (1ll << 31)) ? avt_conv3d_igemm_x3_xl_picked(cout, (int)k_all, (int)m) : 0;
+      const int64_t fho = g.ho > 0 ? g.ho : (g.h + 2 * g.ph - g.kh) / g.sh + 1, fwo = g.wo > 0 ? g.wo : (g.w + 2 * g.pw - g.kw) / g.sw + 1;
+      const int64_t fto = g.to > 0 ? g.to : (g.t + 2 * g.pt - g.kt) / g.st + 1;
+      const int64_t m = (int64_t)g.batch * fto * fho * fwo;
+      xl = (m > 0 && m < (1ll << 31)) ? avt_conv3d_igemm_x3_xl_picked(g.cout, (int)k_all, (int)m) : 0;
     }
-    return igemm_x3_one(in_hi, in_lo, wt_hi, wt_lo, bias, res_hi, res_lo, out_hi, out_lo, ktab, batch, t, h, w, cin, cout, kt, kh, kw, st,
-                        sh, sw, pt, ph, pw, to, ho, wo, ldi, ldo, ldr, relu, out_row_stride, out_h, out_w, plane_dtype, wscale, stream, wblk,
-                        xl);
+    return igemm_x3_one(p, ktab, g, plane_dtype, wscale, stream, wblk, xl);
   }
-  AVT_REQUIRE(frame < kMaxPlane, "avt_conv3d_igemm_x3: one frame's input plane (%d x %d x %d elements) is too large for 32-bit offsets", h, w,
-              ldi);
-  AVT_REQUIRE(in_hi && in_lo && out_hi && out_lo && (!res_hi == !res_lo), "avt_conv3d_igemm_x3: every tensor needs both planes");
-  const int fho = ho > 0 ? ho : (h + 2 * ph - kh) / sh + 1, fwo = wo > 0 ? wo : (w + 2 * pw - kw) / sw + 1;
+  AVT_REQUIRE(frame < kMaxPlane, "avt_conv3d_igemm_x3: one frame's input plane (%d x %d x %d elements) is too large for 32-bit offsets", g.h,
+              g.w, g.ldi);
+  AVT_REQUIRE(p.in_hi && p.in_lo && p.out_hi && p.out_lo && (!p.res_hi == !p.res_lo), "avt_conv3d_igemm_x3: every tensor needs both planes");
+  const int fho = g.ho > 0 ? g.ho : (g.h + 2 * g.ph - g.kh) / g.sh + 1, fwo = g.wo > 0 ? g.wo : (g.w + 2 * g.pw - g.kw) / g.sw + 1;
   AVT_REQUIRE(fho > 0 && fwo > 0, "avt_conv3d_igemm_x3: bad output extent");
-  const bool remap = out_row_stride > 1 || (out_h > 0 && out_w > 0);
+  const bool remap = g.out_row_stride > 1 || (g.out_h > 0 && g.out_w > 0);
   const int64_t m_all = frames * fho * fwo;
-  const int64_t orows = remap ? (int64_t)out_h * out_w : (int64_t)fho * fwo;  // output-buffer rows per frame
-  AVT_REQUIRE(m_all < (1ll << 31) && frames * orows < (1ll << 31) && (int64_t)kh * kw * cin < (1ll << 31),
+  const int64_t orows = remap ? (int64_t)g.out_h * g.out_w : (int64_t)fho * fwo;  // output-buffer rows per frame
+  AVT_REQUIRE(m_all < (1ll << 31) && frames * orows < (1ll << 31) && (int64_t)g.kh * g.kw * g.cin < (1ll << 31),
               "avt_conv3d_igemm_x3: tensor too large for 32-bit rows");
-  const int xl = avt_conv3d_igemm_x3_xl_picked(cout, kh * kw * cin, (int)m_all);
+  const int xl = avt_conv3d_igemm_x3_xl_picked(g.cout, g.kh * g.kw * g.cin, (int)m_all);
   const int64_t fmax = kMaxPlane / frame;                 // frames whose planes one launch can address (>= 1)
   const int64_t nrange = (frames + fmax - 1) / fmax;
   const int64_t per = (frames + nrange - 1) / nrange;     // even ranges: no short tail launch
   for (int64_t f0 = 0; f0 < frames; f0 += per) {
-    const int nf = (int)((frames - f0 < per) ? frames - f0 : per);
-    const int64_t io = f0 * frame, oo = f0 * orows * ldo, ro = f0 * fho * fwo * ldr;
-    auto adv = [](const void* p, int64_t e) { return p ? static_cast<const void*>(static_cast<const uint16_t*>(p) + e) : nullptr; };
-    const int rc = igemm_x3_one(adv(in_hi, io), adv(in_lo, io), wt_hi, wt_lo, bias, adv(res_hi, ro), adv(res_lo, ro),
-                                const_cast<void*>(adv(out_hi, oo)), const_cast<void*>(adv(out_lo, oo)), ktab, nf, 1, h, w, cin, cout, kt, kh,
-                                kw, st, sh, sw, pt, ph, pw, to ? 1 : 0, ho, wo, ldi, ldo, ldr, relu, out_row_stride, out_h, out_w,
-                                plane_dtype, wscale, stream, wblk, xl);
+    ConvGeom gr = g;  // the range's frames as a batch of single frames
+    gr.batch = (int)((frames - f0 < per) ? frames - f0 : per);
+    gr.t = 1;
+    gr.to = g.to ? 1 : 0;
+    const int64_t io = f0 * frame, oo = f0 * orows * g.ldo, ro = f0 * fho * fwo * g.ldr;
+    auto adv = [](const void* q, int64_t e) { return q ? static_cast<const void*>(static_cast<const uint16_t*>(q) + e) : nullptr; };
+    X3Planes pr = p;
+    pr.in_hi = adv(p.in_hi, io), pr.in_lo = adv(p.in_lo, io);
+    pr.res_hi = adv(p.res_hi, ro), pr.res_lo = adv(p.res_lo, ro);
+    pr.out_hi = const_cast<void*>(adv(p.out_hi, oo)), pr.out_lo = const_cast<void*>(adv(p.out_lo, oo));
+    const int rc = igemm_x3_one(pr, ktab, gr, plane_dtype, wscale, stream, wblk, xl);
     if (rc != AVT_OK) return rc;
   }
   return AVT_OK;
@@ -1092,9 +1086,12 @@ extern "C" int avt_conv3d_igemm_x3(const void* in_hi, const void* in_lo, const v
                                    int kw, int st, int sh, int sw, int pt, int ph, int pw, int to, int ho, int wo, int ldi,
                                    int ldo, int ldr, int relu, int out_row_stride, int out_h, int out_w, int plane_dtype,
                                    const float* wscale, void* stream) {
-  return igemm_x3_impl(in_hi, in_lo, wt_hi, wt_lo, bias, res_hi, res_lo, out_hi, out_lo, ktab, batch, t, h, w, cin, cout, kt, kh, kw,
-                       st, sh, sw, pt, ph, pw, to, ho, wo, ldi, ldo, ldr, relu, out_row_stride, out_h, out_w, plane_dtype, wscale,
-                       stream, 0);
+  const ConvGeom g = {.batch = batch, .t = t, .h = h, .w = w, .cin = cin, .cout = cout, .kt = kt, .kh = kh, .kw = kw,
+                      .st = st, .sh = sh, .sw = sw, .pt = pt, .ph = ph, .pw = pw, .to = to, .ho = ho, .wo = wo,
+                      .ldi = ldi, .ldo = ldo, .ldr = ldr, .relu = relu, .out_row_stride = out_row_stride, .out_h = out_h, .out_w = out_w};
+  const X3Planes p = {.in_hi = in_hi, .in_lo = in_lo, .wt_hi = wt_hi, .wt_lo = wt_lo, .bias = bias,
+                      .res_hi = res_hi, .res_lo = res_lo, .out_hi = out_hi, .out_lo = out_lo};
+  return igemm_x3_impl(p, ktab, g, plane_dtype, wscale, stream, 0);
 }
 
 // the same convolution with the weight planes in K-blocked order [K / 32][cout][32] (see include/avt.h): only where
@@ -1105,9 +1102,12 @@ extern "C" int avt_conv3d_igemm_x3_wblk(const void* in_hi, const void* in_lo, co
                                         int kw, int st, int sh, int sw, int pt, int ph, int pw, int to, int ho, int wo, int ldi,
                                         int ldo, int ldr, int relu, int out_row_stride, int out_h, int out_w, int plane_dtype,
                                         const float* wscale, void* stream) {
-  return igemm_x3_impl(in_hi, in_lo, wt_hi, wt_lo, bias, res_hi, res_lo, out_hi, out_lo, ktab, batch, t, h, w, cin, cout, kt, kh, kw,
-                       st, sh, sw, pt, ph, pw, to, ho, wo, ldi, ldo, ldr, relu, out_row_stride, out_h, out_w, plane_dtype, wscale,
-                       stream, 1);
+  const ConvGeom g = {.batch = batch, .t = t, .h = h, .w = w, .cin = cin, .cout = cout, .kt = kt, .kh = kh, .kw = kw,
+                      .st = st, .sh = sh, .sw = sw, .pt = pt, .ph = ph, .pw = pw, .to = to, .ho = ho, .wo = wo,
+                      .ldi = ldi, .ldo = ldo, .ldr = ldr, .relu = relu, .out_row_stride = out_row_stride, .out_h = out_h, .out_w = out_w};
+  const X3Planes p = {.in_hi = in_hi, .in_lo = in_lo, .wt_hi = wt_hi, .wt_lo = wt_lo, .bias = bias,
+                      .res_hi = res_hi, .res_lo = res_lo, .out_hi = out_hi, .out_lo = out_lo};
+  return igemm_x3_impl(p, ktab, g, plane_dtype, wscale, stream, 1);
 }
 
 // out[m][n] = (sum_k A[m][k] * B[n][k]) / divisor with A, B as plane pairs and an fp32 result: the 256 x 256 LDS-DMA tile as a plain
@@ -1118,9 +1118,12 @@ extern "C" int avt_gemm_nt_x3_f32out(const void* a_hi, const void* a_lo, int lda
   AVT_REQUIRE(a_lo && b_lo && avt::aligned16(a_lo) && avt::aligned16(b_lo) && divisor != 0.0f, "avt_gemm_nt_x3_f32out: both planes, divisor != 0");
   AVT_REQUIRE(m > 0 && n % 256 == 0 && k % 32 == 0 && k >= 256 && k <= kMaxTabSteps * 64 && ldo >= n && ldo % 4 == 0 && ldo < (1ll << 31),
               "avt_gemm_nt_x3_f32out: n %% 256 == 0, 256 <= k <= %d in multiples of 32 (got m %d n %d k %d)", kMaxTabSteps * 64, m, n, k);
+  // a 1x1x1 convolution over one frame of 1 x m positions, k channels in, n out
+  const ConvGeom g = {.batch = 1, .t = 1, .h = 1, .w = m, .cin = k, .cout = n, .kt = 1, .kh = 1, .kw = 1, .st = 1, .sh = 1, .sw = 1,
+                      .pt = 0, .ph = 0, .pw = 0, .to = 0, .ho = 0, .wo = 0, .ldi = lda, .ldo = 8 * (int)((ldo + 7) / 8), .ldr = 0,
+                      .relu = 0, .out_row_stride = 1, .out_h = 0, .out_w = 0};
   ConvArgs a;
-  const int rc = conv_args_fill(a, "avt_gemm_nt_x3_f32out", a_hi, b_hi, nullptr, nullptr, out, ktab, 1, 1, 1, m, k, n, 1, 1, 1, 1, 1, 1, 0, 0, 0,
-                                0, 0, 0, lda, 8 * (int)((ldo + 7) / 8), 0, 0, 1, 0, 0);
+  const int rc = conv_args_fill(a, "avt_gemm_nt_x3_f32out", a_hi, b_hi, nullptr, nullptr, out, ktab, g);
   if (rc != AVT_OK) return rc;
   a.ldo = (int)ldo;
   a.in_lo = static_cast<const uint16_t*>(a_lo);
@@ -1156,17 +1159,16 @@ extern "C" int avt_conv_x3_set_small_tile(int on) {
   return was;
 }
 
-static int igemm_x3_f32_impl(const float* in, const void* wt_hi, const void* wt_lo, const float* wscale, const float* add,
-                             float* out, const int32_t* ktab, int batch, int t, int h, int w, int cin, int cout, int kt, int kh,
-                             int kw, int st, int sh, int sw, int pt, int ph, int pw, int to, int ho, int wo, int ldi, int ldo, int lda,
-                             int out_row_stride, int out_h, int out_w, int plane_dtype, void* stream, double* stat_part = nullptr,
+// g: the entry's geometry with ldr = the add operand's leading dimension, 0 without one (fields an entry does not have stay 0)
+static int igemm_x3_f32_impl(const float* in, const void* wt_hi, const void* wt_lo, const float* wscale, const float* add, float* out,
+                             const int32_t* ktab, const ConvGeom& g, int plane_dtype, void* stream, double* stat_part = nullptr,
                              int stat_groups = 0, int stat_c = 0, const ConvArgs* bst = nullptr) {
+  const int cout = g.cout;
   AVT_REQUIRE(plane_dtype == AVT_X3_BF16 || plane_dtype == AVT_X3_F16, "avt_conv3d_igemm_x3_f32: plane_dtype must be 0 (bf16) or 1 (fp16)");
   AVT_REQUIRE(wt_lo && avt::aligned16(wt_lo) && (!wscale || avt::aligned16(wscale)), "avt_conv3d_igemm_x3_f32: weight planes / wscale NULL or unaligned");
-  AVT_REQUIRE((int64_t)batch * t * h * w * ldi < (1ll << 30) - 64, "avt_conv3d_igemm_x3_f32: input too large for 32-bit byte offsets");
+  AVT_REQUIRE((int64_t)g.batch * g.t * g.h * g.w * g.ldi < (1ll << 30) - 64, "avt_conv3d_igemm_x3_f32: input too large for 32-bit byte offsets");
   ConvArgs a;
-  const int rc = conv_args_fill(a, "avt_conv3d_igemm_x3_f32", in, wt_hi, nullptr, add, out, ktab, batch, t, h, w, cin, cout, kt, kh, kw,
-                                st, sh, sw, pt, ph, pw, to, ho, wo, ldi, ldo, add ? lda : 0, 0, out_row_stride, out_h, out_w);
+  const int rc = conv_args_fill(a, "avt_conv3d_igemm_x3_f32", in, wt_hi, nullptr, add, out, ktab, g);
   if (rc != AVT_OK) return rc;
   a.in_bytes *= 2u;  // fp32 elements
   a.in_lo = nullptr;
@@ -1192,7 +1194,7 @@ static int igemm_x3_f32_impl(const float* in, const void* wt_hi, const void* wt_
                   bn_launch);
     }
     if (bst) {  // backward statistics: the BatchNorm input has the output's geometry, contiguous rows
-      AVT_REQUIRE(bst->bst_x && bst->bst_mean && bst->bst_invstd && bst->bst_gamma && ldo == cout && avt::aligned16(bst->bst_x) &&
+      AVT_REQUIRE(bst->bst_x && bst->bst_mean && bst->bst_invstd && bst->bst_gamma && g.ldo == cout && avt::aligned16(bst->bst_x) &&
                       (!bst->bst_relu || bst->bst_mask || bst->bst_beta),
                   "avt_conv3d_igemm_x3_f32_bwdstats: BatchNorm input / statistics / scale missing, or the output rows are not contiguous");
       a.bst_x = bst->bst_x; a.bst_mean = bst->bst_mean; a.bst_invstd = bst->bst_invstd; a.bst_gamma = bst->bst_gamma;
@@ -1208,33 +1210,23 @@ static int igemm_x3_f32_impl(const float* in, const void* wt_hi, const void* wt_
   if (bst) {  // backward statistics: the 128-row tiles only (bf16 planes: gradients)
     AVT_REQUIRE(plane_dtype == AVT_X3_BF16 && io32_tile_rows(cout, a.K, a.M) != 256,
                 "avt_conv3d_igemm_x3_f32_bwdstats: bf16 planes, layers of the 128- / 64-row tiles (avt_conv3d_igemm_x3_f32_bwdstats_rows)");
-    if (cout <= 32) return launch_x3<128, 32, 32, false, true, true>(a, s);
-    if (cout <= 64) return launch_x3<128, 64, 64, false, true, true>(a, s);
-    if (io32_tile_rows(cout, a.K, a.M) == 64) return launch_x3<64, 128, 32, false, true, true>(a, s);
-    return launch_x3<128, 128, 64, false, true, true>(a, s);
+    return launch_x3_by_cout<false, true, true>(a, s, io32_tile_rows(cout, a.K, a.M) == 64);
   }
   const bool small = io32_tile_rows(cout, a.K, a.M) == 64;
   // long-K layers at a batch that fills 256 x 256 tiles (a rank's items as one batch): the XL tile's IO32 form
   if (a.oH == 0 && io32_tile_rows(cout, a.K, a.M) == 256)
     return plane_dtype == AVT_X3_F16 ? launch_x3_xl<true, true>(a, s) : launch_x3_xl<false, true>(a, s);
-  if (plane_dtype == AVT_X3_F16) {
-    if (cout <= 32) return launch_x3<128, 32, 32, true, true>(a, s);
-    if (cout <= 64) return launch_x3<128, 64, 64, true, true>(a, s);
-    if (small) return launch_x3<64, 128, 32, true, true>(a, s);
-    return launch_x3<128, 128, 64, true, true>(a, s);
-  }
-  if (cout <= 32) return launch_x3<128, 32, 32, false, true>(a, s);
-  if (cout <= 64) return launch_x3<128, 64, 64, false, true>(a, s);
-  if (small) return launch_x3<64, 128, 32, false, true>(a, s);
-  return launch_x3<128, 128, 64, false, true>(a, s);
+  return plane_dtype == AVT_X3_F16 ? launch_x3_by_cout<true, true>(a, s, small) : launch_x3_by_cout<false, true>(a, s, small);
 }
 
 extern "C" int avt_conv3d_igemm_x3_f32(const float* in, const void* wt_hi, const void* wt_lo, const float* wscale, const float* add,
                                        float* out, const int32_t* ktab, int batch, int t, int h, int w, int cin, int cout, int kt, int kh,
                                        int kw, int st, int sh, int sw, int pt, int ph, int pw, int ldi, int ldo, int lda, int plane_dtype,
                                        void* stream) {
-  return igemm_x3_f32_impl(in, wt_hi, wt_lo, wscale, add, out, ktab, batch, t, h, w, cin, cout, kt, kh, kw, st, sh, sw, pt, ph, pw, 0, 0, 0,
-                           ldi, ldo, lda, 1, 0, 0, plane_dtype, stream);
+  const ConvGeom g = {.batch = batch, .t = t, .h = h, .w = w, .cin = cin, .cout = cout, .kt = kt, .kh = kh, .kw = kw,
+                      .st = st, .sh = sh, .sw = sw, .pt = pt, .ph = ph, .pw = pw, .ldi = ldi, .ldo = ldo, .ldr = add ? lda : 0,
+                      .out_row_stride = 1};
+  return igemm_x3_f32_impl(in, wt_hi, wt_lo, wscale, add, out, ktab, g, plane_dtype, stream);
 }
 
 // ... leaving the train-mode BatchNorm statistics of its output behind (see include/avt.h): per-tile sums in `stat_part`, the rows as
@@ -1250,8 +1242,11 @@ extern "C" int avt_conv3d_igemm_x3_f32_stats(const float* in, const void* wt_hi,
                                              int st, int sh, int sw, int pt, int ph, int pw, int ldi, int ldo, int plane_dtype,
                                              void* stat_part, int groups, int stat_c, void* stream) {
   AVT_REQUIRE(stat_part, "avt_conv3d_igemm_x3_f32_stats: NULL stat_part");
-  return igemm_x3_f32_impl(in, wt_hi, wt_lo, wscale, nullptr, out, ktab, batch, t, h, w, cin, cout, kt, kh, kw, st, sh, sw, pt, ph, pw, 0, 0, 0,
-                           ldi, ldo, 0, 1, 0, 0, plane_dtype, stream, static_cast<double*>(stat_part), groups, stat_c);
+  const ConvGeom g = {.batch = batch, .t = t, .h = h, .w = w, .cin = cin, .cout = cout, .kt = kt, .kh = kh, .kw = kw,
+                      .st = st, .sh = sh, .sw = sw, .pt = pt, .ph = ph, .pw = pw, .ldi = ldi, .ldo = ldo, .ldr = 0,
+                      .out_row_stride = 1};
+  return igemm_x3_f32_impl(in, wt_hi, wt_lo, wscale, nullptr, out, ktab, g, plane_dtype, stream, static_cast<double*>(stat_part), groups,
+                           stat_c);
 }
 
 // rows of partials per group avt_conv3d_igemm_x3_f32_bwdstats writes, or -1 where it does not apply (the 256 x 256 tile's layers)
@@ -1273,8 +1268,11 @@ extern "C" int avt_conv3d_igemm_x3_f32_bwdstats(const float* in, const void* wt_
   ConvArgs b = {};
   b.bst_x = bn_x; b.bst_mean = bn_mean; b.bst_invstd = bn_invstd; b.bst_gamma = bn_gamma; b.bst_beta = bn_beta;
   b.bst_mask = static_cast<const uint8_t*>(bn_mask); b.bst_relu = relu;
-  return igemm_x3_f32_impl(in, wt_hi, wt_lo, wscale, add, out, ktab, batch, t, h, w, cin, cout, kt, kh, kw, 1, 1, 1, pt, ph, pw, 0, 0, 0, ldi,
-                           ldo, lda, 1, 0, 0, plane_dtype, stream, static_cast<double*>(stat_part), groups, stat_c, &b);
+  const ConvGeom g = {.batch = batch, .t = t, .h = h, .w = w, .cin = cin, .cout = cout, .kt = kt, .kh = kh, .kw = kw,
+                      .st = 1, .sh = 1, .sw = 1, .pt = pt, .ph = ph, .pw = pw, .ldi = ldi, .ldo = ldo, .ldr = add ? lda : 0,
+                      .out_row_stride = 1};
+  return igemm_x3_f32_impl(in, wt_hi, wt_lo, wscale, add, out, ktab, g, plane_dtype, stream, static_cast<double*>(stat_part), groups,
+                           stat_c, &b);
 }
 
 // ... with an explicit output extent (any padding on the far side) and the output-row remap of avt_conv3d_igemm_x3: one class of
@@ -1283,6 +1281,8 @@ extern "C" int avt_conv3d_igemm_x3_f32_ex(const float* in, const void* wt_hi, co
                                           const int32_t* ktab, int batch, int t, int h, int w, int cin, int cout, int kt, int kh, int kw,
                                           int pt, int ph, int pw, int to, int ho, int wo, int ldi, int ldo, int out_row_stride, int out_h,
                                           int out_w, int plane_dtype, void* stream) {
-  return igemm_x3_f32_impl(in, wt_hi, wt_lo, wscale, nullptr, out, ktab, batch, t, h, w, cin, cout, kt, kh, kw, 1, 1, 1, pt, ph, pw, to, ho,
-                           wo, ldi, ldo, 0, out_row_stride, out_h, out_w, plane_dtype, stream);
+  const ConvGeom g = {.batch = batch, .t = t, .h = h, .w = w, .cin = cin, .cout = cout, .kt = kt, .kh = kh, .kw = kw,
+                      .st = 1, .sh = 1, .sw = 1, .pt = pt, .ph = ph, .pw = pw, .to = to, .ho = ho, .wo = wo, .ldi = ldi, .ldo = ldo, .ldr = 0,
+                      .out_row_stride = out_row_stride, .out_h = out_h, .out_w = out_w};
+  return igemm_x3_f32_impl(in, wt_hi, wt_lo, wscale, nullptr, out, ktab, g, plane_dtype, stream);
 }

@@ -18,6 +18,7 @@
 #include <stdlib.h>
 
 #include "avt_common.h"
+#include "launch.h"
 #include "mfma.h"
 
 namespace {
@@ -298,32 +299,19 @@ template <int K1S, int N1, int N2, bool HAS_RES, bool W1_LDS, int NW, int K2X = 
 int launch(PwArgs& a, hipStream_t st) {
   constexpr int lds_bytes = (N2 / 16) * (N1 / 32 + K2X) * 1024 + (W1_LDS ? (N1 / 16) * K1S * 1024 : 0) + (N1 + N2) * 4;
   static_assert(lds_bytes <= 160 * 1024, "weights do not fit the LDS");
-  static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pw_chain_kernel<K1S, N1, N2, HAS_RES, W1_LDS, NW, K2X>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  if (e != hipSuccess) {
-    avt::set_error("avt_pw_chain_bf16: hipFuncSetAttribute(%d B LDS): %s", lds_bytes, hipGetErrorString(e));
-    return AVT_ERR_LAUNCH;
-  }
   constexpr int per_cu = (160 * 1024) / lds_bytes >= 2 ? 2 : 1;
   int grid = 256 * per_cu;
   const int need = (a.ntiles + NW - 1) / NW;
   if (grid > need) grid = need;
-  hipLaunchKernelGGL((pw_chain_kernel<K1S, N1, N2, HAS_RES, W1_LDS, NW, K2X>), dim3((unsigned)grid), dim3(NW * 64), lds_bytes, st, a);
-  return avt::check_launch("avt_pw_chain_bf16");
+  return avt::launch<pw_chain_kernel<K1S, N1, N2, HAS_RES, W1_LDS, NW, K2X>>("avt_pw_chain_bf16", dim3((unsigned)grid), dim3(NW * 64),
+                                                                             lds_bytes, lds_bytes, st, a);
 }
 
 int launch_wide(PwArgs& a, hipStream_t st) {
   constexpr int lds_bytes = 160 * 1024;
-  static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pw_chain_wide_kernel<4, 512, 128, 8>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  if (e != hipSuccess) {
-    avt::set_error("avt_pw_chain_bf16: hipFuncSetAttribute(%d B LDS): %s", lds_bytes, hipGetErrorString(e));
-    return AVT_ERR_LAUNCH;
-  }
   a.ntiles = (a.M + 31) / 32;
   const int grid = a.ntiles < 256 ? a.ntiles : 256;
-  hipLaunchKernelGGL((pw_chain_wide_kernel<4, 512, 128, 8>), dim3((unsigned)grid), dim3(512), lds_bytes, st, a);
-  return avt::check_launch("avt_pw_chain_bf16");
+  return avt::launch<pw_chain_wide_kernel<4, 512, 128, 8>>("avt_pw_chain_bf16", dim3((unsigned)grid), dim3(512), lds_bytes, lds_bytes, st, a);
 }
 
 }  // namespace

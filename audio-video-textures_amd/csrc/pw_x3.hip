@@ -19,6 +19,7 @@
 #include <type_traits>
 
 #include "avt_common.h"
+#include "launch.h"
 #include "mfma.h"
 #include "split_planes.h"
 
@@ -717,16 +718,9 @@ template <int K1S, int NT1, bool F16, int MODE>
 int launch_pf_stats(PfArgs& a, hipStream_t st, int groups) {  // blockIdx.y = the BatchNorm's replica group, a.M / a.ntiles per group
   constexpr int lds_bytes = pf_lds_bytes<K1S, NT1>(MODE);
   static_assert(lds_bytes <= 160 * 1024, "weights + the statistics scratch fit the LDS");
-  static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pw_x3_f32_kernel<K1S, NT1, F16, MODE>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  if (e != hipSuccess) {
-    avt::set_error("avt_pw_x3_f32_stats: hipFuncSetAttribute(%d B LDS): %s", lds_bytes, hipGetErrorString(e));
-    return AVT_ERR_LAUNCH;
-  }
   a.n_rg = pf_row_groups(lds_bytes, a.n_chunks, a.ntiles, groups);
-  hipLaunchKernelGGL((pw_x3_f32_kernel<K1S, NT1, F16, MODE>), dim3((unsigned)(a.n_rg * a.n_chunks), (unsigned)groups), dim3(PX_NW * 64),
-                     lds_bytes, st, a);
-  return avt::check_launch("avt_pw_x3_f32_stats");
+  return avt::launch<pw_x3_f32_kernel<K1S, NT1, F16, MODE>>("avt_pw_x3_f32_stats", dim3((unsigned)(a.n_rg * a.n_chunks), (unsigned)groups),
+                                                            dim3(PX_NW * 64), lds_bytes, lds_bytes, st, a);
 }
 
 template <int K1S, int NT1, bool F16>
@@ -740,15 +734,9 @@ int launch_pf(PfArgs& a, hipStream_t st, int groups = 0) {
     return launch_pf_stats<K1S, NT1, F16, 1>(a, st, groups);
   }
   constexpr int lds_bytes = pf_lds_bytes<K1S, NT1>(0);
-  static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pw_x3_f32_kernel<K1S, NT1, F16>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  if (e != hipSuccess) {
-    avt::set_error("avt_pw_x3_f32: hipFuncSetAttribute(%d B LDS): %s", lds_bytes, hipGetErrorString(e));
-    return AVT_ERR_LAUNCH;
-  }
   a.n_rg = pf_row_groups(lds_bytes, a.n_chunks, a.ntiles, 1);
-  hipLaunchKernelGGL((pw_x3_f32_kernel<K1S, NT1, F16>), dim3((unsigned)(a.n_rg * a.n_chunks)), dim3(PX_NW * 64), lds_bytes, st, a);
-  return avt::check_launch("avt_pw_x3_f32");
+  return avt::launch<pw_x3_f32_kernel<K1S, NT1, F16>>("avt_pw_x3_f32", dim3((unsigned)(a.n_rg * a.n_chunks)), dim3(PX_NW * 64), lds_bytes,
+                                                      lds_bytes, st, a);
 }
 
 // LDS bytes of the (K1S, NT1) instance, for the row-group query (avt_pw_x3_f32_stat_rows)
@@ -797,21 +785,10 @@ int pick_nt1(int k1s, int n) {
 template <int K1S, int NT1, bool F16>
 int launch_px(PxArgs& a, hipStream_t st) {
   constexpr int lds_bytes = 2 * NT1 * K1S * 1024 + 2 * NT1 * 16 * 4;
-  static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pw_x3_kernel<K1S, NT1, F16>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  if (e != hipSuccess) {
-    avt::set_error("avt_pw_x3: hipFuncSetAttribute(%d B LDS): %s", lds_bytes, hipGetErrorString(e));
-    return AVT_ERR_LAUNCH;
-  }
   // persistent workgroups: as many as stay resident (LDS-limited), split into row groups x channel chunks
-  const int per_cu = lds_bytes > 80 * 1024 ? 1 : (lds_bytes > 52 * 1024 ? 2 : 3);
-  int n_rg = (256 * per_cu) / a.n_chunks;
-  n_rg = n_rg < 8 ? 8 : (n_rg / 8) * 8;
-  const int max_rg = (a.ntiles + PX_NW - 1) / PX_NW;
-  if (n_rg > ((max_rg + 7) / 8) * 8) n_rg = ((max_rg + 7) / 8) * 8;
-  a.n_rg = n_rg;  // a multiple of 8: blocks of one XCD (b % 8) form whole row groups
-  hipLaunchKernelGGL((pw_x3_kernel<K1S, NT1, F16>), dim3((unsigned)(n_rg * a.n_chunks)), dim3(PX_NW * 64), lds_bytes, st, a);
-  return avt::check_launch("avt_pw_x3");
+  a.n_rg = pf_row_groups(lds_bytes, a.n_chunks, a.ntiles, 1);  // a multiple of 8: blocks of one XCD (b % 8) form whole row groups
+  return avt::launch<pw_x3_kernel<K1S, NT1, F16>>("avt_pw_x3", dim3((unsigned)(a.n_rg * a.n_chunks)), dim3(PX_NW * 64), lds_bytes, lds_bytes,
+                                                  st, a);
 }
 
 template <int K1S, bool F16>
@@ -844,6 +821,50 @@ int dispatch_k(PxArgs& a, int k1s, int nt1, hipStream_t st) {
   return AVT_ERR_UNSUPPORTED;
 }
 
+// The fields the PxArgs users share: a pointwise layer of n columns (nt1 tiles per chunk) over m rows.  The lateral and the chained
+// entries then set what differs.
+void px_fill(PxArgs& a, const void* x_hi, const void* x_lo, int ldx, int k, const void* w_hi, const void* w_lo, const float* bias,
+             const float* wscale, const void* res_hi, const void* res_lo, int ldr, void* y_hi, void* y_lo, int ldy, int n, int nt1,
+             int64_t m, int relu) {
+  a.xh = static_cast<const uint16_t*>(x_hi);
+  a.xl = static_cast<const uint16_t*>(x_lo);
+  a.rh = static_cast<const uint16_t*>(res_hi);
+  a.rl = static_cast<const uint16_t*>(res_lo);
+  a.yh = static_cast<uint16_t*>(y_hi);
+  a.yl = static_cast<uint16_t*>(y_lo);
+  a.wh = static_cast<const i32x4*>(w_hi);
+  a.wl = static_cast<const i32x4*>(w_lo);
+  a.bias = bias;
+  a.wscale = wscale;
+  a.M = (int)m;
+  a.ldx = ldx;
+  a.ldr = ldr;
+  a.ldy = ldy;
+  a.k1c = k / 8;
+  a.ntiles = (int)((m + 15) / 16);
+  a.relu = relu;
+  a.n_chunks = n / (16 * nt1);
+  a.n_rg = 0;  // (launch_px)
+  a.taps = 1;
+  a.cin8 = a.T = a.To = a.HW = a.tst = a.tpad = 0;
+  a.n_valid = n;
+}
+
+// ... and the PfArgs users: `rows` = the rows of one launch slab (all of them, or one BatchNorm group's); no backward statistics
+void pf_fill(PfArgs& a, const float* x, int ldx, int k, const void* w_hi, const void* w_lo, const float* wscale, const float* add, int lda,
+             float* y, int ldy, int n, int nt1, int rows, void* stat_part) {
+  a.x = x; a.add = add; a.y = y;
+  a.wh = static_cast<const uint16_t*>(w_hi);
+  a.wl = static_cast<const uint16_t*>(w_lo);
+  a.wscale = wscale;
+  a.M = rows; a.ldx = ldx; a.lda = lda; a.ldy = ldy; a.K = k; a.k1c = k / 8;
+  a.ntiles = (rows + 15) / 16;
+  a.n_chunks = n / (16 * nt1);
+  a.stat_part = static_cast<double*>(stat_part);
+  a.n_total = n;
+  a.bst_x = nullptr;
+}
+
 }  // namespace
 
 extern "C" int avt_pw_x3_supported(int k, int n) {
@@ -869,27 +890,7 @@ extern "C" int avt_pw_x3(const void* x_hi, const void* x_lo, int ldx, int k, con
   AVT_REQUIRE(plane_dtype == AVT_X3_BF16 || plane_dtype == AVT_X3_F16, "avt_pw_x3: bad plane_dtype");
   const int k1s = (k + 31) / 32, nt1 = pick_nt1(k1s, n);
   PxArgs a;
-  a.xh = static_cast<const uint16_t*>(x_hi);
-  a.xl = static_cast<const uint16_t*>(x_lo);
-  a.rh = static_cast<const uint16_t*>(res_hi);
-  a.rl = static_cast<const uint16_t*>(res_lo);
-  a.yh = static_cast<uint16_t*>(y_hi);
-  a.yl = static_cast<uint16_t*>(y_lo);
-  a.wh = static_cast<const i32x4*>(w_hi);
-  a.wl = static_cast<const i32x4*>(w_lo);
-  a.bias = bias;
-  a.wscale = wscale;
-  a.M = (int)m;
-  a.ldx = ldx;
-  a.ldr = ldr;
-  a.ldy = ldy;
-  a.k1c = k / 8;
-  a.ntiles = (int)((m + 15) / 16);
-  a.relu = relu;
-  a.n_chunks = n / (16 * nt1);
-  a.taps = 1;
-  a.cin8 = a.T = a.To = a.HW = a.tst = a.tpad = 0;
-  a.n_valid = n;
+  px_fill(a, x_hi, x_lo, ldx, k, w_hi, w_lo, bias, wscale, res_hi, res_lo, ldr, y_hi, y_lo, ldy, n, nt1, m, relu);
   hipStream_t st = static_cast<hipStream_t>(stream);
   return plane_dtype == AVT_X3_F16 ? dispatch_k<true>(a, k1s, nt1, st) : dispatch_k<false>(a, k1s, nt1, st);
 }
@@ -919,23 +920,8 @@ extern "C" int avt_lateral_x3(const void* x_hi, const void* x_lo, int ldx, int c
   AVT_REQUIRE(to > 0 && m < (1ll << 31) - 16, "avt_lateral_x3: no output frames / too many rows");
   const int k = kt * cin, k1s = (k + 31) / 32, n = (cout + 31) / 32 * 32, nt1 = pick_nt1(k1s, n);
   PxArgs a;
-  a.xh = static_cast<const uint16_t*>(x_hi);
-  a.xl = static_cast<const uint16_t*>(x_lo);
-  a.rh = a.rl = nullptr;
-  a.yh = static_cast<uint16_t*>(y_hi);
-  a.yl = static_cast<uint16_t*>(y_lo);
-  a.wh = static_cast<const i32x4*>(w_hi);  // fused_slowfast.pack_pw_planes over the conv's own [Cout (padded to 32), kt * Cin] rows
-  a.wl = static_cast<const i32x4*>(w_lo);
-  a.bias = bias;      // [n] (padded with the weights)
-  a.wscale = wscale;
-  a.M = (int)m;
-  a.ldx = ldx;
-  a.ldr = 0;
-  a.ldy = ldy;
-  a.k1c = k / 8;
-  a.ntiles = (int)((m + 15) / 16);
-  a.relu = relu;
-  a.n_chunks = n / (16 * nt1);
+  // (weights: fused_slowfast.pack_pw_planes over the conv's own [Cout (padded to 32), kt * Cin] rows; bias [n], padded with them)
+  px_fill(a, x_hi, x_lo, ldx, k, w_hi, w_lo, bias, wscale, nullptr, nullptr, 0, y_hi, y_lo, ldy, n, nt1, m, relu);
   a.taps = kt;
   a.cin8 = cin / 8;
   a.T = t;
@@ -968,29 +954,8 @@ extern "C" int avt_pw_chain_x3(const void* x_hi, const void* x_lo, int ldx, int 
               "avt_pw_chain_x3: pointers must be 16-byte aligned");
   AVT_REQUIRE(plane_dtype == AVT_X3_BF16 || plane_dtype == AVT_X3_F16, "avt_pw_chain_x3: bad plane_dtype");
   PcArgs c;
-  PxArgs& a = c.p;
-  a.xh = static_cast<const uint16_t*>(x_hi);
-  a.xl = static_cast<const uint16_t*>(x_lo);
-  a.rh = static_cast<const uint16_t*>(res_hi);
-  a.rl = static_cast<const uint16_t*>(res_lo);
-  a.yh = static_cast<uint16_t*>(y_hi);
-  a.yl = static_cast<uint16_t*>(y_lo);
-  a.wh = static_cast<const i32x4*>(w1_hi);
-  a.wl = static_cast<const i32x4*>(w1_lo);
-  a.bias = bias1;
-  a.wscale = wscale1;
-  a.M = (int)m;
-  a.ldx = ldx;
-  a.ldr = ldr;
-  a.ldy = ldy;
-  a.k1c = k1 / 8;
-  a.ntiles = (int)((m + 15) / 16);
-  a.relu = relu1;
-  a.n_chunks = 1;
-  a.n_rg = 0;
-  a.taps = 1;
-  a.cin8 = a.T = a.To = a.HW = a.tst = a.tpad = 0;
-  a.n_valid = n1;
+  constexpr int K1S = 2, NT1 = 16, NT2 = 4;
+  px_fill(c.p, x_hi, x_lo, ldx, k1, w1_hi, w1_lo, bias1, wscale1, res_hi, res_lo, ldr, y_hi, y_lo, ldy, n1, NT1, m, relu1);  // one chunk
   c.w2h = static_cast<const i32x4*>(w2_hi);
   c.w2l = static_cast<const i32x4*>(w2_lo);
   c.bias2 = bias2;
@@ -998,24 +963,14 @@ extern "C" int avt_pw_chain_x3(const void* x_hi, const void* x_lo, int ldx, int 
   c.zh = static_cast<uint16_t*>(z_hi);
   c.zl = static_cast<uint16_t*>(z_lo);
   c.ldz = ldz;
-  constexpr int K1S = 2, NT1 = 16, NT2 = 4;
   constexpr int lds_bytes = 2 * NT1 * K1S * 1024 + 2 * NT2 * (NT1 / 2) * 1024 + (2 * NT1 * 16 + 2 * NT2 * 16) * 4;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  static const hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(pw_chain_x3_kernel<K1S, NT1, NT2, true>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  static const hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(pw_chain_x3_kernel<K1S, NT1, NT2, false>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  if (e1 != hipSuccess || e2 != hipSuccess) {
-    avt::set_error("avt_pw_chain_x3: hipFuncSetAttribute(%d B LDS) failed", lds_bytes);
-    return AVT_ERR_LAUNCH;
-  }
-  int grid = (a.ntiles + PX_NW - 1) / PX_NW;
+  int grid = (c.p.ntiles + PX_NW - 1) / PX_NW;
   if (grid > 256) grid = 256;  // persistent: one workgroup per CU (129 KB of fragments)
+  const dim3 block(PX_NW * 64);
   if (plane_dtype == AVT_X3_F16)
-    hipLaunchKernelGGL((pw_chain_x3_kernel<K1S, NT1, NT2, true>), dim3((unsigned)grid), dim3(PX_NW * 64), lds_bytes, st, c);
-  else
-    hipLaunchKernelGGL((pw_chain_x3_kernel<K1S, NT1, NT2, false>), dim3((unsigned)grid), dim3(PX_NW * 64), lds_bytes, st, c);
-  return avt::check_launch("avt_pw_chain_x3");
+    return avt::launch<pw_chain_x3_kernel<K1S, NT1, NT2, true>>("avt_pw_chain_x3", dim3((unsigned)grid), block, lds_bytes, lds_bytes, st, c);
+  return avt::launch<pw_chain_x3_kernel<K1S, NT1, NT2, false>>("avt_pw_chain_x3", dim3((unsigned)grid), block, lds_bytes, lds_bytes, st, c);
 }
 
 // The training form of avt_pw_x3 (see include/avt.h): fp32 rows in / out, plain [n][k] weight planes
@@ -1040,16 +995,7 @@ extern "C" int avt_pw_x3_f32(const float* x, int ldx, int k, const void* w_hi, c
   AVT_REQUIRE(plane_dtype == AVT_X3_BF16 || plane_dtype == AVT_X3_F16, "avt_pw_x3_f32: bad plane_dtype");
   const int k1s = (k + 31) / 32, nt1 = pick_nt1(k1s, n);
   PfArgs a;
-  a.x = x; a.add = add; a.y = y;
-  a.wh = static_cast<const uint16_t*>(w_hi);
-  a.wl = static_cast<const uint16_t*>(w_lo);
-  a.wscale = wscale;
-  a.M = (int)m; a.ldx = ldx; a.lda = lda; a.ldy = ldy; a.K = k; a.k1c = k / 8;
-  a.ntiles = (int)((m + 15) / 16);
-  a.n_chunks = n / (16 * nt1);
-  a.stat_part = nullptr;
-  a.n_total = n;
-  a.bst_x = nullptr;
+  pf_fill(a, x, ldx, k, w_hi, w_lo, wscale, add, lda, y, ldy, n, nt1, (int)m, nullptr);
   hipStream_t st = static_cast<hipStream_t>(stream);
   return plane_dtype == AVT_X3_F16 ? dispatch_pf_k<true>(a, k1s, nt1, st) : dispatch_pf_k<false>(a, k1s, nt1, st);
 }
@@ -1076,16 +1022,7 @@ extern "C" int avt_pw_x3_f32_stats(const float* x, int ldx, int k, const void* w
   AVT_REQUIRE(plane_dtype == AVT_X3_BF16 || plane_dtype == AVT_X3_F16, "avt_pw_x3_f32_stats: bad plane_dtype");
   const int k1s = (k + 31) / 32, nt1 = pick_nt1(k1s, n);
   PfArgs a;
-  a.x = x; a.add = nullptr; a.y = y;
-  a.wh = static_cast<const uint16_t*>(w_hi);
-  a.wl = static_cast<const uint16_t*>(w_lo);
-  a.wscale = wscale;
-  a.M = (int)(m / groups); a.ldx = ldx; a.lda = 0; a.ldy = ldy; a.K = k; a.k1c = k / 8;
-  a.ntiles = (a.M + 15) / 16;
-  a.n_chunks = n / (16 * nt1);
-  a.stat_part = static_cast<double*>(stat_part);
-  a.n_total = n;
-  a.bst_x = nullptr;
+  pf_fill(a, x, ldx, k, w_hi, w_lo, wscale, nullptr, 0, y, ldy, n, nt1, (int)(m / groups), stat_part);
   hipStream_t st = static_cast<hipStream_t>(stream);
   return plane_dtype == AVT_X3_F16 ? dispatch_pf_k<true>(a, k1s, nt1, st, groups) : dispatch_pf_k<false>(a, k1s, nt1, st, groups);
 }
@@ -1118,15 +1055,7 @@ extern "C" int avt_pw_x3_f32_bwdstats(const float* x, int ldx, int k, const void
   //  tiles and twice the chunks — the dy rows read twice, a small operand here — are 10 % (K = 64) to 27 % (K = 128) faster)
   if (nt1 == 16) nt1 = 8;
   PfArgs a;
-  a.x = x; a.add = add; a.y = y;
-  a.wh = static_cast<const uint16_t*>(w_hi);
-  a.wl = static_cast<const uint16_t*>(w_lo);
-  a.wscale = nullptr;
-  a.M = (int)(m / groups); a.ldx = ldx; a.lda = lda; a.ldy = ldy; a.K = k; a.k1c = k / 8;
-  a.ntiles = (a.M + 15) / 16;
-  a.n_chunks = n / (16 * nt1);
-  a.stat_part = static_cast<double*>(stat_part);
-  a.n_total = n;
+  pf_fill(a, x, ldx, k, w_hi, w_lo, nullptr, add, lda, y, ldy, n, nt1, (int)(m / groups), stat_part);
   a.bst_x = bn_x; a.bst_mean = bn_mean; a.bst_invstd = bn_invstd; a.bst_gamma = bn_gamma; a.bst_beta = bn_beta;
   a.bst_mask = static_cast<const uint8_t*>(bn_mask); a.bst_relu = relu;
   return dispatch_pf_k<false>(a, k1s, nt1, static_cast<hipStream_t>(stream), groups);

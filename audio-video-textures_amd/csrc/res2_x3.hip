@@ -38,6 +38,7 @@
 #include <type_traits>
 
 #include "avt_common.h"
+#include "launch.h"
 #include "mfma.h"
 #include "split_planes.h"
 
@@ -459,17 +460,10 @@ __global__ __launch_bounds__(NWV * 64) void res2_x3_kernel(R2Args a) {
 
 template <int W, bool F16>
 int launch(R2Args& a, hipStream_t st) {
-  static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(res2_x3_kernel<W, F16>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-  if (e != hipSuccess) {
-    avt::set_error("avt_res2_x3: hipFuncSetAttribute(%d B LDS): %s", LDS_BYTES, hipGetErrorString(e));
-    return AVT_ERR_LAUNCH;
-  }
   int grid = a.nsteps < 256 ? a.nsteps : 256;  // persistent: one workgroup per CU (147 KB of LDS each)
   a.spw = (a.nsteps + grid - 1) / grid;
   grid = (a.nsteps + a.spw - 1) / a.spw;
-  hipLaunchKernelGGL((res2_x3_kernel<W, F16>), dim3((unsigned)grid), dim3(NWV * 64), LDS_BYTES, st, a);
-  return avt::check_launch("avt_res2_x3");
+  return avt::launch<res2_x3_kernel<W, F16>>("avt_res2_x3", dim3((unsigned)grid), dim3(NWV * 64), LDS_BYTES, LDS_BYTES, st, a);
 }
 
 }  // namespace

@@ -23,6 +23,7 @@
 // rows padded to 144 B so each 16-lane ds_read_b128 group (16 distinct rows at
 // one k-offset) touches all 64 banks once.  Roofline: MFMA (2*nq*nt*d flop).
 #include "avt_common.h"
+#include "launch.h"
 #include "mfma.h"
 
 namespace {
@@ -377,17 +378,8 @@ int launch(Args& a, bool aligned, hipStream_t st) {
   a.nblk = (int)(tiles_m * tiles_n);
   const dim3 grid((unsigned)a.nblk), block(256);
   constexpr int lds_bytes = Cfg<MODE>::NPL * (PLANE + TN * LSTR);
-  auto kern = aligned ? sim_gemm_kernel<MODE, true, TN> : sim_gemm_kernel<MODE, false, TN>;
-  if (lds_bytes > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       lds_bytes);
-    if (e != hipSuccess) {
-      avt::set_error("avt_sim_gemm_nt: hipFuncSetAttribute(%d B LDS): %s", lds_bytes, hipGetErrorString(e));
-      return AVT_ERR_LAUNCH;
-    }
-  }
-  hipLaunchKernelGGL(kern, grid, block, lds_bytes, st, a);
-  return avt::check_launch("avt_sim_gemm_nt");
+  if (aligned) return avt::launch<sim_gemm_kernel<MODE, true, TN>>("avt_sim_gemm_nt", grid, block, lds_bytes, lds_bytes, st, a);
+  return avt::launch<sim_gemm_kernel<MODE, false, TN>>("avt_sim_gemm_nt", grid, block, lds_bytes, lds_bytes, st, a);
 }
 
 }  // namespace

@@ -25,6 +25,7 @@
 #include <stdlib.h>
 
 #include "avt_common.h"
+#include "launch.h"
 #include "mfma.h"
 #include "split_planes.h"
 
@@ -407,18 +408,11 @@ int launch(const StemArgs& a, int batch, hipStream_t st, const char* what) {
   constexpr int R = POOL ? OWNP + 1 : RB;
   constexpr int patch = ((2 * R + 5) * (MT * 16 + 4) + BCH) * 16 * (PL ? 2 : 1), tile = POOL ? R * MT * 16 * (PL ? 128 : 64) : 0;
   constexpr int lds_bytes = patch > tile ? patch : tile;
-  static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(stem_kernel<MT, POOL, PL>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  if (e != hipSuccess) {
-    avt::set_error("%s: hipFuncSetAttribute(%d B LDS): %s", what, lds_bytes, hipGetErrorString(e));
-    return AVT_ERR_LAUNCH;
-  }
   StemArgs b = a;
   b.ncg = (a.Cout + NT * 16 - 1) / (NT * 16);
   b.swz = 1;
   const dim3 grid((unsigned)(batch * a.To * (a.Ho / (POOL ? OWNP : RB)) * b.ncg));
-  hipLaunchKernelGGL((stem_kernel<MT, POOL, PL>), grid, dim3(POOL ? 512 : 256), lds_bytes, st, b);
-  return avt::check_launch(what);
+  return avt::launch<stem_kernel<MT, POOL, PL>>(what, grid, dim3(POOL ? 512 : 256), lds_bytes, lds_bytes, st, b);
 }
 
 int fill(StemArgs& a, const char* what, const void* in, const void* wt, const float* bias, void* out, int batch, int t,

@@ -24,6 +24,7 @@
 // is read once per step and used by every (output row r, row tap dh) with 2 r + dh = j.
 // Roofline: MFMA (3 x the bf16 work; the padded columns 112 -> 128 and the sixth frame tap are issued work, not algorithmic).
 #include "avt_common.h"
+#include "launch.h"
 #include "mfma.h"
 #include "split_planes.h"
 
@@ -502,19 +503,13 @@ static_assert(stem_wgrad_lds_bytes(1, 16) <= CU_LDS_BYTES && stem_wgrad_lds_byte
 template <int KT, int CO>
 int launch_wgrad(SwArgs& a, hipStream_t st) {
   constexpr int lds_bytes = stem_wgrad_lds_bytes(KT, CO);
-  static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(stem_wgrad_kernel<KT, CO>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  if (e != hipSuccess) {
-    avt::set_error("avt_stem_wgrad_x3: hipFuncSetAttribute(%d B LDS): %s", lds_bytes, hipGetErrorString(e));
-    return AVT_ERR_LAUNCH;
-  }
   const int slices = (a.Cout + 15) / 16;
   constexpr int wgs = 256;  // persistent workgroups (one per CU: up to 150 KB of LDS)
   int gx = wgs / slices;
   if (gx < 1) gx = 1;
   if (gx > a.nunit) gx = a.nunit;
-  hipLaunchKernelGGL((stem_wgrad_kernel<KT, CO>), dim3((unsigned)gx, (unsigned)slices), dim3(NTHR), lds_bytes, st, a);
-  return avt::check_launch("avt_stem_wgrad_x3");
+  return avt::launch<stem_wgrad_kernel<KT, CO>>("avt_stem_wgrad_x3", dim3((unsigned)gx, (unsigned)slices), dim3(NTHR), lds_bytes, lds_bytes,
+                                                st, a);
 }
 
 }  // namespace

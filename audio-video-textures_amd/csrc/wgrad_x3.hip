@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "avt_common.h"
+#include "launch.h"
 #include "conv_args.h"
 #include "mfma.h"
 
@@ -399,16 +400,9 @@ int launch_b(WgArgs& a, int s_count, hipStream_t st) {
   static_assert(128 * (BN + 1) * 4 <= lds_small, "the swapped epilogue stages its tile over the operand planes (and tables)");
   static_assert(lds_small <= 80 * 1024, "two workgroups per CU");
   const int lds_bytes = a.tapcap > kMaxTaps ? lds_big : lds_small;
-  static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_x3_kernel<BN, SWAP, BUF>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds_big);
-  if (e != hipSuccess) {
-    avt::set_error("avt_conv3d_wgrad_x3_f32: hipFuncSetAttribute(%d B LDS): %s", lds_big, hipGetErrorString(e));
-    return AVT_ERR_LAUNCH;
-  }
   const int64_t grid = (int64_t)tiles * a.nchunk;
   AVT_REQUIRE(grid < (1ll << 31), "avt_conv3d_wgrad_x3_f32: grid too large");
-  hipLaunchKernelGGL((wgrad_x3_kernel<BN, SWAP, BUF>), dim3((unsigned)grid), dim3(256), lds_bytes, st, a);
-  return avt::check_launch("avt_conv3d_wgrad_x3_f32");
+  return avt::launch<wgrad_x3_kernel<BN, SWAP, BUF>>("avt_conv3d_wgrad_x3_f32", dim3((unsigned)grid), dim3(256), lds_big, lds_bytes, st, a);
 }
 
 
@@ -698,16 +692,9 @@ int launch_xl(WgArgs& a, int r_count, int s_count, hipStream_t st) {
   a.nchunk = (a.nslab + a.slabs_per_chunk - 1) / a.slabs_per_chunk;
   constexpr int lds_bytes = XTABS + 4 * XP * 4 + 4 * XP * kMaxTaps * 4 + 64 * 4;  // (+ the tap table)
   static_assert(128 * 129 * 4 <= XTABS && lds_bytes <= 160 * 1024, "the swapped epilogue's staging and the whole layout fit");
-  static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_x3_xl_kernel<SWAP, SW>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  if (e != hipSuccess) {
-    avt::set_error("avt_conv3d_wgrad_x3_f32: hipFuncSetAttribute(%d B LDS): %s", lds_bytes, hipGetErrorString(e));
-    return AVT_ERR_LAUNCH;
-  }
   const int64_t grid = (int64_t)tiles * a.nchunk;
   AVT_REQUIRE(grid < (1ll << 31), "avt_conv3d_wgrad_x3_f32: grid too large");
-  hipLaunchKernelGGL((wgrad_x3_xl_kernel<SWAP, SW>), dim3((unsigned)grid), dim3(512), lds_bytes, st, a);
-  return avt::check_launch("avt_conv3d_wgrad_x3_f32");
+  return avt::launch<wgrad_x3_xl_kernel<SWAP, SW>>("avt_conv3d_wgrad_x3_f32", dim3((unsigned)grid), dim3(512), lds_bytes, lds_bytes, st, a);
 }
 
 // which tile avt_conv3d_wgrad_x3_f32 launches for (longer axis, shorter axis, taps, positions): 1 = the 256 x 128 tile

@@ -102,3 +102,85 @@ def test_conv_ktab(avt):
     kc = 5  # chunk 5: tap 2 (dh=0, dw=2), channels 8..15
     assert tab[kc, 1] == (1 | 1 << 8 | 1 << 18) and tab[kc, 0] == 2 * 16 + 8
     assert (tab[18:24, 1] == -1).all() and (tab[24:] == 0).all()
+
+
+# ---- argument rejection of the convolution / pointwise entries: every AVT_REQUIRE runs before the first HIP call, so the raw entries
+# can be called on a box without a GPU with made-up (16-byte-aligned, never dereferenced) addresses and ONE bad argument each
+_P = [0x10000 * (i + 1) for i in range(10)]  # fake device addresses
+_GEOM = dict(batch=2, t=5, h=8, w=6, cin=24, cout=40, kt=2, kh=1, kw=3, st=1, sh=2, sw=1, pt=1, ph=0, pw=2, to=0, ho=0, wo=0,
+             ldi=24, ldo=40, ldr=0, relu=1, out_row_stride=1, out_h=0, out_w=0, plane_dtype=0)
+_GEOM_S1 = dict(_GEOM, sh=1)  # the entries without strides
+_PW = dict(ldx=64, k=64, ldr=0, ldy=64, n=64, m=100, relu=1, plane_dtype=0)
+
+
+def _ints(g, names):
+    return [g[n] for n in names.split()]
+
+
+_ENTRIES = {
+    "avt_conv3d_igemm_bf16": (_GEOM, lambda g: [_P[0], _P[1], _P[2], 0, _P[3], _P[4]] + _ints(
+        g, "batch t h w cin cout kt kh kw st sh sw pt ph pw to ho wo ldi ldo ldr relu") + [0]),
+    "avt_conv3d_igemm_x3": (_GEOM, lambda g: [_P[0], _P[1], _P[2], _P[3], _P[4], 0, 0, _P[5], _P[6], _P[7]] + _ints(
+        g, "batch t h w cin cout kt kh kw st sh sw pt ph pw to ho wo ldi ldo ldr relu out_row_stride out_h out_w plane_dtype") + [0, 0]),
+    "avt_conv3d_igemm_x3_f32": (_GEOM, lambda g: [_P[0], _P[1], _P[2], 0, 0, _P[3], _P[4]] + _ints(
+        g, "batch t h w cin cout kt kh kw st sh sw pt ph pw ldi ldo ldr plane_dtype") + [0]),
+    "avt_conv3d_igemm_x3_f32_ex": (_GEOM_S1, lambda g: [_P[0], _P[1], _P[2], 0, _P[3], _P[4]] + _ints(
+        g, "batch t h w cin cout kt kh kw pt ph pw to ho wo ldi ldo out_row_stride out_h out_w plane_dtype") + [0]),
+    "avt_pw_x3": (_PW, lambda g: [_P[0], _P[1], g["ldx"], g["k"], _P[2], _P[3], _P[4], 0, 0, 0, g["ldr"], _P[5], _P[6], g["ldy"], g["n"],
+                                  g["m"], g["relu"], g["plane_dtype"], 0]),
+    "avt_pw_x3_f32": (_PW, lambda g: [_P[0], g["ldx"], g["k"], _P[1], _P[2], 0, 0, 0, _P[3], g["ldy"], g["n"], g["m"], g["plane_dtype"], 0]),
+}
+_BIG = dict(batch=1 << 12, t=8, h=256, w=256, kt=3)  # 2^31 input rows of 24 channels, temporal taps: no frame ranges
+# ... and with few rows, so that the input plane's term of the shared check trips alone: 4096 x 240 rows of 2192 columns are 2^31 + 7.3e6
+# elements, the output is 786 432 rows of 40
+_BIG_IN = dict(batch=1 << 12, ldi=2192, kt=3)
+_REJECTED = [
+    ("avt_conv3d_igemm_bf16", dict(cin=12), "avt_conv3d_igemm_bf16: Cin/Cout must be multiples of 8"),
+    ("avt_conv3d_igemm_bf16", dict(kw=9), "avt_conv3d_igemm_bf16: kernel extents must be 1..8"),
+    ("avt_conv3d_igemm_bf16", dict(ldo=32), "avt_conv3d_igemm_bf16: leading dimensions must be multiples of 8 and cover the channels"),
+    ("avt_conv3d_igemm_bf16", _BIG_IN, "avt_conv3d_igemm_bf16: tensor too large for 32-bit offsets"),
+    ("avt_conv3d_igemm_x3", dict(cin=12), "avt_conv3d_igemm_x3: Cin/Cout must be multiples of 8"),
+    ("avt_conv3d_igemm_x3", dict(kw=9), "avt_conv3d_igemm_x3: kernel extents must be 1..8"),
+    ("avt_conv3d_igemm_x3", dict(ldo=32), "avt_conv3d_igemm_x3: leading dimensions must be multiples of 8 and cover the channels"),
+    # the layer's output is 6 x 4 x 8: stride-2 rows need a grid of 7 x 15
+    ("avt_conv3d_igemm_x3", dict(out_row_stride=2, out_h=7, out_w=14),
+     "avt_conv3d_igemm_x3: the remapped rows need an out_h x out_w grid that holds 2 x (4 x 8), no residual"),
+    ("avt_conv3d_igemm_x3", dict(out_row_stride=2, out_h=6, out_w=15),
+     "avt_conv3d_igemm_x3: the remapped rows need an out_h x out_w grid that holds 2 x (4 x 8), no residual"),
+    ("avt_conv3d_igemm_x3", _BIG_IN, "avt_conv3d_igemm_x3: tensor too large for 32-bit offsets"),
+    ("avt_conv3d_igemm_x3", dict(plane_dtype=2), "avt_conv3d_igemm_x3: plane_dtype must be 0 (bf16) or 1 (fp16)"),
+    ("avt_conv3d_igemm_x3_f32", dict(cin=12), "avt_conv3d_igemm_x3_f32: Cin/Cout must be multiples of 8"),
+    ("avt_conv3d_igemm_x3_f32", dict(kw=9), "avt_conv3d_igemm_x3_f32: kernel extents must be 1..8"),
+    ("avt_conv3d_igemm_x3_f32", dict(ldo=32), "avt_conv3d_igemm_x3_f32: leading dimensions must be multiples of 8 and cover the channels"),
+    ("avt_conv3d_igemm_x3_f32", _BIG, "avt_conv3d_igemm_x3_f32: input too large for 32-bit byte offsets"),
+    ("avt_conv3d_igemm_x3_f32", dict(plane_dtype=2), "avt_conv3d_igemm_x3_f32: plane_dtype must be 0 (bf16) or 1 (fp16)"),
+    ("avt_conv3d_igemm_x3_f32_ex", dict(cin=12), "avt_conv3d_igemm_x3_f32: Cin/Cout must be multiples of 8"),
+    ("avt_conv3d_igemm_x3_f32_ex", dict(kw=9), "avt_conv3d_igemm_x3_f32: kernel extents must be 1..8"),
+    ("avt_conv3d_igemm_x3_f32_ex", dict(ldo=32), "avt_conv3d_igemm_x3_f32: leading dimensions must be multiples of 8 and cover the channels"),
+    # stride 1: the output is 6 x 8 x 8; one class of a stride-2 transposed convolution needs a grid of 15 x 15
+    ("avt_conv3d_igemm_x3_f32_ex", dict(out_row_stride=2, out_h=15, out_w=14),
+     "avt_conv3d_igemm_x3_f32: the remapped rows need an out_h x out_w grid that holds 2 x (8 x 8), no residual"),
+    ("avt_conv3d_igemm_x3_f32_ex", dict(out_row_stride=2, out_h=14, out_w=15),
+     "avt_conv3d_igemm_x3_f32: the remapped rows need an out_h x out_w grid that holds 2 x (8 x 8), no residual"),
+    ("avt_conv3d_igemm_x3_f32_ex", dict(to=8), "avt_conv3d_igemm_x3_f32: bad output extent 8x8x8 (max 7x8x10)"),  # max = the formula's 6x8x8 + (k - 1) / s
+    ("avt_conv3d_igemm_x3_f32_ex", _BIG, "avt_conv3d_igemm_x3_f32: input too large for 32-bit byte offsets"),
+    ("avt_conv3d_igemm_x3_f32_ex", dict(plane_dtype=2), "avt_conv3d_igemm_x3_f32: plane_dtype must be 0 (bf16) or 1 (fp16)"),
+    ("avt_pw_x3", dict(k=192, ldx=192), "avt_pw_x3: unsupported layer K=192 N=64"),
+    ("avt_pw_x3", dict(ldy=56), "avt_pw_x3: bad sizes / leading dimensions"),
+    ("avt_pw_x3", dict(plane_dtype=2), "avt_pw_x3: bad plane_dtype"),
+    ("avt_pw_x3_f32", dict(k=96, ldx=96), "avt_pw_x3_f32: unsupported layer K=96 N=64"),
+    ("avt_pw_x3_f32", dict(ldy=60), "avt_pw_x3_f32: bad sizes / leading dimensions"),
+    ("avt_pw_x3_f32", dict(plane_dtype=2), "avt_pw_x3_f32: bad plane_dtype"),
+]
+
+
+# (with made-up addresses a check that went missing would be a real launch: never where a device is visible)
+@pytest.mark.skipif(torch.cuda.is_available(), reason="made-up device addresses: only on a box without a GPU")
+@pytest.mark.parametrize("entry,bad,message", _REJECTED, ids=["%s-%s" % (e, "-".join(b)) for e, b, _ in _REJECTED])
+def test_bad_arguments_are_rejected_before_any_launch(avt, entry, bad, message):
+    lib = avt._lib.lib()
+    base, args = _ENTRIES[entry]
+    assert set(bad) <= set(base)
+    AVT_ERR_ARG = -1  # include/avt.h
+    assert getattr(lib, entry)(*args(dict(base, **bad))) == AVT_ERR_ARG
+    assert lib.avt_last_error().decode() == message

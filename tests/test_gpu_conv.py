@@ -61,6 +61,7 @@ def _run(avt, dev, cin, cout, k, s, p, dims, relu, with_res, ld_extra=0):
     (1024, 256, (3, 1, 1), (1, 1, 1), (1, 0, 0), (1, 4, 5, 5)),     # XB tile (fragment-order weights in registers): temporal
     (256, 328, (1, 3, 3), (1, 1, 1), (0, 1, 1), (1, 2, 9, 7)),      # ... N tail, ragged M
     (160, 256, (1, 3, 3), (1, 2, 2), (0, 1, 1), (2, 2, 12, 10)),    # ... 45 K units (three all-zero trailing units), strided
+    (24, 40, (2, 1, 3), (1, 2, 1), (1, 0, 2), (2, 5, 8, 6)),        # no two extents / pads alike, output 6 x 4 x 8: a swapped pair shows
 ])
 @pytest.mark.parametrize("relu,with_res", [(True, False), (True, True), (False, False)])
 def test_conv_igemm_matches_torch(avt, dev, cin, cout, k, s, p, dims, relu, with_res):

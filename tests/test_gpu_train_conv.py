@@ -26,6 +26,8 @@ def _cl(t):
     (256, 256, (1, 3, 3), (1, 1, 1), (0, 1, 1), (24, 8, 20, 20), 1.0),   # 76 800 positions: the 256 x 256 tile's IO32 form (fwd + dgrad)
     (512, 256, (3, 1, 1), (1, 1, 1), (1, 0, 0), (41, 8, 15, 15), 1e-6),  # ragged last tile (73 800 rows), long K, tiny gradients
     (256, 1024, (1, 1, 1), (1, 1, 1), (0, 0, 0), (24, 8, 20, 20), 1.0),  # pointwise rows, 4 column tiles; dgrad has K = 1024
+    (64, 72, (3, 1, 5), (1, 1, 1), (1, 0, 2), (2, 5, 7, 6), 1.0),        # no two kernel extents / pads / input extents alike: plain tile
+    (16, 24, (3, 1, 5), (1, 1, 1), (1, 0, 2), (2, 5, 7, 8), 1.0),        # ... the pixel-grouped form (w % 4 == 0)
 ])
 def test_conv_forward_and_gradients_match_fp32_autograd(cin, cout, kernel, stride, pad, dims, gscale):
     from avtex import train_ops

@@ -47,6 +47,8 @@ def _planes(x, pd, dev):
     (512, 256, (3, 1, 1), (1, 1, 1), (1, 0, 0), (1, 8, 46, 46), True),      # temporal taps, M = 16928 = 66.1 tiles
     (64, 256, (1, 3, 3), (1, 2, 2), (0, 1, 1), (1, 4, 130, 130), False),    # strided 3x3, K = 576 (18 half-steps)
     (520, 512, (1, 1, 1), (1, 2, 2), (0, 0, 0), (1, 8, 92, 92), True),      # strided pointwise, K = 520: a 32-step tail of 8
+    # appended last so that the ids of the rows above keep their index
+    (24, 40, (2, 1, 3), (1, 2, 1), (1, 0, 2), (2, 5, 8, 6), True),        # no two extents / pads alike, output 6 x 4 x 8: a swapped pair shows
 ])
 def test_conv_x3_matches_fp32(avt, dev, mode, cin, cout, k, s, p, dims, with_res):
     from avtex.fused_slowfast import Act, FusedConv
