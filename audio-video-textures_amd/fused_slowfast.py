@@ -62,6 +62,20 @@ _KW1_CAP = 32        # pixel grouping of temporal-tap layers stops at this outpu
 PROFILER = None
 
 
+def _observed(name, launch, flops, nbytes):
+    """One kernel launch, handed to the observer when one is set (read here, at call time: bench.py and tests assign it after
+    import).  name: the kernel's symbol, or a function that returns it where finding it costs a library call."""
+    if PROFILER is None:
+        launch()
+    else:
+        PROFILER(name() if callable(name) else name, launch, flops, nbytes)
+
+
+def _rows(dims):
+    """GEMM rows of an NDHWC extent (b, t, h, w)."""
+    return dims[0] * dims[1] * dims[2] * dims[3]
+
+
 class Act:
     """A [M, C] channel slice of a row-major bf16 buffer [M, ld] holding NDHWC activations of extent dims.
     Split-plane ("x3") activations carry a second buffer `lo` of identical geometry (value = buf + lo, include/avt.h)."""
@@ -83,6 +97,10 @@ class Act:
     @property
     def ld(self):
         return self.buf.shape[1]
+
+    @property
+    def rows(self):
+        return _rows(self.dims)
 
     def float(self, plane_dtype=None):
         """fp32 [M, C] copy of the slice (plane_dtype = ops.X3_* for split-plane activations)."""
@@ -188,7 +206,7 @@ class FusedConv:
             raise AvtError("FusedConv: input channels must be a multiple of 8 (got %d)" % self.cin)
         if cout % 8:  # pad the output channels with zero filters (the caller's buffer must be that wide)
             raise AvtError("FusedConv: output channels must be a multiple of 8 (got %d)" % cout)
-        self.wfrag = self.wt_lo = self.wscale = self.wblk = None
+        self.wfrag = self.wt_lo = self.wscale = self.wblk = self.pw = self.lat = None
         taps = self.kernel[0] * self.kernel[1] * self.kernel[2]
         if x3 is not None:
             wf = wt.detach().float()
@@ -209,14 +227,12 @@ class FusedConv:
                 blk = lambda p: p.view(cout, k_all // 32, 32).permute(1, 0, 2).contiguous().to(device)
                 self.wblk = (blk(hi), blk(lo))
             # pointwise stride-1 layers: the streaming kernel (csrc/pw_x3.hip) with LDS-resident weight fragments
-            self.pw = None
             if (_PW_X3 and relu != 2 and self.kernel == (1, 1, 1) and self.stride == (1, 1, 1) and self.pad == (0, 0, 0) and
                     not any(self.crop) and cout % 32 == 0 and ops.pw_x3_supported(self.cin, cout) and
                     (self.cin, cout) not in _PW_X3_SKIP):
                 self.pw = (pack_pw_planes(hi).to(device), pack_pw_planes(lo).to(device))
             # Conv3d [kt,1,1] with a temporal stride (the lateral fast -> slow connections): the streaming kernel's temporal-tap
             # form — the operand gathered from the kt input frames of a position, no tap table (avt_lateral_x3, round 4)
-            self.lat = None
             if ((_LATERAL_X3 == "all" or (self.cin, cout) in _LATERAL_X3) and relu != 2 and self.kernel[0] > 1 and self.kernel[1:] == (1, 1) and self.stride[1:] == (1, 1) and
                     self.pad[1:] == (0, 0) and not any(self.crop) and ops.lateral_x3_supported(self.cin, cout, self.kernel[0])):
                 n_pad = -(-cout // 32) * 32
@@ -243,7 +259,7 @@ class FusedConv:
         """The device kernel the dispatcher of csrc/conv_igemm.hip / conv_x3.hip picks for this layer (bench.py names its
         roofline rows by it; mirrors avt_conv3d_igemm_wfrag_bf16 / avt_conv3d_igemm_x3)."""
         if self.x3 is not None:
-            if getattr(self, "pw", None) is not None or getattr(self, "lat", None) is not None:
+            if self.pw is not None or self.lat is not None:
                 return "pw_x3_kernel<%s>" % ("f16" if self.x3 == ops.X3_F16 else "bf16")
             if ops.conv3d_igemm_x3_xl_picked(self.cout, self.wt.shape[1], m_out):
                 return "conv_x3_xl_kernel<%s>" % ("f16" if self.x3 == ops.X3_F16 else "bf16")
@@ -261,7 +277,7 @@ class FusedConv:
         """Pixel-group factor along W for few-channel layers (see group_weights_w); 1 = plain."""
         if self._folded is None or self.stride[2] != 1 or self.pad[2] != self.kernel[2] // 2:
             return 1
-        if getattr(self, "lat", None) is not None and res is None:
+        if self.lat is not None and res is None:
             return 1  # the temporal-tap streaming kernel takes the layer as it is
         if x.ld != x.C or x.c0 or (out is not None and (out.ld != out.C or out.c0)) or \
                 (res is not None and (res.ld != res.C or res.c0)):
@@ -294,9 +310,8 @@ class FusedConv:
                 self._grouped[g] = sub
             b, t, h, w_ = x.dims
             od = self.out_dims(x.dims)
-            m_out = od[0] * od[1] * od[2] * od[3]
             if out is None:
-                out = new_act(m_out, self.cout, od, self.dev, self.x3 is not None)
+                out = new_act(_rows(od), self.cout, od, self.dev, self.x3 is not None)
             view = lambda a, d, c: Act(a.buf.view(-1, g * c), (d[0], d[1], d[2], d[3] // g),
                                        lo=a.lo.view(-1, g * c) if a.lo is not None else None)
             sub(view(x, x.dims, self.cin), out=view(out, od, self.cout),
@@ -308,13 +323,12 @@ class FusedConv:
             tab = torch.from_numpy(ops.conv3d_ktab(self.cin, self.kernel, x.dims[2], x.dims[3], x.ld)).to(self.dev)
             self._tabs[key] = tab
         od = self.out_dims(x.dims)
+        m_out = _rows(od)  # (not out.rows: with out_rows, `out` has the extent of the rows it is scattered into)
         if out is None:
-            m = od[0] * od[1] * od[2] * od[3]
-            out = new_act(m, self.cout, od, self.dev, self.x3 is not None)
+            out = new_act(m_out, self.cout, od, self.dev, self.x3 is not None)
 
         def launch_x3():
-            m_rows = od[0] * od[1] * od[2] * od[3]
-            blocked = self.wblk is not None and ops.conv3d_igemm_x3_xl_picked(self.cout, self.wt.shape[1], m_rows)
+            blocked = self.wblk is not None and ops.conv3d_igemm_x3_xl_picked(self.cout, self.wt.shape[1], m_out)
             wh, wl = self.wblk if blocked else (self.wt, self.wt_lo)
             ops.conv3d_igemm_x3(x.ptrs, wh, wl, self.bias, res.ptrs if res is not None else None, out.ptrs, tab,
                                 x.dims, self.cin, self.cout, self.kernel, self.stride, self.pad, x.ld, out.ld,
@@ -323,10 +337,9 @@ class FusedConv:
                                 wblk=blocked)
 
         def launch_pw():
-            m_rows = x.dims[0] * x.dims[1] * x.dims[2] * x.dims[3]
             ops.pw_x3(x.ptrs, x.ld, self.cin, self.pw[0], self.pw[1], self.bias, self.wscale,
                       res.ptrs if res is not None else None, res.ld if res is not None else 0, out.ptrs, out.ld, self.cout,
-                      m_rows, self.relu if relu is None else relu, self.x3)
+                      x.rows, self.relu if relu is None else relu, self.x3)
 
         def launch_lat():
             b_, t_, h_, w_ = x.dims
@@ -335,7 +348,7 @@ class FusedConv:
 
         def launch():
             if self.x3 is not None:
-                if getattr(self, "lat", None) is not None and out_rows is None and res is None:
+                if self.lat is not None and out_rows is None and res is None:
                     return launch_lat()
                 return launch_pw() if (self.pw is not None and out_rows is None) else launch_x3()
             ops.conv3d_igemm(x.ptr, self.wt, self.bias, res.ptr if res is not None else 0, out.ptr, tab, x.dims,
@@ -343,14 +356,8 @@ class FusedConv:
                              res.ld if res is not None else 0, self.relu if relu is None else relu,
                              out_dims=od[1:] if any(self.crop) else (0, 0, 0), out_rows=out_rows, wfrag=self.wfrag)
 
-        if PROFILER is None:
-            launch()
-        else:
-            m_out = od[0] * od[1] * od[2] * od[3]
-            m_in = x.dims[0] * x.dims[1] * x.dims[2] * x.dims[3]
-            nb = 2.0 * (m_in * self.cin + m_out * self.cout * (2 if res is not None else 1)) + self.wt.numel() * 2
-            PROFILER(self.kernel_symbol(m_out), launch, m_out * self.alg_flops_per_row,
-                     nb * (2 if self.x3 is not None else 1))
+        nb = 2.0 * (x.rows * self.cin + m_out * self.cout * (2 if res is not None else 1)) + self.wt.numel() * 2
+        _observed(lambda: self.kernel_symbol(m_out), launch, m_out * self.alg_flops_per_row, nb * (2 if self.x3 is not None else 1))
         return out
 
 
@@ -449,6 +456,7 @@ def stem_conv(stem, device, tgroup=1, x3=None):
     conv = FusedConv(None, None, True, device,
                      packed=(wp.reshape(c, -1), bias, 8, (kt, kh, 4), (1, 2, 1), (kt // 2, 3, 2), (0, 0, 1)), x3=x3)
     conv.tgroup, conv.frame_channels, conv.frames_per_tile = 1, c, 0
+    conv.wg, conv._merged = None, {}
     conv.alg_flops_per_row = 2.0 * (kt * kh * kw * 3) * c
     conv.wt_lds = stem_lds_image(conv.wt, kt) if conv.cout % 32 == 0 else None
     conv.wt_lds_lo = stem_lds_image(conv.wt_lo, kt) if conv.cout % 32 == 0 and x3 is not None else None
@@ -697,14 +705,80 @@ def pack_pw(w, device):
     return wp[row, col].to(torch.bfloat16).contiguous().to(device)
 
 
-class _Block:
-    def __init__(self, blk, device):
-        self.b1 = FusedConv(blk.branch1, blk.branch1_bn, False, device) if hasattr(blk, "branch1") else None
+class _BlockBase:
+    """What the bf16 and the split-plane residual blocks share: the four convolutions, the K-concatenated first-block forms and the
+    plain tail (shortcut, a, b, c + residual).  The first block of a slow stage folds its shortcut conv into c's GEMM over
+    K = [x | b-output] when the caller left `extra` spare columns behind x's channels (spare_columns): three launches (a, b, merged
+    c) and no shortcut tensor written and read back as the residual —
+      ccat (res2): stride-1 1x1x1 shortcut and pointwise a; b writes its output into the spare columns of x's rows;
+      scat (res3-5): the shortcut and b ([1,3,3]) have spatial stride 2; b writes into x's OWN rows (2 ho, 2 wo) (out_rows), so c
+                     and the shortcut are one stride-2 pointwise GEMM (split planes: one shared per-channel weight scale).
+    A subclass owns its fused kernels, its b conv (_b) and the order in which its __call__ tries the forms."""
+
+    def __init__(self, blk, device, x3=None):
+        self.b1 = FusedConv(blk.branch1, blk.branch1_bn, False, device, x3=x3) if hasattr(blk, "branch1") else None
         t = blk.branch2
-        self.a = FusedConv(t.a, t.a_bn, True, device)
-        self.b = FusedConv(t.b, t.b_bn, True, device)
-        self.c = FusedConv(t.c, t.c_bn, True, device)  # ReLU applied after the residual add (fused)
-        self.dev = device
+        self.a = FusedConv(t.a, t.a_bn, True, device, x3=x3)
+        self.b = FusedConv(t.b, t.b_bn, True, device, x3=x3)
+        self.c = FusedConv(t.c, t.c_bn, True, device, x3=x3)  # ReLU applied after the residual add (fused)
+        self.x3, self.dev = x3, device
+        self.ccat, self.scat, self.extra = None, None, 0  # (extra = columns the caller must leave free behind x)
+
+    def _kcat(self, s):
+        """c and the 1x1x1 shortcut conv of spatial stride s as ONE FusedConv over K = [x | b-output], or None."""
+        st = (1, s, s)
+        if not (self.b1 is not None and self.c.kernel == (1, 1, 1) and self.b1.kernel == (1, 1, 1) and self.a.stride == (1, 1, 1) and
+                self.c.stride == (1, 1, 1) and self.b.stride == st and self.b1.stride == st and self.b1._folded is not None and
+                (self.a.kernel == (1, 1, 1) if s == 1 else (self.a.kernel[1:] == (1, 1) and self.b.kernel == (1, 3, 3)))):
+            return None
+        (wsc, bsc), (wc, bc) = self.b1._folded, self.c._folded
+        cat = FusedConv(None, None, True, self.dev, folded=(torch.cat([wsc, wc], 1), bc + bsc, st, (0, 0, 0)), x3=self.x3)
+        cat.alg_flops_per_row = self.c.alg_flops_per_row + self.b1.alg_flops_per_row
+        self.extra = self.c.cin
+        return cat
+
+    def _build_kcat(self, one_kernel, scat_on):
+        """Called last by a subclass's __init__: one_kernel = its fused first-block kernel (then neither form is built), scat_on =
+        its switch for the strided form."""
+        if one_kernel is None:
+            self.ccat = self._kcat(1) if _FUSE_KCAT else None
+            self.scat = self._kcat(2) if scat_on and self.ccat is None else None
+
+    def spare_columns(self, dims):
+        """Columns to leave free behind this block's input of extent dims, for its K-concatenated c."""
+        return self.extra
+
+    def _spare(self, x):
+        return x.c0 == 0 and (self.x3 is None or x.lo is not None) and x.ld >= x.C + self.extra and x.C == self.a.cin
+
+    def _kcat_ok(self, x):
+        return self.ccat is not None and self._spare(x)
+
+    def _scat_ok(self, x):
+        return self.scat is not None and self._spare(x) and x.dims[2] % 2 == 0 and x.dims[3] % 2 == 0
+
+    def _behind(self, x):
+        return Act(x.buf, x.dims, x.C, self.extra, lo=x.lo)  # where b's output lands: behind x in the same rows
+
+    def _wide(self, x):
+        return Act(x.buf, x.dims, 0, x.C + self.extra, lo=x.lo)  # [x | b-output]
+
+    def _run_scat(self, x, out, a_pre=None):
+        self.b(a_pre if a_pre is not None else self.a(x), out=self._behind(x), out_rows=(2, x.dims[2], x.dims[3]))
+        return self.scat(self._wide(x), out=out)
+
+    def _plain(self, x, out, a_pre=None):
+        # (shortcut conv first, as the bf16 block always ran it; the split-plane block ran it after b when a_pre was given, which
+        # no block with a shortcut conv ever is: a chained pass hands a_pre to a later block of its own stage, and those have none)
+        sc = self.b1(x) if self.b1 is not None else x
+        return self.c(self._b(a_pre if a_pre is not None else self.a(x)), out=out, res=sc, relu=True)
+
+
+class _Block(_BlockBase):
+    """A residual block on bf16 activations."""
+
+    def __init__(self, blk, device):
+        super().__init__(blk, device)
         # identity-shortcut fast-pathway blocks ([3,1,1] -> [1,3,3] -> [1,1,1], stride 1, width <= 32): one kernel
         self.fused = None
         if (_FUSE_BLOCK and self.b1 is None and self.a.kernel == (3, 1, 1) and self.b.kernel == (1, 3, 3) and
@@ -728,35 +802,8 @@ class _Block:
         if (_C33 and self.b.kernel == (1, 3, 3) and self.b.stride == (1, 1, 1) and self.b.cin == 64 and self.b.cout == 64 and
                 self.b._folded is not None):
             self.c33 = (pack_c33(self.b._folded[0], device), self.b.bias)
-        # first block of a stage with a stride-1 1x1x1 shortcut conv and pointwise a (slow res2): c and the shortcut are
-        # ONE GEMM over K = [x | b-output] when b writes its output into spare columns of x's row buffer — no shortcut
-        # launch, no residual read (self.extra = columns the caller must leave free behind x)
-        self.ccat, self.extra, self._pw = None, 0, {}
-        if (_FUSE_KCAT and self.b1 is not None and self.fused_first is None and self.a.kernel == (1, 1, 1) and
-                self.c.kernel == (1, 1, 1) and self.b1.kernel == (1, 1, 1) and self.a.stride == (1, 1, 1) and
-                self.b.stride == (1, 1, 1) and self.b1.stride == (1, 1, 1) and self.c.stride == (1, 1, 1)):
-            (wsc, bsc), (wc, bc) = self.b1._folded, self.c._folded
-            self.ccat = FusedConv(None, None, True, device,
-                                  folded=(torch.cat([wsc, wc], 1), bc + bsc, (1, 1, 1), (0, 0, 0)))
-            self.ccat.alg_flops_per_row = self.c.alg_flops_per_row + self.b1.alg_flops_per_row
-            self.extra = self.c.cin
-        # first block of a stage with a STRIDED 1x1x1 shortcut (slow res3 / res4 / res5): b ([1,3,3], stride 2) writes its
-        # output behind x's channels in x's OWN rows (2 ho, 2 wo) (avt_conv3d_igemm_rows_bf16), so c and the shortcut are one
-        # stride-2 pointwise GEMM over K = [x | b-output]: no shortcut launch, no shortcut tensor written and re-read
-        self.scat = None
-        if (_FUSE_SCAT and self.b1 is not None and self.fused_first is None and self.ccat is None and
-                self.c.kernel == (1, 1, 1) and self.b1.kernel == (1, 1, 1) and self.b.kernel == (1, 3, 3) and
-                self.b.stride == (1, 2, 2) and self.b1.stride == (1, 2, 2) and self.a.stride == (1, 1, 1) and
-                self.c.stride == (1, 1, 1) and self.a.kernel[1:] == (1, 1) and self.b1._folded is not None):
-            (wsc, bsc), (wc, bc) = self.b1._folded, self.c._folded
-            self.scat = FusedConv(None, None, True, device,
-                                  folded=(torch.cat([wsc, wc], 1), bc + bsc, (1, 2, 2), (0, 0, 0)))
-            self.scat.alg_flops_per_row = self.c.alg_flops_per_row + self.b1.alg_flops_per_row
-            self.extra = self.c.cin
-
-    def _scat_ok(self, x):
-        return (self.scat is not None and x.c0 == 0 and x.ld >= x.C + self.extra and x.C == self.a.cin and
-                x.dims[2] % 2 == 0 and x.dims[3] % 2 == 0)
+        self._pw = {}
+        self._build_kcat(self.fused_first, _FUSE_SCAT)
 
     def can_chain(self, nxt, x):
         """True when this block's c (+ residual) and the next block's a run as ONE pointwise pass (csrc/pw_chain.hip).
@@ -769,7 +816,7 @@ class _Block:
             return False
         if any(v is not None for v in (self.fused, self.fused_first, nxt.fused, nxt.fused_first, nxt.ccat)):
             return False
-        kcat = self.ccat is not None and x.c0 == 0 and x.ld >= x.C + self.extra and x.C == self.a.cin
+        kcat = self._kcat_ok(x)
         k1 = x.C + self.extra if kcat else self.c.cin
         return ops.pw_chain_supported(k1, self.c.cout, nxt.a.cout, not kcat, nxt.a.cin - self.c.cout)
 
@@ -778,119 +825,94 @@ class _Block:
         key = (id(first), id(nxt))
         if self._pw.get("key") != key:
             self._pw = {"key": key, "w1": pack_pw(first._folded[0], self.dev), "w2": pack_pw(nxt.a._folded[0], self.dev)}
-        m = dims[0] * dims[1] * dims[2] * dims[3]
+        m = _rows(dims)
         n1, n2 = first.cout, nxt.a.cout
         k2x = nxt.a.cin - n1
         if (k2x > 0) != (x2 is not None) or (x2 is not None and x2.C != k2x):
             raise AvtError("pw_chain: the next a conv reads %d channels, got y (%d) + x2 (%s)" % (nxt.a.cin, n1, x2 and x2.C))
         if y is None:
-            y = Act(torch.empty((m, n1), dtype=torch.bfloat16, device=self.dev), dims)
-        z = Act(torch.empty((m, n2), dtype=torch.bfloat16, device=self.dev), dims)
+            y = new_act(m, n1, dims, self.dev)
+        z = new_act(m, n2, dims, self.dev)
 
         def launch():
             ops.pw_chain(x1.ptr, x1.ld, k1, self._pw["w1"], first.bias, res.ptr if res is not None else 0,
                          res.ld if res is not None else 0, y.ptr, y.ld, n1, self._pw["w2"], nxt.a.bias, z.ptr, z.ld, n2, m,
                          x2_ptr=x2.ptr if x2 is not None else 0, ldx2=x2.ld if x2 is not None else 0, k2x=k2x)
 
-        if PROFILER is None:
-            launch()
-        else:
-            PROFILER("pw_chain_kernel", launch, m * (first.alg_flops_per_row + nxt.a.alg_flops_per_row),
-                     2.0 * m * (k1 + n1 * (2 if res is not None else 1) + k2x + n2))
+        _observed("pw_chain_kernel", launch, m * (first.alg_flops_per_row + nxt.a.alg_flops_per_row),
+                  2.0 * m * (k1 + n1 * (2 if res is not None else 1) + k2x + n2))
         return y, z
 
     def _b(self, m, out=None):
         """The block's b conv: the strip-resident kernel for 64 -> 64 at the production width, else the implicit GEMM."""
-        if (self.c33 is not None and m.c0 == 0 and m.ld == m.C and ops.conv33_c64_supported(m.C, self.b.cout, m.dims[3])):
-            b, t, h, w = m.dims
-            if out is None:
-                out = Act(torch.empty((b * t * h * w, self.b.cout), dtype=torch.bfloat16, device=self.dev), m.dims)
+        if not (self.c33 is not None and m.c0 == 0 and m.ld == m.C and ops.conv33_c64_supported(m.C, self.b.cout, m.dims[3])):
+            return self.b(m, out=out)
+        b, t, h, w = m.dims
+        if out is None:
+            out = new_act(m.rows, self.b.cout, m.dims, self.dev)
 
-            def launch():
-                ops.conv33_c64(m.ptr, self.c33[0], self.c33[1], out.ptr, b, t, h, w, out.ld, relu=True)
+        def launch():
+            ops.conv33_c64(m.ptr, self.c33[0], self.c33[1], out.ptr, b, t, h, w, out.ld, relu=True)
 
-            if PROFILER is None:
-                launch()
-            else:
-                rows = b * t * h * w
-                PROFILER("c33_kernel", launch, rows * self.b.alg_flops_per_row, 2.0 * rows * 2 * self.b.cout)
-            return out
-        return self.b(m, out=out)
+        _observed("c33_kernel", launch, m.rows * self.b.alg_flops_per_row, 2.0 * m.rows * 2 * self.b.cout)
+        return out
 
     def __call__(self, x, out=None, chain=None, a_pre=None, x2=None):
         """chain = the next block (can_chain(...) holds): returns (y, a-output of the next block) — y written to `out`
         when given, x2 = the further inputs of that a conv (stage boundary); a_pre = this block's a-output when the
         previous block's chained pass has already produced it."""
-        if self.ccat is not None and x.c0 == 0 and x.ld >= x.C + self.extra and x.C == self.a.cin:
-            self._b(self.a(x), out=Act(x.buf, x.dims, x.C, self.extra))  # b's output lands behind x in the same rows
+        if self._kcat_ok(x):
+            self._b(self.a(x), out=self._behind(x))
             if chain is not None:
-                return self._chain(Act(x.buf, x.dims, 0, x.C + self.extra), x.C + self.extra, self.ccat, None, chain, x.dims)
-            return self.ccat(Act(x.buf, x.dims, 0, x.C + self.extra), out=out)
+                return self._chain(self._wide(x), x.C + self.extra, self.ccat, None, chain, x.dims)
+            return self.ccat(self._wide(x), out=out)
         if self._scat_ok(x):
-            m = a_pre if a_pre is not None else self.a(x)
-            self.b(m, out=Act(x.buf, x.dims, x.C, self.extra), out_rows=(2, x.dims[2], x.dims[3]))
-            return self.scat(Act(x.buf, x.dims, 0, x.C + self.extra), out=out)
-        if chain is not None or a_pre is not None:
+            return self._run_scat(x, out, a_pre)
+        if chain is not None:
             sc = self.b1(x) if self.b1 is not None else x
             m = self._b(a_pre if a_pre is not None else self.a(x))
-            if chain is not None:
-                return self._chain(m, self.c.cin, self.c, sc, chain, m.dims, y=out, x2=x2)
-            return self.c(m, out=out, res=sc, relu=True)
+            return self._chain(m, self.c.cin, self.c, sc, chain, m.dims, y=out, x2=x2)
+        if a_pre is not None:
+            return self._plain(x, out, a_pre)
         if (self.fused is not None and out is None and x.c0 == 0 and x.ld == x.C and
                 ops.bottleneck_fused_supported(x.C, x.dims[3])):
             b, t, h, w = x.dims
-            y = Act(torch.empty((b * t * h * w, x.C), dtype=torch.bfloat16, device=self.dev), x.dims)
+            m = x.rows
+            y = new_act(m, x.C, x.dims, self.dev)
 
             def launch():
                 ops.bottleneck_fused(x.ptr, y.ptr, self.fused, b, t, h, w, x.C, tchunk=_FUSE_TCHUNK or (16 if w >= 56 else 32))
 
-            if PROFILER is None:
-                launch()
-            else:
-                m = b * t * h * w
-                fl = m * (self.a.alg_flops_per_row + self.b.alg_flops_per_row + self.c.alg_flops_per_row)
-                PROFILER("bottleneck_kernel", launch, fl, 2.0 * (2 * m * x.C))
+            fl = m * (self.a.alg_flops_per_row + self.b.alg_flops_per_row + self.c.alg_flops_per_row)
+            _observed("bottleneck_kernel", launch, fl, 2.0 * (2 * m * x.C))
             return y
         if (self.fused_first is not None and out is None and x.c0 == 0 and x.ld == x.C and
                 ops.bottleneck_first_supported(x.C, self.c.cout, x.dims[3]) and x.dims[2] % self.b.stride[1] == 0):
             b, t, h, w = x.dims
             st = self.b.stride[1]
             od = (b, t, h // st, w // st)
-            mo = od[0] * od[1] * od[2] * od[3]
-            y = Act(torch.empty((mo, self.c.cout), dtype=torch.bfloat16, device=self.dev), od)
+            m, mo = x.rows, _rows(od)
+            y = new_act(mo, self.c.cout, od, self.dev)
 
             def launch():
                 ops.bottleneck_first(x.ptr, y.ptr, self.fused_first, b, t, h, w, x.C, self.c.cout,
                                      tchunk=_FUSE_TCHUNK or (16 if w >= 56 else 32))
 
-            if PROFILER is None:
-                launch()
-            else:
-                m = b * t * h * w
-                fl = (m * self.a.alg_flops_per_row +
-                      mo * (self.b.alg_flops_per_row + self.c.alg_flops_per_row + self.b1.alg_flops_per_row))
-                PROFILER("bottleneck_kernel", launch, fl, 2.0 * (m * x.C + mo * self.c.cout))
+            fl = (m * self.a.alg_flops_per_row +
+                  mo * (self.b.alg_flops_per_row + self.c.alg_flops_per_row + self.b1.alg_flops_per_row))
+            _observed("bottleneck_kernel", launch, fl, 2.0 * (m * x.C + mo * self.c.cout))
             return y
-        sc = self.b1(x) if self.b1 is not None else x
-        return self.c(self._b(self.a(x)), out=out, res=sc, relu=True)
+        return self._plain(x, out)
 
 
-class _BlockX3:
+class _BlockX3(_BlockBase):
     """A residual block in the contract-grade mode.  Fast-pathway blocks with an identity shortcut (res2-4) and res2's
     8-channel first block run as ONE kernel (csrc/bneck_x3.hip: the x3 counterpart of the bf16 path's bottleneck_fused); slow
-    res2's identity blocks too (fp16 planes, csrc/res2_x3.hip).  The first block of a slow stage folds its shortcut conv into c's
-    GEMM over K = [x | b-output] when the caller left `extra` spare columns behind x's channels: three launches (a, b, merged c) —
-    `ccat` (res2, stride 1) and `scat` (res3-5: the shortcut and b have spatial stride 2, b writes into x's own rows (2 ho, 2 wo)).
-    Every other block, and a first block whose input has no spare columns or an odd height / width, is split-plane convolutions
-    one by one (shortcut, a, b, c + residual)."""
+    res2's identity blocks too (fp16 planes, csrc/res2_x3.hip).  Every other block, and a first block whose input has no spare
+    columns or (scat) an odd height / width, is split-plane convolutions one by one."""
 
     def __init__(self, blk, device, x3):
-        self.b1 = FusedConv(blk.branch1, blk.branch1_bn, False, device, x3=x3) if hasattr(blk, "branch1") else None
-        t = blk.branch2
-        self.a = FusedConv(t.a, t.a_bn, True, device, x3=x3)
-        self.b = FusedConv(t.b, t.b_bn, True, device, x3=x3)
-        self.c = FusedConv(t.c, t.c_bn, True, device, x3=x3)  # ReLU after the residual add (fused)
-        self.x3, self.dev = x3, device
+        super().__init__(blk, device, x3)
         self.fused = None
         shape_ok = (self.a.kernel == (3, 1, 1) and self.b.kernel == (1, 3, 3) and self.c.kernel == (1, 1, 1) and
                     self.a.stride == (1, 1, 1) and self.a.cout <= 32)
@@ -905,9 +927,6 @@ class _BlockX3:
             (wa, ba), (wb, bb), (wc, bc) = self.a._folded, self.b._folded, self.c._folded
             self.fused = pack_bottleneck_x3(wa, ba, wb, bb, wc, bc, x3, device,
                                             shortcut=self.b1._folded if (first8 or strided) else None)
-        # first block of a stage with a stride-1 1x1x1 shortcut conv and a pointwise a (slow res2): c and the shortcut are ONE
-        # pointwise GEMM over K = [x | b-output] when b writes its output into spare columns behind x's channels — no shortcut
-        # launch, no shortcut tensor written and read back as the residual (self.extra = columns the caller leaves free)
         # slow res2: b ([1,3,3] 64 -> 64, stride 1) with the activations as direct MFMA operands (csrc/conv33_x3.hip)
         self.c33 = None
         if (_C33_X3 and self.fused is None and self.b.kernel == (1, 3, 3) and self.b.stride == (1, 1, 1) and
@@ -922,56 +941,35 @@ class _BlockX3:
                 ops.res2_x3_supported(self.c.cout, self.a.cout, 56)):
             (wa, ba), (wb, bb), (wc, bc) = self.a._folded, self.b._folded, self.c._folded
             self.res2 = pack_res2_x3(wa, ba, wb, bb, wc, bc, x3, device)
-        self.ccat, self.extra = None, 0
-        if (_FUSE_KCAT and self.b1 is not None and self.fused is None and self.a.kernel == (1, 1, 1) and
-                self.c.kernel == (1, 1, 1) and self.b1.kernel == (1, 1, 1) and self.a.stride == (1, 1, 1) and
-                self.b.stride == (1, 1, 1) and self.b1.stride == (1, 1, 1) and self.c.stride == (1, 1, 1)):
-            (wsc, bsc), (wc, bc) = self.b1._folded, self.c._folded
-            self.ccat = FusedConv(None, None, True, device, folded=(torch.cat([wsc, wc], 1), bc + bsc, (1, 1, 1), (0, 0, 0)), x3=x3)
-            self.ccat.alg_flops_per_row = self.c.alg_flops_per_row + self.b1.alg_flops_per_row
-            self.extra = self.c.cin
-        # first block of a stage with a STRIDED 1x1x1 shortcut (slow res3 / res4 / res5; the same rule as _Block.scat): b ([1,3,3],
-        # stride 2) writes its output behind x's channels in x's OWN rows (2 ho, 2 wo) (out_rows), so c and the shortcut are one
-        # stride-2 pointwise GEMM over K = [x | b-output] with one shared per-channel weight scale: no shortcut launch, no shortcut
-        # tensor written as two planes and read straight back as c's residual
-        self.scat = None
-        if (_FUSE_SCAT_X3 and self.b1 is not None and self.fused is None and self.ccat is None and
-                self.c.kernel == (1, 1, 1) and self.b1.kernel == (1, 1, 1) and self.b.kernel == (1, 3, 3) and
-                self.b.stride == (1, 2, 2) and self.b1.stride == (1, 2, 2) and self.a.stride == (1, 1, 1) and
-                self.c.stride == (1, 1, 1) and self.a.kernel[1:] == (1, 1) and self.b1._folded is not None and
-                (self.a.cin, self.c.cout) not in _SCAT_X3_SKIP):
-            (wsc, bsc), (wc, bc) = self.b1._folded, self.c._folded
-            self.scat = FusedConv(None, None, True, device, folded=(torch.cat([wsc, wc], 1), bc + bsc, (1, 2, 2), (0, 0, 0)), x3=x3)
-            self.scat.alg_flops_per_row = self.c.alg_flops_per_row + self.b1.alg_flops_per_row
-            self.extra = self.c.cin
+        self._build_kcat(self.fused, _FUSE_SCAT_X3 and (self.a.cin, self.c.cout) not in _SCAT_X3_SKIP)
 
-    def _scat_ok(self, x):
-        return (self.scat is not None and x.c0 == 0 and x.lo is not None and x.ld >= x.C + self.extra and x.C == self.a.cin and
-                x.dims[2] % 2 == 0 and x.dims[3] % 2 == 0)
+    def spare_columns(self, dims):
+        """The strided form's columns only where it can run (even height and width); the bf16 walk leaves them regardless.
+        (A block has ccat or scat, never both, and in SlowFast res2 has ccat and res3-5 have scat, so this is the rule the
+        split-plane walk always had: every column at the stem's buffer, the even-extent test at the later ones.)"""
+        return self.extra if self.scat is None or (dims[2] % 2 == 0 and dims[3] % 2 == 0) else 0
 
-    def can_chain(self, nxt):
+    def can_chain(self, nxt, x):
         """True when this block's c (+ residual + ReLU) and the next block's a (+ ReLU) run as ONE pointwise pass
-        (csrc/pw_x3.hip, the chained form): both pointwise on the streaming kernel, identity shortcut here."""
+        (csrc/pw_x3.hip, the chained form): both pointwise on the streaming kernel, identity shortcut here.  Never across a stage
+        boundary: the next stage's a also reads the lateral channels (nxt.a.cin > self.c.cout)."""
         if self.res2 is not None or (nxt is not None and nxt.res2 is not None):
             return False  # (a block that runs as one kernel neither hands its c to a chain nor takes its a from one)
         if self.scat is not None or (nxt is not None and nxt.scat is not None):
             return False  # (nor does a block whose c is the K-concatenated strided GEMM: its c reads x's rows, its a x's slice)
         return (_CHAIN_X3 and nxt is not None and self.b1 is None and self.fused is None and nxt.fused is None and
-                getattr(self.c, "pw", None) is not None and getattr(nxt.a, "pw", None) is not None and nxt.ccat is None and
+                self.c.pw is not None and nxt.a.pw is not None and nxt.ccat is None and
                 nxt.a.cin == self.c.cout and ops.pw_chain_x3_supported(self.c.cin, self.c.cout, nxt.a.cout))
 
     def __call__(self, x, out=None, chain=None, a_pre=None):
         """chain = the next block (can_chain(...) holds): returns (y, a-output of the next block); a_pre = this block's a-output
         when the previous block's chained pass has already produced it."""
         if chain is None and a_pre is None and self._scat_ok(x):
-            self.b(self.a(x), out=Act(x.buf, x.dims, x.C, self.extra, lo=x.lo), out_rows=(2, x.dims[2], x.dims[3]))
-            return self.scat(Act(x.buf, x.dims, 0, x.C + self.extra, lo=x.lo), out=out)
-        if chain is not None or a_pre is not None:
+            return self._run_scat(x, out)
+        if chain is not None:
             m = self._b(a_pre if a_pre is not None else self.a(x))
             sc = self.b1(x) if self.b1 is not None else x
-            if chain is None:
-                return self.c(m, out=out, res=sc, relu=True)
-            rows = m.dims[0] * m.dims[1] * m.dims[2] * m.dims[3]
+            rows = m.rows
             y = out if out is not None else new_act(rows, self.c.cout, m.dims, self.dev, True)
             z = new_act(rows, chain.a.cout, m.dims, self.dev, True)
 
@@ -980,32 +978,28 @@ class _BlockX3:
                                 self.c.cout, True, chain.a.pw, chain.a.bias, chain.a.wscale, z.ptrs, z.ld, chain.a.cout, rows,
                                 self.x3)
 
-            if PROFILER is None:
-                launch()
-            else:
-                PROFILER("pw_chain_x3_kernel", launch, rows * (self.c.alg_flops_per_row + chain.a.alg_flops_per_row),
-                         4.0 * rows * (self.c.cin + 2 * self.c.cout + chain.a.cout))
+            _observed("pw_chain_x3_kernel", launch, rows * (self.c.alg_flops_per_row + chain.a.alg_flops_per_row),
+                      4.0 * rows * (self.c.cin + 2 * self.c.cout + chain.a.cout))
             return y, z
-        if (self.res2 is not None and chain is None and a_pre is None and x.lo is not None and x.C == self.a.cin and
+        if a_pre is not None:
+            return self._plain(x, out, a_pre)
+        if (self.res2 is not None and x.lo is not None and x.C == self.a.cin and
                 ops.res2_x3_supported(self.c.cout, self.a.cout, x.dims[3])):
             b, t, h, w = x.dims
-            rows = b * t * h * w
+            rows = x.rows
             y = out if out is not None else new_act(rows, self.c.cout, x.dims, self.dev, True)
 
             def launch():
                 ops.res2_x3(x.ptrs, x.ld, y.ptrs, y.ld, self.res2, b, t, h, w, self.x3)
 
-            if PROFILER is None:
-                launch()
-            else:
-                fl = rows * (self.a.alg_flops_per_row + self.b.alg_flops_per_row + self.c.alg_flops_per_row)
-                PROFILER("res2_x3_kernel", launch, fl, 4.0 * rows * 2 * self.c.cout)
+            fl = rows * (self.a.alg_flops_per_row + self.b.alg_flops_per_row + self.c.alg_flops_per_row)
+            _observed("res2_x3_kernel", launch, fl, 4.0 * rows * 2 * self.c.cout)
             return y
         if (self.fused is not None and out is None and x.c0 == 0 and x.ld == x.C and
                 ops.bneck_x3_supported(x.C, self.c.cout, x.dims[3]) and x.dims[2] % self.st == 0):
             b, t, h, w = x.dims
             od = (b, t, h // self.st, w // self.st)
-            mo = od[0] * od[1] * od[2] * od[3]
+            m, mo = x.rows, _rows(od)
             y = new_act(mo, self.c.cout, od, self.dev, True)
 
             def launch():
@@ -1014,19 +1008,14 @@ class _BlockX3:
                 # 14-wide stage (round 4): 11 frames per workgroup = 3 chunks per clip: 996 workgroups = 3.9 rounds of the 256 CUs at
                 # 166 clips (4 chunks: 5.2 rounds) and 2 halo frames per 11 instead of per 8 (profiles/r04/probe_bneck_early_load_ab.log)
 
-            if PROFILER is None:
-                launch()
-            else:
-                m = b * t * h * w
-                fl = m * self.a.alg_flops_per_row + mo * (self.b.alg_flops_per_row + self.c.alg_flops_per_row +
-                                                          (self.b1.alg_flops_per_row if self.b1 is not None else 0.0))
-                PROFILER("bneck_x3_kernel", launch, fl, 4.0 * (m * x.C + mo * self.c.cout))
+            fl = m * self.a.alg_flops_per_row + mo * (self.b.alg_flops_per_row + self.c.alg_flops_per_row +
+                                                      (self.b1.alg_flops_per_row if self.b1 is not None else 0.0))
+            _observed("bneck_x3_kernel", launch, fl, 4.0 * (m * x.C + mo * self.c.cout))
             return y
-        if self.ccat is not None and x.c0 == 0 and x.lo is not None and x.ld >= x.C + self.extra and x.C == self.a.cin:
-            self._b(self.a(x), out=Act(x.buf, x.dims, x.C, self.extra, lo=x.lo))  # b's output lands behind x in the same rows
-            return self.ccat(Act(x.buf, x.dims, 0, x.C + self.extra, lo=x.lo), out=out)
-        sc = self.b1(x) if self.b1 is not None else x
-        return self.c(self._b(self.a(x)), out=out, res=sc, relu=True)
+        if self._kcat_ok(x):
+            self._b(self.a(x), out=self._behind(x))
+            return self.ccat(self._wide(x), out=out)
+        return self._plain(x, out)
 
     def _b(self, m, out=None):
         """The block's b conv: the direct-operand kernel for 64 -> 64 [1,3,3], else the implicit GEMM."""
@@ -1034,16 +1023,12 @@ class _BlockX3:
             return self.b(m, out=out)
         b, t, h, w = m.dims
         if out is None:
-            out = new_act(b * t * h * w, self.b.cout, m.dims, self.dev, True)
+            out = new_act(m.rows, self.b.cout, m.dims, self.dev, True)
 
         def launch():
             ops.conv33_x3(m.ptrs, self.c33, out.ptrs, b, t, h, w, m.ld, out.ld, self.x3, relu=True)
 
-        if PROFILER is None:
-            launch()
-        else:
-            rows = b * t * h * w
-            PROFILER("conv33_x3_kernel", launch, rows * self.b.alg_flops_per_row, 4.0 * rows * 2 * self.b.cout)
+        _observed("conv33_x3_kernel", launch, m.rows * self.b.alg_flops_per_row, 4.0 * m.rows * 2 * self.b.cout)
         return out
 
 
@@ -1106,42 +1091,36 @@ class SlowFastMFMA(nn.Module):
         lds_path = _STEM_LDS and conv.wt_lds is not None and ops.stem_conv_supported(h, w // 2, conv.cout)
         kt, st, pt = conv.kernel[0], conv.stride[0], conv.pad[0]
         od = conv.out_dims(x.dims)
-        m_out = od[0] * od[1] * od[2] * od[3]
+        m_out = _rows(od)
         if lds_path and _STEM_POOL and (kt == 1 or _STEM_POOL > 1) and (h // 2) % 8 == 0:
             # production shape: patch-resident stem kernel with the max-pool fused (the conv output stays on chip)
             pd = (b, t, od[2] // 2, od[3] // 2)
             cf = conv.frame_channels
             if out is None:
-                out = Act(torch.empty((pd[0] * pd[1] * pd[2] * pd[3], cf), dtype=torch.bfloat16, device=self.dev), pd)
+                out = new_act(_rows(pd), cf, pd, self.dev)
 
             def launch():
                 ops.stem_conv_pool(x.ptr, conv.wt_lds, conv.bias, out.ptr, b, t, h, w // 2, conv.cout, kt, st, pt,
                                    conv.tgroup, out.ld)
 
-            if PROFILER is None:
-                launch()
-            else:
-                PROFILER("stem_kernel", launch, m_out * conv.alg_flops_per_row,
-                         2.0 * (x.buf.numel() + pd[0] * pd[1] * pd[2] * pd[3] * cf) + conv.wt.numel() * 2)
+            _observed("stem_kernel", launch, m_out * conv.alg_flops_per_row,
+                      2.0 * (x.buf.numel() + _rows(pd) * cf) + conv.wt.numel() * 2)
             return out, pd
         if lds_path:
-            y = Act(torch.empty((m_out, conv.cout), dtype=torch.bfloat16, device=self.dev), od)
+            y = new_act(m_out, conv.cout, od, self.dev)
 
             def launch():
                 ops.stem_conv(x.ptr, conv.wt_lds, conv.bias, y.ptr, b, t, h, w // 2, conv.cout, kt, st, pt, relu=True)
 
-            if PROFILER is None:
-                launch()
-            else:
-                PROFILER("stem_kernel", launch, m_out * conv.alg_flops_per_row,
-                         2.0 * (x.buf.numel() + m_out * conv.cout) + conv.wt.numel() * 2)
+            _observed("stem_kernel", launch, m_out * conv.alg_flops_per_row,
+                      2.0 * (x.buf.numel() + m_out * conv.cout) + conv.wt.numel() * 2)
         else:
             y = conv(x)
         _, tg, h2, w2 = y.dims
         pd = (b, t, (h2 - 1) // 2 + 1, (w2 - 1) // 2 + 1)
         cf = conv.frame_channels
         if out is None:
-            out = Act(torch.empty((pd[0] * pd[1] * pd[2] * pd[3], cf), dtype=torch.bfloat16, device=self.dev), pd)
+            out = new_act(_rows(pd), cf, pd, self.dev)
         ops.maxpool_hw3s2(y.ptr, out.ptr, b * tg, h2, w2, conv.cout, y.ld, out.ld, tgroup=conv.tgroup)
         return out, pd
 
@@ -1162,14 +1141,14 @@ class SlowFastMFMA(nn.Module):
         x = Act(clip.hi.view(nf * h * (w // 2), 8), (sb, st_, h, w // 2), lo=clip.lo.view(nf * h * (w // 2), 8))
         pool_idx = clip.idx.reshape(-1) if per_frame else None
         merged = None
-        if (table and lds_path and _STEM_MERGE and conv.frames_per_tile == 2 and getattr(conv, "wg", None) is not None and
+        if (table and lds_path and _STEM_MERGE and conv.frames_per_tile == 2 and conv.wg is not None and
                 clip.start is not None and t == 32):
             merged = merged_stem_taps(conv, clip.win_len, self.dev)
         if merged is not None:
             # the fast stem on a frame table, the frame taps of one source frame summed into one (5 patches and weight slabs per
             # output-frame group instead of 8 at W = 20)
             od = conv.out_dims(x.dims)
-            m_out = od[0] * od[1] * od[2] * od[3]
+            m_out = _rows(od)
             y = new_act(m_out, conv.cout, od, self.dev, True)
             src = merged["src"]
             taps = torch.where(src.unsqueeze(0) >= 0, clip.start.view(-1, 1, 1) + src.unsqueeze(0), src.unsqueeze(0)).contiguous()
@@ -1179,15 +1158,12 @@ class SlowFastMFMA(nn.Module):
                                         w // 2, conv.cout, conv.kernel[0], conv.stride[0], conv.pad[0], self.x3, taps,
                                         merged["tiles"], merged["ktm"], nf, relu=True)
 
-            if PROFILER is None:
-                launch()
-            else:
-                PROFILER("stem_kernel<x3>", launch, m_out * conv.alg_flops_per_row,
-                         4.0 * (x.buf.numel() + m_out * conv.cout) + conv.wt.numel() * 4)
+            _observed("stem_kernel<x3>", launch, m_out * conv.alg_flops_per_row,
+                      4.0 * (x.buf.numel() + m_out * conv.cout) + conv.wt.numel() * 4)
         elif lds_path:
             # production shape: the patch-resident stem kernel in its plane-pair form (no im2col gather)
             od = conv.out_dims(x.dims)
-            m_out = od[0] * od[1] * od[2] * od[3]
+            m_out = _rows(od)
             y = new_act(m_out, conv.cout, od, self.dev, True)
 
             def launch():
@@ -1196,18 +1172,15 @@ class SlowFastMFMA(nn.Module):
                                  frames_per_tile=conv.frames_per_tile, frame_idx=clip.idx if (table and not per_frame) else None,
                                  table_frames=nf if (table and not per_frame) else 0)
 
-            if PROFILER is None:
-                launch()
-            else:
-                PROFILER("stem_kernel<x3>", launch, m_out * conv.alg_flops_per_row,
-                         4.0 * (x.buf.numel() + m_out * conv.cout) + conv.wt.numel() * 4)
+            _observed("stem_kernel<x3>", launch, m_out * conv.alg_flops_per_row,
+                      4.0 * (x.buf.numel() + m_out * conv.cout) + conv.wt.numel() * 4)
         else:
             y = conv(x)
         _, tg, h2, w2 = y.dims
         pd = (b, t, (h2 - 1) // 2 + 1, (w2 - 1) // 2 + 1)
         cf = conv.frame_channels
         if out is None:
-            out = new_act(pd[0] * pd[1] * pd[2] * pd[3], cf, pd, self.dev, True)
+            out = new_act(_rows(pd), cf, pd, self.dev, True)
         if per_frame:
             ops.maxpool_hw3s2_x3(y.ptrs, out.ptrs, b * t, h2, w2, conv.cout, y.ld, out.ld, self.x3, frame_idx=pool_idx)
         else:
@@ -1215,63 +1188,23 @@ class SlowFastMFMA(nn.Module):
         return out, pd
 
     @torch.no_grad()
-    def _forward_x3(self, slow, fast):
-        """The contract-grade forward: the module's layers one by one on split-plane activations (no fused forms)."""
-        b = slow.shape[0]
-        f_act, df = self._stem_x3(self.stem_f, fast)
-        cs, cf = self.stem_s.frame_channels, self.stem_f.frame_channels
-        hs, ws = (slow.shape[2] // 2 - 1) // 2 + 1, (slow.shape[3] // 2 - 1) // 2 + 1
-        ds = (b, slow.shape[1], hs, ws)
-        extra = getattr(self.stages[0][0][0], "extra", 0)  # spare columns for the first slow block's K-concatenated c
-        cat = new_act(ds[0] * ds[1] * ds[2] * ds[3], cs + 2 * cf + extra, ds, self.dev, True)
-        sl = lambda a, c0, c: Act(a.buf, a.dims, c0, c, lo=a.lo)
-        self._stem_x3(self.stem_s, slow, out=sl(cat, 0, cs))
-        self.fuse[0](f_act, out=sl(cat, cs, 2 * cf))
-        s_act = sl(cat, 0, cs + 2 * cf)
-        for k, (slow_blocks, fast_blocks) in enumerate(self.stages):
-            for blk in fast_blocks:
-                f_act = blk(f_act)
-            last = k == len(self.stages) - 1
-            pre = None  # the a-output of the coming slow block, when the previous block's chained pass produced it
-            for i, blk in enumerate(slow_blocks):
-                nxt = slow_blocks[i + 1] if i + 1 < len(slow_blocks) else None
-                if blk.can_chain(nxt):
-                    s_act, pre = blk(s_act, chain=nxt, a_pre=pre)
-                    continue
-                a_pre, pre = pre, None
-                if i == len(slow_blocks) - 1 and not last:  # straight into the next fusion's concat buffer
-                    od = blk.b.out_dims(blk.a.out_dims(s_act.dims))
-                    cs, cf = blk.c.cout, f_act.C
-                    # (+ spare columns for the next stage's K-concatenated strided c, where its rows are even: _BlockX3.scat)
-                    extra = self.stages[k + 1][0][0].extra if (od[2] % 2 == 0 and od[3] % 2 == 0) else 0
-                    cat = new_act(od[0] * od[1] * od[2] * od[3], cs + 2 * cf + extra, od, self.dev, True)
-                    blk(s_act, out=sl(cat, 0, cs), a_pre=a_pre)
-                    self.fuse[k + 1](f_act, out=sl(cat, cs, 2 * cf))
-                    s_act = sl(cat, 0, cs + 2 * cf)
-                else:
-                    s_act = blk(s_act, a_pre=a_pre)
-        emb = torch.empty((b, s_act.C + f_act.C), dtype=torch.float32, device=self.dev)
-        ops.mean_positions_x3(s_act.ptrs, b, s_act.buf.shape[0] // b, s_act.C, s_act.ld, emb, 0, self.x3)
-        ops.mean_positions_x3(f_act.ptrs, b, f_act.buf.shape[0] // b, f_act.C, f_act.ld, emb, s_act.C, self.x3)
-        return emb
-
-    @torch.no_grad()
     def forward_ndhwc4(self, slow, fast):
         """slow [B,8,H,W,4], fast [B,32,H,W,4] bf16 channels-last clips (ops.clip_pack layout "ndhwc4"); ops.SplitClip
         pairs (clip_pack(..., planes=self.planes)) in the contract-grade modes."""
-        if self.x3 is not None:
-            return self._forward_x3(slow, fast)
+        x3 = self.x3 is not None
+        stem = self._stem_x3 if x3 else self._stem
         b = slow.shape[0]
-        f_act, df = self._stem(self.stem_f, fast)
+        f_act, df = stem(self.stem_f, fast)
         cs, cf = self.stem_s.frame_channels, self.stem_f.frame_channels
         hs, ws = (slow.shape[2] // 2 - 1) // 2 + 1, (slow.shape[3] // 2 - 1) // 2 + 1
         ds = (b, slow.shape[1], hs, ws)
-        # the slow stem is pooled straight into the concat buffer of the first lateral fusion
-        extra = self.stages[0][0][0].extra  # spare columns for the first slow block's K-concatenated c (see _Block)
-        sbuf = torch.empty((ds[0] * ds[1] * ds[2] * ds[3], cs + 2 * cf + extra), dtype=torch.bfloat16, device=self.dev)
-        self._stem(self.stem_s, slow, out=Act(sbuf, ds, 0, cs))
-        self.fuse[0](f_act, out=Act(sbuf, ds, cs, 2 * cf))
-        s_act = Act(sbuf, ds, 0, cs + 2 * cf)
+        sl = lambda a, c0, c: Act(a.buf, a.dims, c0, c, lo=a.lo)
+        # the slow stem is pooled straight into the concat buffer of the first lateral fusion (+ the spare columns for the first
+        # slow block's K-concatenated c, see _BlockBase)
+        cat = new_act(_rows(ds), cs + 2 * cf + self.stages[0][0][0].spare_columns(ds), ds, self.dev, x3)
+        stem(self.stem_s, slow, out=sl(cat, 0, cs))
+        self.fuse[0](f_act, out=sl(cat, cs, 2 * cf))
+        s_act = sl(cat, 0, cs + 2 * cf)
         pre = None  # the a-output of the coming slow block, when the previous block's chained pass produced it
         for k, (slow_blocks, fast_blocks) in enumerate(self.stages):
             for blk in fast_blocks:
@@ -1288,20 +1221,24 @@ class SlowFastMFMA(nn.Module):
                     od = blk.b.out_dims(blk.a.out_dims(s_act.dims))
                     cs, cf = blk.c.cout, f_act.C
                     nxt0 = self.stages[k + 1][0][0]
-                    sbuf = torch.empty((od[0] * od[1] * od[2] * od[3], cs + 2 * cf + nxt0.extra), dtype=torch.bfloat16,
-                                       device=self.dev)  # (+ spare columns for the next block's K-concatenated c)
+                    cat = new_act(_rows(od), cs + 2 * cf + nxt0.spare_columns(od), od, self.dev, x3)
+                    y, lateral = sl(cat, 0, cs), sl(cat, cs, 2 * cf)
                     if blk.can_chain(nxt0, s_act):
-                        # ... and the next stage's first a conv reads [y | lateral]: lateral first, then one chained pass
-                        self.fuse[k + 1](f_act, out=Act(sbuf, od, cs, 2 * cf))
-                        _, pre = blk(s_act, out=Act(sbuf, od, 0, cs), chain=nxt0, a_pre=a_pre, x2=Act(sbuf, od, cs, 2 * cf))
+                        # ... and the next stage's first a conv reads [y | lateral]: lateral first, then one chained pass (bf16
+                        # only: a split-plane block never chains into an a that reads more than its c wrote)
+                        self.fuse[k + 1](f_act, out=lateral)
+                        _, pre = blk(s_act, out=y, chain=nxt0, a_pre=a_pre, x2=lateral)
                     else:
-                        blk(s_act, out=Act(sbuf, od, 0, cs), a_pre=a_pre)
-                        self.fuse[k + 1](f_act, out=Act(sbuf, od, cs, 2 * cf))
-                    s_act = Act(sbuf, od, 0, cs + 2 * cf)
+                        blk(s_act, out=y, a_pre=a_pre)
+                        self.fuse[k + 1](f_act, out=lateral)
+                    s_act = sl(cat, 0, cs + 2 * cf)
                 else:
                     s_act = blk(s_act, a_pre=a_pre)
         # head (models.py:576-580 surgery): global average pool per pathway, concat slow | fast
         emb = torch.empty((b, s_act.C + f_act.C), dtype=torch.float32, device=self.dev)
-        ops.mean_positions(s_act.ptr, b, s_act.buf.shape[0] // b, s_act.C, s_act.ld, emb, 0)
-        ops.mean_positions(f_act.ptr, b, f_act.buf.shape[0] // b, f_act.C, f_act.ld, emb, s_act.C)
+        for act, c0 in ((s_act, 0), (f_act, s_act.C)):
+            if x3:
+                ops.mean_positions_x3(act.ptrs, b, act.buf.shape[0] // b, act.C, act.ld, emb, c0, self.x3)
+            else:
+                ops.mean_positions(act.ptr, b, act.buf.shape[0] // b, act.C, act.ld, emb, c0)
         return emb
