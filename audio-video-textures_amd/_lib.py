@@ -106,6 +106,8 @@ SIGNATURES = {
     "avt_sgd_job_bytes": [],
     "avt_sgd_multi": [_vp, _vp, C.c_int, _vp, _vp],
     "avt_sgd_upload": [_vp, _vp, C.c_int64, _vp],
+    "avt_pack_job_bytes": [],
+    "avt_grad_pack_multi": [_vp, _vp, C.c_int, _vp, _vp],
     "avt_maxpool_train_fwd": [_vp, _vp, _vp] + [C.c_int] * 4 + [C.c_int64, _vp],
     "avt_maxpool_train_bwd": [_vp, _vp, _vp] + [C.c_int] * 4 + [C.c_int64, _vp],
     "avt_maxpool3d_train_fwd": [_vp, _vp, _vp] + [C.c_int] * 5 + [C.c_int64, _vp],

@@ -56,13 +56,20 @@ def build_parser():
            "the first group only as DataParallel keeps replica 0's buffers; 1 = over the rank's whole batch; -1 = one group "
            "per item (batch 8 on 8 GPUs in the reference)")
     a("--train_graph", default=0, type=int, choices=[0, 1],
-      help="1: train() captures the device side of a step (forward, loss, backward, optimizer) once per batch shape as a HIP graph and "
-           "replays it (train_ops.GraphedStep) — for small batches whose launches the host issues slower than the device runs them; one "
-           "process only; the first batch of a shape also serves the two warm-up steps (not in the reference)")
+      help="1: train() captures the device side of a step once per batch shape as a HIP graph and replays it (train_ops.GraphedStep) — "
+           "for small batches whose launches the host issues slower than the device runs them.  One process: forward, loss, backward and "
+           "optimizer are the graph; with torch's SGD the first batch of a shape also serves the two warm-up steps (not in the "
+           "reference).  Under torch.distributed.run every rank replays forward, loss, backward and one launch that packs the gradients "
+           "into a flat buffer (train_ops.GradExchange); one all-reduce and the optimizer follow each replay eagerly, the model is not "
+           "wrapped in DistributedDataParallel, and every batch takes one step with either optimizer")
     a("--train_optimizer", default="torch", choices=["torch", "hip"],
       help="torch: torch.optim.SGD (the reference's, main.py:440); hip: train_ops.ArenaSGD — the same update as one HIP launch over all "
-           "parameters with --lr / --momentum / --weight_decay read from device memory: with --train_graph 1 the replayed step then "
-           "follows the StepLR schedule (torch's SGD keeps the rate it was captured with) and the first batch of a shape takes one step")
+           "parameters with --lr / --momentum / --weight_decay read from device memory: with --train_graph 1 in one process the replayed "
+           "step then follows the StepLR schedule (torch's SGD keeps the rate it was captured with) and the first batch of a shape takes "
+           "one step; across ranks the optimizer runs outside the graph and both choices follow the schedule")
+    a("--dist_backend", default=None, choices=["nccl", "gloo"],
+      help="torch.distributed backend under torch.distributed.run: nccl = RCCL, one rank per GPU; gloo = ranks that may share a GPU (RCCL "
+           "refuses two ranks on one device); default: nccl where a GPU is visible, gloo otherwise")
     a("--train_input", default="loader", choices=["loader", "device"],
       help="where train() gets its batches: loader = torch DataLoader over AudioVideoSegments (host preprocessing, the reference's "
            "path); device = dataset.DeviceSegmentBatcher: the video resident in HBM (SlowFast: uint8 frames; other encoders: the "
@@ -131,8 +138,10 @@ parser = build_parser()
 
 def main(args, video_name, itr=0):
     best_loss = 1000000
-    rank, world, local = avt_dist.init_from_env()
+    rank, world, local = avt_dist.init_from_env(backend=getattr(args, "dist_backend", None))
     device = torch.device("cuda", local)
+    if world > 1 and torch.distributed.get_backend() == "gloo":  # (gloo ranks may share one GPU; RCCL ranks have one each)
+        device = torch.device("cuda", local % max(torch.cuda.device_count(), 1))
     torch.cuda.set_device(device)
     if not args.evaluate and not args.visualize_evaluate:
         dataset_train = AudioVideoSegments(args, video_name, split="train")
@@ -200,7 +209,14 @@ def main(args, video_name, itr=0):
             print("training convolutions: %s" % ("split-plane MFMA (x3: fp16 planes forward 2^-22, bf16 planes gradients 2^-16, "
                                                   "fp32 accumulation)" if mode == "x3" else "MIOpen fp32"))
     if world > 1 and not args.evaluate:  # weights resident per rank, gradients all-reduced over RCCL
-        model = wrap_ddp(model, device, local)
+        if getattr(args, "train_graph", 0):
+            # every rank replays its step as a HIP graph and the gradients cross the ranks in one flat buffer outside it (train.train):
+            # no DistributedDataParallel wrapper, whose bucketed all-reduce is not captured
+            from . import train_ops
+
+            model = train_ops.prepare_ranks(model)
+        else:
+            model = wrap_ddp(model, device, local)
     torch.backends.cudnn.benchmark = True
     tb_logdir = os.path.join(args.logdir, logname)
     os.makedirs(tb_logdir, exist_ok=True)
@@ -243,14 +259,9 @@ def wrap_ddp(model, device, local):
     t_a_mlp (models.py:267-284) and VGGish's fc stack (vggish.py:45) — are frozen first: DDP's reducer would otherwise wait
     for gradients that never come (DataParallel tolerated them), and ~300 M dead parameters would be all-reduced every
     step.  find_unused_parameters covers plugin encoders with dead parameters of their own."""
-    net = model
-    for name in ("q_a_mlp", "t_a_mlp"):
-        if hasattr(net, name):
-            getattr(net, name).requires_grad_(False)
-    for name in ("q_a_encoder", "t_a_encoder"):
-        enc = getattr(net, name, None)
-        if isinstance(enc, VGGish) and hasattr(enc, "fc"):
-            enc.fc.requires_grad_(False)
+    from . import train_ops
+
+    train_ops.freeze_checkpoint_only_modules(model)
     ddp = torch.nn.parallel.DistributedDataParallel(model, device_ids=[local] if device.type == "cuda" else None,
                                                     find_unused_parameters=True)
     if device.type == "cuda":

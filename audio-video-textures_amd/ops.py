@@ -671,6 +671,18 @@ def sgd_upload(dst, src_pinned, nbytes):
     _lib.check(_lib.lib().avt_sgd_upload(_p(dst), _p(src_pinned), int(nbytes), _stream()), "avt_sgd_upload")
 
 
+def pack_job_bytes():
+    return int(_lib.lib().avt_pack_job_bytes())
+
+
+def grad_pack_multi(jobs, blk2job, nblocks, scale):
+    """dst = src * scale[0] over every job of a DEVICE table of AvtPackJob (include/avt.h) in one launch, `scale` a device fp32 tensor
+    of one element the kernel loads (train_ops.GradExchange builds the table: every gradient of a step into one flat buffer)."""
+    assert jobs.is_cuda and blk2job.is_cuda and blk2job.dtype == torch.int32 and blk2job.numel() == nblocks
+    assert scale.is_cuda and scale.dtype == torch.float32 and scale.numel() == 1
+    _lib.check(_lib.lib().avt_grad_pack_multi(_p(jobs), _p(blk2job), int(nblocks), _p(scale), _stream()), "avt_grad_pack_multi")
+
+
 def weight_planes_t_f32(w3d, sel):
     """[cout, taps, cin] fp32 -> (hi, lo) bf16 planes [cin, len(sel) * cout] with out[ci][a][co] = w[co][sel[a]][ci]: the input
     gradient's filter (sel = all taps reversed) or one residue class of a strided layer's (csrc/stem_train.hip)."""

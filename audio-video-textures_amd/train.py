@@ -26,15 +26,25 @@ def train(train_loader, model, optimizer, args, epoch, tb_logger=None):
     if not next(model.parameters()).is_cuda:
         raise AvtError("train(): model must be on the MI355X (model.cuda()); the loss runs on the HIP kernels, no CPU fallback")
     criterion = InfoNCECriterion()
-    # --train_graph: the device side of a step (forward, loss, backward, optimizer) captured once per batch shape as a HIP graph and
-    # replayed (train_ops.GraphedStep) — for small batches, whose ~3400 launches the host issues slower than the device runs them
-    # (config 5 on 8 GPUs: one item per rank).  One process only: a DDP all-reduce is not captured.
+    # --train_graph: the device side of a step captured once per batch shape as a HIP graph and replayed (train_ops.GraphedStep) — for
+    # small batches, whose ~3400 launches the host issues slower than the device runs them (config 5 on 8 GPUs: one item per rank;
+    # DESIGN.md 5.2).  One process: forward, loss, backward and the optimizer are the graph.  Several ranks (the model prepared by
+    # train_ops.prepare_ranks, not wrapped in DistributedDataParallel, whose bucketed all-reduce is not captured): the graph ends with the
+    # backward and ONE launch that packs the gradients into a flat buffer (train_ops.GradExchange); one all-reduce and the optimizer
+    # follow every replay eagerly.  A DistributedDataParallel model keeps the eager loop.
     graphed = model.__dict__.setdefault("_avt_graphed_steps", {})  # (kept on the model: train() is called once per epoch)
     if graphed.get("optimizer") is not optimizer:
         graphed.clear()
         graphed["optimizer"] = optimizer
-    use_graph = bool(getattr(args, "train_graph", 0)) and not (torch.distributed.is_available() and torch.distributed.is_initialized()
-                                                               and torch.distributed.get_world_size() > 1)
+    dist_on = torch.distributed.is_available() and torch.distributed.is_initialized()
+    world = torch.distributed.get_world_size() if dist_on else 1
+    ddp = isinstance(model, torch.nn.parallel.DistributedDataParallel)
+    # (a model that train_ops.prepare_ranks prepared takes the ranks form under a ONE-rank process group too:
+    #  tools/probe_train_graph_ranks.py times it on one GPU; main() prepares a model only at world > 1)
+    ranks = bool(getattr(args, "train_graph", 0)) and dist_on and not ddp and (world > 1 or train_ops.prepared_for_ranks(model))
+    use_graph = bool(getattr(args, "train_graph", 0)) and (world == 1 or ranks)
+    if ranks and "exchange" not in graphed:
+        graphed["exchange"] = train_ops.GradExchange(model.parameters(), world)
     end = time.time()
     for i, batch_data in enumerate(train_loader):
         q_frames, q_audio_wav, q_audio_eg, t_frames, t_audio_wav, t_audio_eg = batch_data
@@ -58,7 +68,10 @@ def train(train_loader, model, optimizer, args, epoch, tb_logger=None):
                     tf = static[max(nq, 1) : max(nq, 1) + nt] if nt else static[max(nq, 1)]
                     return _eager_step(model, optimizer, criterion, args, qf, tf, static[-2], static[-1], batch_size)
 
-                if isinstance(optimizer, train_ops.ArenaSGD):
+                if ranks:
+                    ent = graphed[key] = (static, _graphed_ranks_step(model, optimizer, criterion, args, static, nq, nt, batch_size,
+                                                                      graphed["exchange"]))
+                elif isinstance(optimizer, train_ops.ArenaSGD):
                     # the warm-up steps train on this batch; put the state back afterwards, so that the first replay is the ONE step the
                     # batch takes (as in the eager loop and the reference).  The capture must start from stale weight planes — their
                     # re-make launch is then part of the graph and every replay splits the weights it finds — which the step hook of the
@@ -77,9 +90,13 @@ def train(train_loader, model, optimizer, args, epoch, tb_logger=None):
             else:
                 for dst, src in zip(ent[0], flat):
                     dst.copy_(src, non_blocking=True)
-            if hasattr(optimizer, "sync_hyper"):
-                optimizer.sync_hyper()  # (the replay reads the learning rate from device memory: what the scheduler set since the last one)
-            loss = ent[1]()
+            if ranks:
+                loss = ent[1]()  # (the rank's own loss, as under DistributedDataParallel)
+                _exchange_and_step(optimizer, graphed["exchange"])
+            else:
+                if hasattr(optimizer, "sync_hyper"):
+                    optimizer.sync_hyper()  # (the replay reads the learning rate from device memory: what the scheduler set since the last one)
+                loss = ent[1]()
             losses.update(loss.item(), batch_size)
         else:
             loss = _eager_step(model, optimizer, criterion, args, q_frames, t_frames, q_audio_eg, t_audio_eg, batch_size)
@@ -121,8 +138,57 @@ def _restore(saved):
         torch._foreach_copy_([t.detach() for t, _ in saved], [c for _, c in saved])
 
 
-def _eager_step(model, optimizer, criterion, args, q_frames, t_frames, q_audio_eg, t_audio_eg, batch_size):
-    """One optimizer step of train(): forward (train.py:114-116), InfoNCE + CE, backward, step -> the loss tensor."""
+def _stateless(optimizer):
+    """The parameters the optimizer keeps no state for yet (torch's SGD creates its momentum buffers at the first step)."""
+    return [p for g in optimizer.param_groups for p in g["params"] if p not in optimizer.state or not optimizer.state[p]]
+
+
+def _exchange_and_step(optimizer, exchange):
+    """The eager rest of a step across ranks: one all-reduce of the packed gradients, the optimizer on their views, stale weight planes."""
+    exchange.all_reduce()
+    exchange.install()
+    if hasattr(optimizer, "sync_hyper"):
+        optimizer.sync_hyper()
+    optimizer.step()
+    train_ops.invalidate_weight_cache()  # (optimizers that update through .data do not bump Tensor._version)
+
+
+def _graphed_ranks_step(model, optimizer, criterion, args, static, nq, nt, batch_size, exchange):
+    """The captured part of a step across ranks for one batch shape -> train_ops.GraphedStep: stale weight planes, zero_grad, forward,
+    loss, backward, and the pack of the gradients as the last launch.  Every rank meets a new shape at the same iteration
+    (DistributedSampler + drop_last), so the collectives of the warm-up steps match."""
+
+    def device_step():
+        # the optimizer runs OUTSIDE this function: whatever ran since the last call, the weight planes are re-made here — and that
+        # launch is part of the capture (a capture that found the cache current would replay convolutions on old planes)
+        train_ops.invalidate_weight_cache()
+        qf = static[:nq] if nq else static[0]
+        tf = static[max(nq, 1) : max(nq, 1) + nt] if nt else static[max(nq, 1)]
+        loss = _forward_backward(model, optimizer, criterion, args, qf, tf, static[-2], static[-1], batch_size)
+        if not exchange.bound:
+            exchange.bind()  # (the first backward of the run: which parameters have gradients; one small collective)
+        exchange.pack()
+        return loss.detach()
+
+    # the warm-up steps are whole steps on this batch, exchange and optimizer included; the state goes back afterwards — with either
+    # optimizer — so that the first replay is the ONE step the batch takes.  State the optimizer did not have yet (torch's SGD creates
+    # its momentum buffers at the first step) is restored as absent
+    saved, absent = _snapshot(model, optimizer), _stateless(optimizer)
+
+    def stale_planes():
+        assert train_ops.weight_cache_is_stale(), "the capture would start from current weight planes: no re-make in the graph"
+
+    step = train_ops.GraphedStep(device_step, static[0].device, warmup=2, before_capture=stale_planes,
+                                 after_warmup=lambda: _exchange_and_step(optimizer, exchange))
+    _restore(saved)
+    for p in absent:
+        optimizer.state.pop(p, None)
+    train_ops.invalidate_weight_cache()
+    return step
+
+
+def _forward_backward(model, optimizer, criterion, args, q_frames, t_frames, q_audio_eg, t_audio_eg, batch_size):
+    """zero_grad, forward (train.py:114-116), InfoNCE + CE, backward -> the loss tensor (with its graph freed)."""
     groups = getattr(args, "bn_replicas", 1)
     groups = batch_size if groups < 0 else groups
     if groups > 1 and batch_size % groups:  # (a short last batch: say so instead of changing the BatchNorm semantics silently)
@@ -137,6 +203,12 @@ def _eager_step(model, optimizer, criterion, args, q_frames, t_frames, q_audio_e
     loss = criterion(output, labels).mean()
     optimizer.zero_grad()
     loss.backward()
+    return loss
+
+
+def _eager_step(model, optimizer, criterion, args, q_frames, t_frames, q_audio_eg, t_audio_eg, batch_size):
+    """One optimizer step of train(): forward, loss, backward, step -> the loss tensor."""
+    loss = _forward_backward(model, optimizer, criterion, args, q_frames, t_frames, q_audio_eg, t_audio_eg, batch_size)
     optimizer.step()
     train_ops.invalidate_weight_cache()  # (optimizers that update through .data do not bump Tensor._version)
     return loss.detach()

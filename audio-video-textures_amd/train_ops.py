@@ -85,7 +85,7 @@ except ImportError:  # (torch < 2.0: callers invalidate by hand, as train() alwa
 # per-process launch counters of the hand-written training kernels (tests assert that the default path really runs them)
 CALLS = {"conv_fwd_x3": 0, "dgrad_x3": 0, "dgrad_strided_x3": 0, "wgrad_x3": 0, "wgrad_stem_x3": 0, "bn_fwd": 0, "bn_bwd": 0,
          "miopen_dgrad": 0, "miopen_wgrad": 0, "stem_fwd_patch": 0, "wgrad_stem_patch": 0, "maxpool_hip": 0, "pw_f32": 0,
-         "bn_fwd_pre": 0, "bn_bwd_pre": 0, "dgrad_bwdstats": 0, "planes_multi": 0, "maxpool3d_hip": 0, "sgd_multi": 0}
+         "bn_fwd_pre": 0, "bn_bwd_pre": 0, "dgrad_bwdstats": 0, "planes_multi": 0, "maxpool3d_hip": 0, "sgd_multi": 0, "grad_pack_multi": 0}
 
 
 def _p(t):
@@ -385,8 +385,11 @@ class GraphedStep:
     graph and returns the same (graph-owned) result tensor.  Inputs must be STATIC tensors that step_fn closes over (fill them with
     copy_ before each call); anything the host decides inside step_fn (branches, cache lookups, shapes) is frozen at capture."""
 
-    def __init__(self, step_fn, device, warmup=3, before_capture=None):
+    def __init__(self, step_fn, device, warmup=3, before_capture=None, after_warmup=None):
         self.graph, self.out = None, None
+        # after_warmup: the eager rest of a step whose capture ends early (train() across ranks: exchange + optimizer), run after every
+        # warm-up call of step_fn on that call's stream, never captured
+        after = after_warmup if after_warmup is not None else (lambda: None)
         # warm-up and capture run on ONE stream of this object: the step's side streams are chosen per step stream
         # (models._side_stream), and a capture stream that differs from the warm-up's was handed the fast pathway's side stream for
         # its query encoder — two of the graph's three branches on one stream: 65 ms per one-item step instead of 52
@@ -398,12 +401,14 @@ class GraphedStep:
         # hardware queues
         for _ in range(max(warmup - 1, 0)):
             step_fn()
+            after()
         torch.cuda.synchronize(device)
         self.stream = torch.cuda.Stream(device=device)
         self.stream.wait_stream(torch.cuda.current_stream(device))
         with torch.cuda.stream(self.stream):
             if warmup > 0:
                 step_fn()
+                after()
         torch.cuda.current_stream(device).wait_stream(self.stream)
         torch.cuda.synchronize(device)
         if before_capture is not None:  # (the caller's checks of the state the capture starts from: train() with an ArenaSGD)
@@ -604,6 +609,216 @@ class ArenaSGD(torch.optim.Optimizer):
         ops.sgd_multi(tab["jobs"], tab["blk2job"], tab["blocks"], self._hyper_dev)
         CALLS["sgd_multi"] += 1
         return loss
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# The gradient exchange of a step that every rank replays as a HIP graph (train.train() at world > 1 with --train_graph 1).
+# DistributedDataParallel's bucketed all-reduce is not capturable as it stands, and its hooks issue from the host.  Here the capture
+# ends with ONE launch (csrc/grad_pack.hip) that copies every gradient, times 1 / world, into one flat buffer; the ranks all-reduce
+# that buffer OUTSIDE the graph and the optimizer — any optimizer — steps on views of it.
+def exchange_layout(numels):
+    """-> (offsets, total) in floats: tensor k of `numels` starts at a multiple of 4 floats (16 bytes, as _GradArena.take slices),
+    total = sum of ceil4(numel)."""
+    offsets, total = [], 0
+    for n in numels:
+        offsets.append(total)
+        total += (int(n) + 3) // 4 * 4
+    return offsets, total
+
+
+def pack_grad_jobs(recs):
+    """recs: (src, dst, numel) per gradient — addresses as ints -> (AvtPackJob table as bytes, blk2job int32 array, blocks): job n
+    owns ceil(numel / 4096) consecutive blocks from its blk0 (include/avt.h).  The twin of pack_sgd_jobs."""
+    import struct
+
+    raw, blk, b0 = [], [], 0
+    for n, (src, dst, numel) in enumerate(recs):
+        nb = (int(numel) + _SGD_CHUNK - 1) // _SGD_CHUNK
+        raw.append(struct.pack("<2Qq2i", src, dst, int(numel), b0, 0))
+        blk.append(np.full(nb, n, dtype=np.int32))
+        b0 += nb
+    return b"".join(raw), (np.concatenate(blk) if blk else np.zeros(0, np.int32)), b0
+
+
+class GradExchange:
+    """The mean gradient over `world` ranks through ONE flat fp32 buffer:
+
+        ex = GradExchange(model.parameters(), world)
+        loss.backward(); ex.bind()        # once, after the first backward: which parameters have gradients
+        ex.pack()                         # one launch: flat views = grad * (1 / world)   — capturable, the graph's last node
+        ex.all_reduce(); ex.install()     # eager: one all-reduce (sum), then p.grad = the parameter's view of the buffer
+        optimizer.step()
+
+    `flat` holds parameter k at exchange_layout's offset, through a view with the PARAMETER's strides (a channels-last weight's view is
+    an as_strided one: the same memory order as its gradient, so the pack is a flat copy); the padding between tensors stays zero.
+    `scale` is a device tensor the kernel loads: a replay follows what the host last wrote there."""
+
+    def __init__(self, params, world, group=None):
+        self.candidates = [p for p in params if p.requires_grad]
+        if not self.candidates:
+            raise _lib.AvtError("GradExchange: no parameter requires a gradient")
+        self.world, self.group = int(world), group
+        if self.world < 1:
+            raise _lib.AvtError("GradExchange: world must be >= 1, got %d" % self.world)
+        self.params, self.views, self.flat, self.offsets, self.total = None, None, None, None, 0
+        self.scale = torch.full((1,), 1.0 / self.world, dtype=torch.float32, device=self.candidates[0].device)
+        self._table = None     # {"key", "jobs", "blk2job", "blocks", "captured", "keep"} of the last launch
+        self._captured = []    # tables a stream capture launched with: alive as long as the graphs that replay them may be
+        self._spare = None     # pinned staging buffer for the table of the next captured pack()
+
+    @property
+    def bound(self):
+        return self.params is not None
+
+    def bind(self):
+        """After the first backward: the exchanged set is the parameters whose .grad is not None, in the order given.  Allocates the
+        flat buffer and the views, and checks ONCE that every rank exchanges the same number of tensors and floats."""
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.AvtError("GradExchange.bind() under stream capture: bind after the first eager backward")
+        params = [p for p in self.candidates if p.grad is not None and p.numel() > 0]
+        if not params:
+            raise _lib.AvtError("GradExchange.bind(): no parameter has a gradient (call it after backward)")
+        for p in params:
+            ArenaSGD._check_param(p)
+        offsets, total = exchange_layout([p.numel() for p in params])
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1:
+            # (MAX of (x, -x): the largest and the smallest of both figures in one collective; host integers under gloo)
+            host = dist.get_backend(self.group) == "gloo"
+            t = torch.tensor([len(params), total, -len(params), -total], dtype=torch.int64, device="cpu" if host else params[0].device)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
+            hi_n, hi_t, lo_n, lo_t = (int(v) for v in t.cpu())
+            if hi_n != -lo_n or hi_t != -lo_t:
+                raise _lib.AvtError("GradExchange.bind(): the ranks do not exchange the same gradients: %d..%d tensors, %d..%d floats "
+                                    "(this rank: %d, %d)" % (-lo_n, hi_n, -lo_t, hi_t, len(params), total))
+        self.flat = torch.zeros(max(total, 4), dtype=torch.float32, device=params[0].device)
+        self.views = [torch.as_strided(self.flat, tuple(p.shape), tuple(p.stride()), o) for p, o in zip(params, offsets)]
+        self.params, self.offsets, self.total = params, offsets, total
+        self._set_aside()
+
+    def _set_aside(self):
+        """A pinned buffer for the job table, allocated outside any capture: what a captured pack() stages its table in."""
+        if self._spare is None:
+            nbytes = 32 * len(self.params) + 4 * sum((p.numel() + _SGD_CHUNK - 1) // _SGD_CHUNK for p in self.params)
+            self._spare = torch.empty(max(nbytes, 8), dtype=torch.uint8, pin_memory=True)
+
+    def _build_table(self, key, capturing):
+        from . import ops
+        raw, blk, blocks = pack_grad_jobs(key)
+        assert len(raw) == len(key) * ops.pack_job_bytes(), "AvtPackJob layout"
+        data = torch.from_numpy(np.frombuffer(raw + blk.tobytes(), dtype=np.uint8).copy())  # jobs and blk2job: one buffer, one copy
+        dev = torch.empty(data.numel(), dtype=torch.uint8, device=self.flat.device)
+        if capturing:
+            # the gradients of a captured step live in the graph's own pool: the table's copy is a node of the graph, re-reading the
+            # pinned buffer set aside before the capture on every replay (ArenaSGD._build_table: the same mechanism)
+            host, self._spare = self._spare, None
+            if host is None or host.numel() < data.numel():
+                raise _lib.AvtError("GradExchange.pack() under stream capture: no staging buffer is left (two captures in a row: call "
+                                    "pack() outside a capture between them)")
+            host[:data.numel()].copy_(data)
+            ops.sgd_upload(dev, host, data.numel())
+        else:
+            host = data.pin_memory()  # (a new pinned tensor per table: an earlier copy may be in flight)
+            dev.copy_(host, non_blocking=True)
+        tab = {"key": key, "jobs": dev[:len(raw)], "blk2job": dev[len(raw):].view(torch.int32), "blocks": blocks, "captured": capturing,
+               "keep": (host, dev)}
+        self._table = tab
+        return tab
+
+    @torch.no_grad()
+    def pack(self):
+        """views[k] = params[k].grad * scale for every bound parameter, in one launch on the current stream."""
+        from . import ops
+        if not self.bound:
+            raise _lib.AvtError("GradExchange.pack() before bind()")
+        capturing = torch.cuda.is_current_stream_capturing()
+        if not capturing:
+            self._set_aside()
+        # a parameter outside the bound set that gains a gradient later (another batch shape, a plugin encoder's branch) would be stepped
+        # on its local gradient and the ranks would drift apart silently
+        bound = {id(p) for p in self.params}
+        for p in self.candidates:
+            if id(p) not in bound and p.grad is not None and p.numel() > 0:
+                raise _lib.AvtError("GradExchange.pack(): a parameter of shape %s has a gradient now but had none at bind(): it is not "
+                                    "exchanged (the set of trained parameters must not change between steps)" % (tuple(p.shape),))
+        key = []
+        for p, v in zip(self.params, self.views):
+            g = p.grad
+            if g is None:
+                raise _lib.AvtError("GradExchange.pack(): a bound parameter has no gradient in this step (shape %s)" % (tuple(p.shape),))
+            if g.dtype != torch.float32 or g.device != v.device or g.layout != torch.strided or not _same_layout(g, p):
+                raise _lib.AvtError("GradExchange.pack(): a gradient must be an fp32 device tensor with its parameter's strides; got %s %s "
+                                    "strides %s for a parameter with strides %s" % (g.dtype, g.device, tuple(g.stride()), tuple(p.stride())))
+            if g.data_ptr() == v.data_ptr():
+                raise _lib.AvtError("GradExchange.pack(): a gradient still IS its exchange view (the step accumulated into the installed "
+                                    "gradient: zero the gradients with set_to_none=True)")
+            key.append((g.data_ptr(), v.data_ptr(), p.numel()))
+        key = tuple(key)
+        tab = self._table
+        # (a table made under capture is filled by its own graph's replays only: no later launch uses it)
+        if tab is None or tab["key"] != key or tab["captured"]:
+            tab = self._build_table(key, capturing)
+        if capturing and not any(t is tab for t in self._captured):
+            self._captured.append(tab)  # a HIP graph holds this table's address: it outlives every later rebuild
+        ops.grad_pack_multi(tab["jobs"], tab["blk2job"], tab["blocks"], self.scale)
+        CALLS["grad_pack_multi"] += 1
+
+    def all_reduce(self):
+        """The sum over the ranks of the packed buffer, one collective on the current stream (the scale made it the mean)."""
+        import torch.distributed as dist
+        if not self.bound:
+            raise _lib.AvtError("GradExchange.all_reduce() before bind()")
+        if dist.is_available() and dist.is_initialized():
+            dist.all_reduce(self.flat, group=self.group)
+        elif self.world > 1:
+            raise _lib.AvtError("GradExchange.all_reduce(): world %d without an initialised process group" % self.world)
+
+    def install(self):
+        """p.grad = the parameter's view of the exchange buffer: whatever optimizer steps next steps on the mean gradient, and on the
+        same addresses every step (ArenaSGD builds its table once)."""
+        if not self.bound:
+            raise _lib.AvtError("GradExchange.install() before bind()")
+        for p, v in zip(self.params, self.views):
+            p.grad = v
+
+
+def prepared_for_ranks(model):
+    """True for a model that went through prepare_ranks()."""
+    return bool(model.__dict__.get("_avt_prepared_for_ranks", False))
+
+
+def freeze_checkpoint_only_modules(model):
+    """Modules that exist only so reference checkpoints load by key and are never applied — q_a_mlp / t_a_mlp (models.py:267-284)
+    and VGGish's fc stack (vggish.py:45) — take no gradient: nothing waits for or exchanges ~300 M dead parameters."""
+    from .vggish import VGGish
+    for name in ("q_a_mlp", "t_a_mlp"):
+        if hasattr(model, name):
+            getattr(model, name).requires_grad_(False)
+    for name in ("q_a_encoder", "t_a_encoder"):
+        enc = getattr(model, name, None)
+        if isinstance(enc, VGGish) and hasattr(enc, "fc"):
+            enc.fc.requires_grad_(False)
+    return model
+
+
+def prepare_ranks(model, group=None):
+    """A model for train()'s graphed step across ranks, in place of the DistributedDataParallel wrapper: the checkpoint-only modules
+    frozen, then every parameter and buffer broadcast from rank 0 ONCE (afterwards the ranks apply the same all-reduced gradient to the
+    same weights; BatchNorm buffers stay per rank and rank 0 writes the checkpoint).  -> the model itself, unwrapped."""
+    import torch.distributed as dist
+    freeze_checkpoint_only_modules(model)
+    world = 1
+    if dist.is_available() and dist.is_initialized():
+        world = dist.get_world_size(group)
+        src = dist.get_global_rank(group, 0) if group is not None else 0
+        with torch.no_grad():
+            for t in list(model.parameters()) + list(model.buffers()):
+                dist.broadcast(t.data, src=src, group=group)
+    model.__dict__["_avt_prepared_for_ranks"] = True
+    if world == 1 or dist.get_rank(group) == 0:
+        print("prepare_ranks: %d rank(s), %d parameters and %d buffers broadcast from rank 0; gradients through train_ops.GradExchange, "
+              "no DistributedDataParallel wrapper" % (world, len(list(model.parameters())), len(list(model.buffers()))))
+    return model
 
 
 def weight_cache_is_stale():

@@ -751,6 +751,24 @@ int avt_sgd_multi(const void* jobs, const int32_t* blk2job, int nblocks, const f
  * replay: PINNED host memory that stays alive and unchanged as long as the graph. */
 int avt_sgd_upload(void* dst, const void* src_host, int64_t nbytes, void* stream);
 
+/* Every gradient of a training step, scaled, into ONE flat exchange buffer in one launch (csrc/grad_pack.hip; the reference: the gradient
+ * gather of torch.nn.DataParallel, main.py:420) — the last node of a step captured as a HIP graph on every rank; the ranks all-reduce the
+ * buffer outside the graph.  The job-table pattern of avt_sgd_multi: `jobs` a DEVICE array of AvtPackJob (one per gradient), `blk2job` a
+ * DEVICE int32 [nblocks]; job j owns blocks blk0 .. blk0 + ceil(numel / 4096), block b the elements [(b - blk0) * 4096, + 4096) of its
+ * tensor (64-bit offsets).  dst[i] = src[i] * scale[0]: one fp32 multiply; `scale` is DEVICE fp32 [1], a load — a replay follows what the
+ * host last wrote there.  src / dst: fp32, dense, 4-byte aligned (16-byte aligned chunks take 16-byte accesses); nothing outside
+ * [dst, dst + numel) is written.  The table of a step under capture is uploaded by avt_sgd_upload.  avt_pack_job_bytes() =
+ * sizeof(AvtPackJob).  Additive symbols: the ABI version stays 8. */
+typedef struct AvtPackJob {
+  const float* src;
+  float* dst;
+  int64_t numel;
+  int32_t blk0;          /* first block of the job in the launch */
+  int32_t pad;
+} AvtPackJob;
+int avt_pack_job_bytes(void);
+int avt_grad_pack_multi(const void* jobs, const int32_t* blk2job, int nblocks, const float* scale, void* stream);
+
 /* MaxPool3d((1,3,3),(1,2,2),(0,1,1)) of the stems in the training step on fp32 NDHWC rows [bt, h, w, c] (csrc/stem_train.hip;
  * the reference: the third-party SlowFast stem under autograd, train.py:114-141).  fwd: y [bt, ho, wo, c] and `tap`
  * (bt*ho*wo*c/2 bytes: 4 bits per element = which of the 9 taps held the maximum; the first one on ties, a NaN wins — torch's
