@@ -176,6 +176,9 @@ int avt_row_topk(const float* sim, int64_t nq, int64_t nt, int64_t ld,
  * softmax cross-entropy — replaces nn.CrossEntropyLoss on the InfoNCE logits
  *   (train.py:129-135; label 0 = positive).  fwd writes per-row loss and the
  *   softmax; bwd writes dlogits = scale * (prob - onehot(label)).
+ *   label NULL = column 0; loss or prob may be NULL (not both).  A label outside
+ *   [0, c) is checked on the device (the step is graph-captured): that row's loss
+ *   and dlogits are NaN, nothing outside the row is read, prob is as ever.
  * ---------------------------------------------------------------------- */
 int avt_softmax_ce_fwd(const float* logits, int64_t b, int64_t c,
                        const int64_t* label, float* loss, float* prob,

@@ -345,10 +345,20 @@ void avt_oracle_softmax_ce_fwd(const float* logits, int64_t b, int64_t c,
     const float* x = logits + r * c;
     float mx = x[0];
     for (int64_t j = 1; j < c; ++j) mx = x[j] > mx ? x[j] : mx;
-    double se = 0.0;
-    for (int64_t j = 0; j < c; ++j) se += exp((double)x[j] - (double)mx);
-    const int64_t y = label ? label[r] : 0;
-    if (loss) loss[r] = (float)((double)mx + log(se) - (double)x[y]);
+    /* se = 1 + rest, one entry at the maximum left out of rest: log1p keeps a loss that log(1 + rest) would lose.
+     * This IS the kernel's formula (csrc/softmax_ce.hip), so agreement with it does not check the formula: that is
+     * done by tests/loss_classic_refs.py softmax_ce_ref (held to fp64 torch log_softmax by the host test) and by
+     * the torch cross_entropy line of test_softmax_ce. */
+    double rest = 0.0, at_max = 0.0;
+    for (int64_t j = 0; j < c; ++j) {
+      const double d = (double)x[j] - (double)mx;
+      if (d == 0.0) at_max += 1.0;
+      else rest += exp(d);
+    }
+    rest += at_max - 1.0;
+    const double se = 1.0 + rest;
+    const uint64_t y = label ? (uint64_t)label[r] : 0;
+    if (loss) loss[r] = y < (uint64_t)c ? (float)(log1p(rest) - ((double)x[y] - (double)mx)) : NAN;
     if (prob)
       for (int64_t j = 0; j < c; ++j) prob[r * c + j] = (float)(exp((double)x[j] - (double)mx) / se);
   }
@@ -356,8 +366,8 @@ void avt_oracle_softmax_ce_fwd(const float* logits, int64_t b, int64_t c,
 void avt_oracle_softmax_ce_bwd(const float* prob, const int64_t* label,
                                int64_t b, int64_t c, float scale, float* dlogits) {
   for (int64_t r = 0; r < b; ++r) {
-    const int64_t y = label ? label[r] : 0;
+    const uint64_t y = label ? (uint64_t)label[r] : 0;
     for (int64_t j = 0; j < c; ++j)
-      dlogits[r * c + j] = scale * (prob[r * c + j] - (j == y ? 1.0f : 0.0f));
+      dlogits[r * c + j] = y < (uint64_t)c ? scale * (prob[r * c + j] - ((uint64_t)j == y ? 1.0f : 0.0f)) : NAN;
   }
 }
