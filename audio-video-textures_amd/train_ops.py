@@ -22,14 +22,16 @@ Weight planes are cached per tensor and rebuilt when `weight._version` changes (
 in-place op on the parameter).  In-place updates through `.data` (EMA / momentum encoders, `p.data.clamp_()`) do NOT bump
 that counter: call `invalidate_weight_cache()` after them (train.train() does after every optimizer step)."""
 import contextlib
-import ctypes as C
+import struct
 import weakref
+from collections import namedtuple
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, ops
+from .ops import _RAW_STREAM, _p, _stream
 
 # Which passes of the training step run on the hand-written kernels.  Module constants (no environment switches since round 4);
 # `set_conv_mode` (main.py --train_conv) is the user-facing switch, tests set some of these to 0 for the stock-op reference path.
@@ -66,7 +68,8 @@ def invalidate_weight_cache(drop=False):
     _PLANES_GEN[0] += 1
     if drop:
         _PLANES.clear()
-        _PLANE_TABLES.clear()
+        for tabs in _PLANE_JOBS.values():
+            tabs.forget()
     _STEM_IMAGES.clear()
 
 
@@ -86,21 +89,6 @@ except ImportError:  # (torch < 2.0: callers invalidate by hand, as train() alwa
 CALLS = {"conv_fwd_x3": 0, "dgrad_x3": 0, "dgrad_strided_x3": 0, "wgrad_x3": 0, "wgrad_stem_x3": 0, "bn_fwd": 0, "bn_bwd": 0,
          "miopen_dgrad": 0, "miopen_wgrad": 0, "stem_fwd_patch": 0, "wgrad_stem_patch": 0, "maxpool_hip": 0, "pw_f32": 0,
          "bn_fwd_pre": 0, "bn_bwd_pre": 0, "dgrad_bwdstats": 0, "planes_multi": 0, "maxpool3d_hip": 0, "sgd_multi": 0, "grad_pack_multi": 0}
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-_RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)  # the current stream's handle without building a Stream object
-
-
-def _stream():
-    # (one call per launch, ~2900 a step at one item per rank — a host-bound step: the raw getter is ~1.5 us cheaper than
-    #  torch.cuda.current_stream().cuda_stream)
-    if _RAW_STREAM is not None:
-        return C.c_void_p(_RAW_STREAM(torch.cuda.current_device()))
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _rows(x):
@@ -424,24 +412,109 @@ class GraphedStep:
 
 
 # ------------------------------------------------------------------------------------------------------------------------
-# SGD whose hyper-parameters live in device memory (csrc/sgd.hip): the optimizer of a step replayed as a HIP graph.  torch's SGD
-# (fused or multi-tensor) takes the learning rate as a kernel ARGUMENT, which a capture freezes: after scheduler.step() every replay
-# kept applying the first epoch's rate.  Here the rate is a load from `hyper`, which sync_hyper() rewrites outside the graph.
-_SGD_CHUNK = 4096  # elements per block (csrc/sgd.hip kChunk)
+# Device job tables.  A training step has three launches that each cover many tensors (ops.sgd_multi, ops.grad_pack_multi,
+# ops.weight_planes_multi): the kernel reads a device table of jobs and a block -> job map, both built on the host.  One packer
+# (_pack_jobs) and one owner (_JobTable) serve the three, so the rules of a table's lifetime under stream capture are written once.
+_SGD_CHUNK = 4096  # elements per block (csrc/sgd.hip and csrc/grad_pack.hip kChunk)
+_SGD_JOB, _PACK_JOB, _PLANE_JOB = "<3Qq2i", "<2Qq2i", "<5Q12i32i"  # AvtSgdJob, AvtPackJob, AvtPlaneJob (include/avt.h)
 
 
-def pack_sgd_jobs(recs):
-    """recs: (p, g, buf, numel, group) per parameter — addresses as ints, buf 0 without momentum -> (AvtSgdJob table as bytes,
-    blk2job int32 array, blocks): job n owns ceil(numel / 4096) consecutive blocks from its blk0 (include/avt.h)."""
-    import struct
+def _chunks(numel):
+    return (int(numel) + _SGD_CHUNK - 1) // _SGD_CHUNK
 
+
+def _pack_jobs(recs, blocks_of, row):
+    """blocks_of(rec) -> blocks of the job, row(rec, blk0) -> the job's struct as bytes -> (job table as bytes, blk2job int32 array,
+    blocks): job n owns blocks_of(rec) consecutive blocks from its blk0."""
     raw, blk, b0 = [], [], 0
-    for n, (p, g, buf, numel, group) in enumerate(recs):
-        nb = (int(numel) + _SGD_CHUNK - 1) // _SGD_CHUNK
-        raw.append(struct.pack("<3Qq2i", p, g, buf, int(numel), int(group), b0))
+    for n, rec in enumerate(recs):
+        nb = blocks_of(rec)
+        raw.append(row(rec, b0))
         blk.append(np.full(nb, n, dtype=np.int32))
         b0 += nb
     return b"".join(raw), (np.concatenate(blk) if blk else np.zeros(0, np.int32)), b0
+
+
+_Table = namedtuple("_Table", "key jobs blk2job blocks captured keep")  # jobs, blk2job: views of ONE uploaded device buffer
+
+
+class _JobTable:
+    """The device job table of one multi-tensor launch and what keeps it valid:
+
+    * `table`: the table of the last launch.  get() reuses it while the key (the tuple of addresses) is unchanged — the same tensors
+      at the same addresses every step: built once — and it was not built under capture: such a table is filled by its own graph's
+      replays only, so no later launch uses it.
+    * `kept`: every table a stream capture launched with.  A HIP graph holds its address: it outlives every later rebuild.
+    * the spare pinned buffer: a table built under capture is uploaded by a copy that is a node of the graph and re-reads its pinned
+      source on every replay.  No pinned allocation inside a capture, so reserve() sets the buffer aside before one.
+
+    capture_builds: what a capture does with a key it does not know.  True (the optimizer and the gradient pack: a captured step's
+    gradients live in the graph's own pool, their addresses are not known before the capture): build, staged in the spare buffer.
+    False (the weight planes: the weights do not move, the warm-up has built the table): get() -> None and the caller does without
+    the launch."""
+
+    def __init__(self, who, fmt, sizeof, remedy=None, capture_builds=True):
+        # who, remedy: the caller and the calls that reserve for it, for the refusal's text; sizeof(): the library's view of fmt
+        self.who, self.fmt, self.sizeof, self.remedy, self.capture_builds = who, fmt, sizeof, remedy, capture_builds
+        self.table, self.kept, self._spare, self._alive = None, [], None, []
+
+    def reserve(self, blocks):
+        """Outside a capture: a pinned buffer for the largest table the next get() under capture may stage in it.  blocks: the blocks
+        of each of its jobs, as the caller's packer counts them (an iterable, read only when no buffer is held)."""
+        if self._spare is None:
+            blocks = list(blocks)
+            nbytes = struct.calcsize(self.fmt) * len(blocks) + 4 * sum(blocks)
+            self._spare = torch.empty(max(nbytes, 8), dtype=torch.uint8, pin_memory=True)
+
+    def unreserve(self):
+        self._spare = None
+
+    def keep_alive(self, obj):
+        """Something else a captured launch read, kept for as long as the tables (not in `kept`: that lists tables only)."""
+        self._alive.append(obj)
+
+    def forget(self):
+        """The next get() builds anew.  What captures launched with stays."""
+        self.table = None
+
+    def get(self, key, device, pack):
+        """-> the table for `key` on the current stream, uploaded (one copy) when it had to be built: pack() -> (job table as bytes,
+        blk2job, blocks), called for a new table only (the caller's checks of the tensors behind the key belong in it)."""
+        capturing = torch.cuda.is_current_stream_capturing()
+        tab = self.table
+        if tab is None or tab.key != key or tab.captured:
+            if capturing and not self.capture_builds:
+                return None
+            raw, blk, blocks = pack()
+            assert len(raw) == len(key) * self.sizeof() == len(key) * struct.calcsize(self.fmt), "%s: job struct layout" % self.who
+            data = torch.from_numpy(np.frombuffer(raw + blk.tobytes(), dtype=np.uint8).copy())  # jobs and blk2job: one buffer, one copy
+            dev = torch.empty(data.numel(), dtype=torch.uint8, device=device)
+            if capturing:
+                host, self._spare = self._spare, None  # (this table keeps it from now on: its graph re-reads it on every replay)
+                if host is None or host.numel() < data.numel():
+                    raise _lib.AvtError("%s under stream capture: no staging buffer is left (two captures in a row: call %s outside a "
+                                        "capture between them)" % (self.who, self.remedy))
+                host[:data.numel()].copy_(data)
+                ops.sgd_upload(dev, host, data.numel())
+            else:
+                host = data.pin_memory()  # (a new pinned tensor per table: an earlier copy may be in flight)
+                dev.copy_(host, non_blocking=True)
+            # (keep: not the tensors behind the addresses — held, gradients would never return to the allocator and move every step)
+            tab = self.table = _Table(key, dev[:len(raw)], dev[len(raw):].view(torch.int32), blocks, capturing, (host, dev))
+        if capturing and not any(t is tab for t in self.kept):
+            self.kept.append(tab)
+        return tab
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# SGD whose hyper-parameters live in device memory (csrc/sgd.hip): the optimizer of a step replayed as a HIP graph.  torch's SGD
+# (fused or multi-tensor) takes the learning rate as a kernel ARGUMENT, which a capture freezes: after scheduler.step() every replay
+# kept applying the first epoch's rate.  Here the rate is a load from `hyper`, which sync_hyper() rewrites outside the graph.
+def pack_sgd_jobs(recs):
+    """recs: (p, g, buf, numel, group) per parameter — addresses as ints, buf 0 without momentum -> (AvtSgdJob table as bytes,
+    blk2job int32 array, blocks): job n owns ceil(numel / 4096) consecutive blocks from its blk0 (include/avt.h)."""
+    return _pack_jobs(recs, lambda r: _chunks(r[3]),
+                      lambda r, b0: struct.pack(_SGD_JOB, r[0], r[1], r[2], int(r[3]), int(r[4]), b0))
 
 
 def _same_layout(a, b):
@@ -458,9 +531,7 @@ class ArenaSGD(torch.optim.Optimizer):
 
     def __init__(self, params, lr, momentum=0, weight_decay=0, nesterov=False, dampening=0, maximize=False):
         self._hyper_dev, self._hyper_host = None, None
-        self._table = None     # {"key", "jobs", "blk2job", "blocks", "captured", "keep"} of the last launch
-        self._captured = []    # what a stream capture launched with: alive as long as the graphs that replay it may be
-        self._spare = None     # pinned staging buffer for the table of the next captured step
+        self._jobs = _JobTable("ArenaSGD.step()", _SGD_JOB, ops.sgd_job_bytes, remedy="sync_hyper() or step()")
         defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov, maximize=maximize)
         super().__init__(params, defaults)
         self._check_groups()
@@ -503,16 +574,13 @@ class ArenaSGD(torch.optim.Optimizer):
             self._check_param(p)
         if self._hyper_host is not None:  # (after construction: the next sync_hyper() uploads a table with the new group's row)
             self._check_groups()
-            self._captured.append(self._hyper_dev)
-            self._hyper_dev, self._hyper_host, self._spare = None, None, None
+            self._jobs.keep_alive(self._hyper_dev)  # (a captured step may still read it)
+            self._jobs.unreserve()  # (sized for the groups so far)
+            self._hyper_dev, self._hyper_host = None, None
 
-    def _set_aside(self):
-        """A pinned buffer large enough for the table over ALL parameters, allocated outside any capture: what a captured step() stages
-        its table in (_build_table)."""
-        if self._spare is None:
-            ps = [p for g in self.param_groups for p in g["params"]]
-            nbytes = 40 * len(ps) + 4 * sum((p.numel() + _SGD_CHUNK - 1) // _SGD_CHUNK for p in ps)
-            self._spare = torch.empty(max(nbytes, 8), dtype=torch.uint8, pin_memory=True)
+    def _blocks(self):
+        """Per job of the table over ALL parameters: the largest a captured step() may build (what _JobTable.reserve sizes for)."""
+        return (_chunks(p.numel()) for g in self.param_groups for p in g["params"])
 
     def _buffer(self, p):
         buf = self.state[p].get("momentum_buffer")
@@ -533,7 +601,7 @@ class ArenaSGD(torch.optim.Optimizer):
         if torch.cuda.is_current_stream_capturing():
             raise _lib.AvtError("ArenaSGD.sync_hyper() under stream capture: call it before the capture / between replays")
         self._check_groups()
-        self._set_aside()
+        self._jobs.reserve(self._blocks())
         device = self.param_groups[0]["params"][0].device
         host = torch.tensor(vals, dtype=torch.float32).pin_memory()  # (a new pinned tensor per change: an earlier copy may be in flight)
         if self._hyper_dev is None:
@@ -542,40 +610,19 @@ class ArenaSGD(torch.optim.Optimizer):
         self._hyper_host = vals
         return True
 
-    def _build_table(self, key, keep, capturing):
-        from . import ops
+    @staticmethod
+    def _pack(key, keep):
+        """What _JobTable.get packs a NEW table with: the tensors behind the addresses checked first."""
         for p, g, buf in keep:
             if g.dtype != torch.float32 or g.device != p.device or g.layout != torch.strided or not _same_layout(g, p):
                 raise _lib.AvtError("ArenaSGD.step(): a gradient must be an fp32 device tensor with its parameter's strides; got %s %s "
                                     "strides %s for a parameter with strides %s" % (g.dtype, g.device, tuple(g.stride()), tuple(p.stride())))
             if buf is not None and (buf.dtype != torch.float32 or buf.device != p.device or not _same_layout(buf, p)):
                 raise _lib.AvtError("ArenaSGD.step(): a momentum buffer must be an fp32 device tensor with its parameter's strides")
-        raw, blk, blocks = pack_sgd_jobs(key)
-        assert len(raw) == len(key) * ops.sgd_job_bytes(), "AvtSgdJob layout"
-        # jobs and blk2job in one pinned buffer, one copy
-        data = torch.from_numpy(np.frombuffer(raw + blk.tobytes(), dtype=np.uint8).copy())
-        dev = torch.empty(data.numel(), dtype=torch.uint8, device=keep[0][0].device)
-        if capturing:
-            # the gradients of a captured step live in the graph's own pool: their addresses are not known before the capture, so the
-            # table's copy is a node of the graph.  It re-reads `host` on every replay: the pinned buffer set aside before the capture
-            # (no pinned allocation inside one), which this table keeps from now on
-            host, self._spare = self._spare, None
-            if host is None or host.numel() < data.numel():
-                raise _lib.AvtError("ArenaSGD.step() under stream capture: no staging buffer is left (two captures in a row: call "
-                                    "sync_hyper() or step() outside a capture between them)")
-            host[:data.numel()].copy_(data)
-            ops.sgd_upload(dev, host, data.numel())
-        else:
-            host = data.pin_memory()  # (a new pinned tensor per table: an earlier copy may be in flight)
-            dev.copy_(host, non_blocking=True)
-        tab = {"key": key, "jobs": dev[:len(raw)], "blk2job": dev[len(raw):].view(torch.int32), "blocks": blocks, "captured": capturing,
-               "keep": (host, dev)}  # (not the gradients: held, they would never return to the allocator and move every step)
-        self._table = tab
-        return tab
+        return pack_sgd_jobs(key)
 
     @torch.no_grad()
     def step(self, closure=None):
-        from . import ops
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -583,7 +630,7 @@ class ArenaSGD(torch.optim.Optimizer):
         capturing = torch.cuda.is_current_stream_capturing()
         if not capturing:
             self.sync_hyper()  # (while capturing no hyper-parameter is uploaded: the graph reads what the host copies between replays)
-            self._set_aside()
+            self._jobs.reserve(self._blocks())
         elif self._hyper_dev is None:
             raise _lib.AvtError("ArenaSGD.step() under stream capture before any sync_hyper()")
         key, keep = [], []
@@ -599,14 +646,8 @@ class ArenaSGD(torch.optim.Optimizer):
         if not key:
             return loss
         key = tuple(key)
-        tab = self._table
-        # (the same tensors at the same addresses every step: built once.  A table made under capture is filled by its own graph's
-        #  replays only, so no later step launches with it)
-        if tab is None or tab["key"] != key or tab["captured"]:
-            tab = self._build_table(key, keep, capturing)
-        if capturing and not any(t is tab for t in self._captured):
-            self._captured.append(tab)  # a HIP graph holds this table's address: it outlives every later rebuild
-        ops.sgd_multi(tab["jobs"], tab["blk2job"], tab["blocks"], self._hyper_dev)
+        tab = self._jobs.get(key, keep[0][0].device, lambda: self._pack(key, keep))
+        ops.sgd_multi(tab.jobs, tab.blk2job, tab.blocks, self._hyper_dev)
         CALLS["sgd_multi"] += 1
         return loss
 
@@ -628,16 +669,8 @@ def exchange_layout(numels):
 
 def pack_grad_jobs(recs):
     """recs: (src, dst, numel) per gradient — addresses as ints -> (AvtPackJob table as bytes, blk2job int32 array, blocks): job n
-    owns ceil(numel / 4096) consecutive blocks from its blk0 (include/avt.h).  The twin of pack_sgd_jobs."""
-    import struct
-
-    raw, blk, b0 = [], [], 0
-    for n, (src, dst, numel) in enumerate(recs):
-        nb = (int(numel) + _SGD_CHUNK - 1) // _SGD_CHUNK
-        raw.append(struct.pack("<2Qq2i", src, dst, int(numel), b0, 0))
-        blk.append(np.full(nb, n, dtype=np.int32))
-        b0 += nb
-    return b"".join(raw), (np.concatenate(blk) if blk else np.zeros(0, np.int32)), b0
+    owns ceil(numel / 4096) consecutive blocks from its blk0 (include/avt.h)."""
+    return _pack_jobs(recs, lambda r: _chunks(r[2]), lambda r, b0: struct.pack(_PACK_JOB, r[0], r[1], int(r[2]), b0, 0))
 
 
 class GradExchange:
@@ -662,9 +695,7 @@ class GradExchange:
             raise _lib.AvtError("GradExchange: world must be >= 1, got %d" % self.world)
         self.params, self.views, self.flat, self.offsets, self.total = None, None, None, None, 0
         self.scale = torch.full((1,), 1.0 / self.world, dtype=torch.float32, device=self.candidates[0].device)
-        self._table = None     # {"key", "jobs", "blk2job", "blocks", "captured", "keep"} of the last launch
-        self._captured = []    # tables a stream capture launched with: alive as long as the graphs that replay them may be
-        self._spare = None     # pinned staging buffer for the table of the next captured pack()
+        self._jobs = _JobTable("GradExchange.pack()", _PACK_JOB, ops.pack_job_bytes, remedy="pack()")
 
     @property
     def bound(self):
@@ -694,46 +725,15 @@ class GradExchange:
         self.flat = torch.zeros(max(total, 4), dtype=torch.float32, device=params[0].device)
         self.views = [torch.as_strided(self.flat, tuple(p.shape), tuple(p.stride()), o) for p, o in zip(params, offsets)]
         self.params, self.offsets, self.total = params, offsets, total
-        self._set_aside()
-
-    def _set_aside(self):
-        """A pinned buffer for the job table, allocated outside any capture: what a captured pack() stages its table in."""
-        if self._spare is None:
-            nbytes = 32 * len(self.params) + 4 * sum((p.numel() + _SGD_CHUNK - 1) // _SGD_CHUNK for p in self.params)
-            self._spare = torch.empty(max(nbytes, 8), dtype=torch.uint8, pin_memory=True)
-
-    def _build_table(self, key, capturing):
-        from . import ops
-        raw, blk, blocks = pack_grad_jobs(key)
-        assert len(raw) == len(key) * ops.pack_job_bytes(), "AvtPackJob layout"
-        data = torch.from_numpy(np.frombuffer(raw + blk.tobytes(), dtype=np.uint8).copy())  # jobs and blk2job: one buffer, one copy
-        dev = torch.empty(data.numel(), dtype=torch.uint8, device=self.flat.device)
-        if capturing:
-            # the gradients of a captured step live in the graph's own pool: the table's copy is a node of the graph, re-reading the
-            # pinned buffer set aside before the capture on every replay (ArenaSGD._build_table: the same mechanism)
-            host, self._spare = self._spare, None
-            if host is None or host.numel() < data.numel():
-                raise _lib.AvtError("GradExchange.pack() under stream capture: no staging buffer is left (two captures in a row: call "
-                                    "pack() outside a capture between them)")
-            host[:data.numel()].copy_(data)
-            ops.sgd_upload(dev, host, data.numel())
-        else:
-            host = data.pin_memory()  # (a new pinned tensor per table: an earlier copy may be in flight)
-            dev.copy_(host, non_blocking=True)
-        tab = {"key": key, "jobs": dev[:len(raw)], "blk2job": dev[len(raw):].view(torch.int32), "blocks": blocks, "captured": capturing,
-               "keep": (host, dev)}
-        self._table = tab
-        return tab
+        self._jobs.reserve(_chunks(p.numel()) for p in params)  # (outside any capture: what a captured pack() stages its table in)
 
     @torch.no_grad()
     def pack(self):
         """views[k] = params[k].grad * scale for every bound parameter, in one launch on the current stream."""
-        from . import ops
         if not self.bound:
             raise _lib.AvtError("GradExchange.pack() before bind()")
-        capturing = torch.cuda.is_current_stream_capturing()
-        if not capturing:
-            self._set_aside()
+        if not torch.cuda.is_current_stream_capturing():
+            self._jobs.reserve(_chunks(p.numel()) for p in self.params)
         # a parameter outside the bound set that gains a gradient later (another batch shape, a plugin encoder's branch) would be stepped
         # on its local gradient and the ranks would drift apart silently
         bound = {id(p) for p in self.params}
@@ -754,13 +754,8 @@ class GradExchange:
                                     "gradient: zero the gradients with set_to_none=True)")
             key.append((g.data_ptr(), v.data_ptr(), p.numel()))
         key = tuple(key)
-        tab = self._table
-        # (a table made under capture is filled by its own graph's replays only: no later launch uses it)
-        if tab is None or tab["key"] != key or tab["captured"]:
-            tab = self._build_table(key, capturing)
-        if capturing and not any(t is tab for t in self._captured):
-            self._captured.append(tab)  # a HIP graph holds this table's address: it outlives every later rebuild
-        ops.grad_pack_multi(tab["jobs"], tab["blk2job"], tab["blocks"], self.scale)
+        tab = self._jobs.get(key, self.flat.device, lambda: pack_grad_jobs(key))
+        ops.grad_pack_multi(tab.jobs, tab.blk2job, tab.blocks, self.scale)
         CALLS["grad_pack_multi"] += 1
 
     def all_reduce(self):
@@ -953,8 +948,7 @@ class MicroBatchGradients:
 _TABS, _PLANES = {}, {}
 _PLANES_MULTI = 1      # stale planes are re-made by ONE launch over every cached weight (0: one by one, as rounds 3-5 did; tests)
 _PLANES_GEN = [0]      # invalidate_weight_cache() bumps it
-_PLANE_TABLES = {}     # device -> (key, job table, blk2job, blocks) of the last multi-job launch
-_PLANE_TABLES_CAPTURED = []  # tables a stream capture has launched with (kept alive for the graphs that replay them)
+_PLANE_JOBS = {}       # device -> _JobTable of the multi-job launch
 _PLANE_REFRESH = {}    # device -> {"id", "event", "stream", "waited": {stream handle: id}}
 
 
@@ -987,12 +981,18 @@ def _job_transposed(w, owner, hi, lo, cout, taps, cin, sel):
             "sel": tuple(int(v) for v in sel), "keep": (hi, lo)}
 
 
+def pack_plane_jobs(jobs):
+    """jobs: (address of the owner's storage, job dict of _job_rows / _job_transposed) per launch -> (AvtPlaneJob table as bytes,
+    blk2job int32 array, blocks): job n reads its source at the address + "off", has `sel` zero-padded to 32 taps and owns "blocks"
+    consecutive blocks from its blk0 (include/avt.h)."""
+    return _pack_jobs(jobs, lambda r: r[1]["blocks"],
+                      lambda r, b0: struct.pack(_PLANE_JOB, r[0] + r[1]["off"], *r[1]["fields"], b0, 0,
+                                                *r[1]["sel"], *(0,) * (32 - len(r[1]["sel"]))))
+
+
 def _refresh_planes(device):
     """Re-make EVERY stale cached plane set of `device` whose recipe is known, in place, with one launch (ops.weight_planes_multi);
     -> False when there was nothing to do.  Other streams order themselves behind the launch in _plane_lookup (one event)."""
-    import struct
-
-    from . import ops
     todo = []
     for ent in list(_PLANES.values()):
         owner = ent.ref()
@@ -1003,26 +1003,16 @@ def _refresh_planes(device):
             todo.append((ent, owner))
     if not todo:
         return False
-    recs = tuple((owner.data_ptr() + j["off"],) + j["fields"] + j["sel"] for ent, owner in todo for j in ent.jobs)
-    tab = _PLANE_TABLES.get(device)
-    if tab is None or tab[0] != recs:  # (the same weights at the same addresses every step: built once; a HIP graph captures its pointers)
-        if torch.cuda.is_current_stream_capturing():
-            return False  # (a capture whose warm-up did not see this set of weights: no host-to-device copy inside it — one by one, as before)
-        raw, blk, b0 = [], [], 0
-        for n, (ent, owner) in enumerate(todo):
-            for j in ent.jobs:
-                sel = j["sel"] + (0,) * (32 - len(j["sel"]))
-                raw.append(struct.pack("<5Q12i32i", owner.data_ptr() + j["off"], *j["fields"][:4], *j["fields"][4:], b0, 0, *sel))
-                blk.append(np.full(j["blocks"], len(raw) - 1, dtype=np.int32))
-                b0 += j["blocks"]
-        raw = b"".join(raw)
-        assert len(raw) == len(blk) * ops.weight_planes_job_bytes(), "AvtPlaneJob layout"
-        tab = (recs, torch.from_numpy(np.frombuffer(raw, dtype=np.uint8).copy()).to(device), torch.from_numpy(np.concatenate(blk)).to(device), b0)
-        _PLANE_TABLES[device] = tab
-    if torch.cuda.is_current_stream_capturing() and not any(t is tab for t in _PLANE_TABLES_CAPTURED):
-        _PLANE_TABLES_CAPTURED.append(tab)  # a HIP graph holds this table's address: it outlives every later rebuild
+    jobs = [(owner.data_ptr(), j) for ent, owner in todo for j in ent.jobs]
+    tabs = _PLANE_JOBS.get(device)
+    if tabs is None:
+        # capture_builds=False: the weights' addresses do not move, so the warm-up's table serves the capture (and is then kept alive)
+        tabs = _PLANE_JOBS[device] = _JobTable("the weight-plane refresh", _PLANE_JOB, ops.weight_planes_job_bytes, capture_builds=False)
+    tab = tabs.get(tuple((base + j["off"],) + j["fields"] + j["sel"] for base, j in jobs), device, lambda: pack_plane_jobs(jobs))
+    if tab is None:
+        return False  # (a capture whose warm-up did not see this set of weights: no host-to-device copy inside it — one by one, as before)
     with torch.no_grad():
-        ops.weight_planes_multi(tab[1], tab[2], tab[3])
+        ops.weight_planes_multi(tab.jobs, tab.blk2job, tab.blocks)
     for ent, owner in todo:
         ent.version, ent.gen = owner._version, _PLANES_GEN[0]
     cur = torch.cuda.current_stream(device)
@@ -1062,7 +1052,6 @@ def _plane_store(key, owner, value, jobs=None):
 
 
 def _ktab(cin, kernel, h, w, ldi, device):
-    from . import ops
     key = (cin, tuple(kernel), h, w, ldi, str(device))
     tab = _TABS.get(key)
     if tab is None:
@@ -1074,7 +1063,6 @@ def _ktab(cin, kernel, h, w, ldi, device):
 def _weight_planes(weight, transposed):
     """(hi, lo, wscale) planes of a Conv3d weight in the kernel's [Cout, taps * Cin] order, cached until the optimizer
     changes the tensor.  transposed: the dgrad filter W'[ci, co, flipped taps], as bf16 planes."""
-    from . import ops
     from .fused_slowfast import split_planes
     # keyed on the tensor that OWNS the storage: conv2d hands over `conv.weight.unsqueeze(2)`, a fresh view per call, which never
     # hit the cache and left an entry per call behind (ADVICE r4); a view shares its base's version counter
@@ -1131,7 +1119,6 @@ _GROUP_IDX = {}
 
 def _group_factor(cin, cout, kernel, stride, pad, w):
     if _PW_F32 and tuple(kernel) == (1, 1, 1) and tuple(stride) == (1, 1, 1) and tuple(pad) == (0, 0, 0):
-        from . import ops
         if ops.pw_x3_f32_supported(cin, cout):
             return 1  # (a pointwise layer the streaming kernel takes as it is: _conv_x3_rows)
     if not _GROUP or tuple(stride) != (1, 1, 1) or pad[2] != kernel[2] // 2 or kernel[2] % 2 == 0 or cin % 8 or cout % 8:
@@ -1179,7 +1166,6 @@ def _grouped_planes(weight, g, transposed, plane_dtype):
     -> (hi, lo, wscale | None), (kt, kh, kwg), rg.  The grouped rows are a fixed GATHER of the weight's elements: the map of storage
     offsets is built once per (shape, layout, g, direction) by running the assembly on the offsets themselves, and every step is one
     launch (ops.weight_planes_gather_f32) instead of a flip, a cat, an index, a permute and a copy in front of the split."""
-    from . import ops
     key = (id(weight), "group", g, bool(transposed))
     hit = _plane_lookup(key, weight)
     if hit is not None:
@@ -1221,7 +1207,6 @@ def _conv_x3_rows(x, planes, plane_dtype, cin, cout, kernel, stride, pad, add=No
     stats = n > 0: the output feeds a train-mode BatchNorm of n replica groups — the kernel's epilogue leaves its statistics'
     partial sums (ops.conv3d_igemm_x3_f32_stats / ops.pw_x3_f32_stats; recorded in _LAST_STATS)."""
     global _LAST_STATS
-    from . import ops
     b, _, t, h, w = x.shape
     od = [(n + 2 * p - k) // s_ + 1 for n, p, k, s_ in zip((t, h, w), pad, kernel, stride)]
     y = torch.empty((b, cout, od[0], od[1], od[2]), dtype=torch.float32, device=x.device, memory_format=torch.channels_last_3d)
@@ -1302,7 +1287,6 @@ def _tag_stats(y):
 class _ConvX3(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, stride, padding, stats=0, bn_in=None):
-        from . import ops
         cout, cin = weight.shape[0], weight.shape[1]
         kernel = tuple(weight.shape[2:])
         ctx.conf = (stride, padding, kernel, cin, cout)
@@ -1331,7 +1315,6 @@ def _conv_backward(ctx, dy, dalias):
     in the stride-1 kernel's epilogue instead of by a separate pass.  (Weight gradients on a side stream of their own — nothing in the
     backward waits for a dW — were measured three times and not kept: round 5 at 8 items per rank, -4 ... -11 %; round 6 at one item
     per rank, eager 234 -> 227 clips/s, inside the replayed HIP graph 303 -> 280: profiles/r06/train_wgrad_side_stream_ab_not_kept.log)"""
-    from . import ops
     x, weight = ctx.saved_tensors
     stride, padding, kernel, cin, cout = ctx.conf
     dy = dy.contiguous(memory_format=torch.channels_last_3d)
@@ -1341,7 +1324,6 @@ def _conv_backward(ctx, dy, dalias):
 
 def _conv_wgrad(ctx, dy, x, weight, stride, padding, kernel, cin, cout):
     """dW of the convolution (split-plane weight-gradient kernels; MIOpen for the shapes they do not cover)."""
-    from . import ops
     dw = None
     taps = kernel[0] * kernel[1] * kernel[2]
     if (_WGRAD_X3 and cin % 8 == 0 and taps <= 28 and max(x.numel(), dy.numel()) < (1 << 31) - 64 and
@@ -1393,7 +1375,6 @@ def _conv_wgrad(ctx, dy, x, weight, stride, padding, kernel, cin, cout):
 
 
 def _conv_dgrad(ctx, dy, dalias, x, weight, stride, padding, kernel, cin, cout):
-    from . import ops
     dx = None
     if ctx.needs_input_grad[0]:
         if dalias is not None:
@@ -1448,7 +1429,6 @@ def _dgrad_strided(dy, weight, stride, padding, kernel, xshape):
     1 ... 8 taps (seven of the projection's eight are zeros).  There frame i_t of a class is frame 2 i_t + r_t, which is the spatial
     remap over PAIRS of frames (2 h rows) as long as T is even — so odd extents (T = 5 and 3 at W = 20) are computed on a grid
     rounded up to even extents and cropped.  -> dx, or None outside that domain (the caller falls back to MIOpen)."""
-    from . import ops
     from .fused_slowfast import split_planes
     b, cin, t, h, w = xshape
     cout = weight.shape[0]
@@ -1559,7 +1539,6 @@ def _stem_tgroup(cout, t):
 
 
 def stem_patch_ok(x, conv):
-    from . import ops
     if not (_STEM_PATCH and conv.in_channels == 3 and x.dim() == 5 and x.shape[1] == 3):
         return False
     kt = conv.kernel_size[0]
@@ -1574,7 +1553,6 @@ def _stem_weight_image(weight, g):
     """(hi, lo, wscale) of a stem weight [C, 3, kt, 7, 7] in the LDS image order of csrc/stem_conv.hip: pixel-pair taps
     (column tap k -> pair tap (k + 1) // 2, pixel (k + 1) % 2; the first is a structural zero), g output frames as g * C
     channels over kt + g - 1 frame taps, fp16 planes of rows scaled into [2^9, 2^10).  Cached until the tensor changes."""
-    from . import ops
     from .fused_slowfast import split_planes, stem_lds_image
     key = (id(weight), g)
     hit = _STEM_IMAGES.get(key)
@@ -1604,7 +1582,6 @@ def _stem_weight_image(weight, g):
 class _StemX3(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight):
-        from . import ops
         b, _, t, h, w = x.shape
         c, kt = weight.shape[0], weight.shape[2]
         g = _stem_tgroup(c, t)
@@ -1619,7 +1596,6 @@ class _StemX3(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        from . import ops
         x, weight = ctx.saved_tensors
         if not ctx.needs_input_grad[1]:
             return None, None

@@ -27,8 +27,11 @@ def test_library_exports_every_declared_symbol(avt):
 
 def test_plane_job_table_layout_matches_the_header(avt):
     """AvtPlaneJob (include/avt.h) as the three parties see it: the header's fields mirrored in ctypes, the library's own sizeof, and the
-    struct format train_ops._refresh_planes packs its device table with."""
+    struct format train_ops.pack_plane_jobs packs the device table with — and the table's bytes for one job of each kind (rows, transposed
+    with three selected taps, gathered rows; made-up addresses) against the ctypes mirror filled field by field."""
     import struct
+
+    from avtex import train_ops
 
     class AvtPlaneJob(ctypes.Structure):
         _fields_ = ([(n, ctypes.c_void_p) for n in ("w", "hi", "lo", "wscale", "map")] +
@@ -42,6 +45,33 @@ def test_plane_job_table_layout_matches_the_header(avt):
     assert declared == [f[0] for f in AvtPlaneJob._fields_], declared
     assert ctypes.sizeof(AvtPlaneJob) == avt._lib.lib().avt_weight_planes_job_bytes() == struct.calcsize("<5Q12i32i") == 216
     assert AvtPlaneJob.sel.offset == 88 and AvtPlaneJob.blk0.offset == 80
+
+    def fields(ptrs, ints, sel=()):
+        return {"fields": tuple(ptrs) + tuple(ints), "sel": tuple(sel)}
+
+    # (owner's address, job): kind 0 = 24 rows of 72 into fp16 planes with a row scale, one block per row; kind 1 = [cout 40, 9 taps,
+    # cin 48] transposed for taps 8, 4, 0: 2 x 2 tiles of 32 per tap; kind 2 = 16 rows of 40 gathered through an index map
+    jobs = [(0x7F0000001000, dict(fields((0xA000, 0xB000, 0xC000, 0), (0, 1, 24, 72, 0, 0, 0, 0, 0, 0)), off=0, blocks=24)),
+            (0x7F0000001000, dict(fields((0xD000, 0xE000, 0, 0), (1, 0, 0, 0, 40, 9, 48, 3, 2, 2), (8, 4, 0)), off=64, blocks=12)),
+            (0x7F0000200000, dict(fields((0x1A000, 0x1B000, 0, 0x1C000), (2, 0, 16, 40, 0, 0, 0, 0, 0, 0)), off=4096, blocks=16))]
+    raw, blk2job, blocks = train_ops.pack_plane_jobs(jobs)
+    want, blk0 = b"", 0
+    for base, j in jobs:
+        s = AvtPlaneJob()
+        s.w = base + j["off"]
+        s.hi, s.lo, s.wscale, s.map = (v or None for v in j["fields"][:4])
+        (s.kind, s.f16, s.rows, s.k, s.cout, s.taps, s.cin, s.nsel, s.gx, s.gy) = j["fields"][4:]
+        s.blk0, s.pad_ = blk0, 0
+        for i, v in enumerate(j["sel"]):
+            s.sel[i] = v  # (the other taps stay zero)
+        want += bytes(s)
+        blk0 += j["blocks"]
+    assert raw == want and len(raw) == 3 * 216
+    assert [AvtPlaneJob.from_buffer_copy(raw, 216 * n).blk0 for n in range(3)] == [0, 24, 36]
+    assert list(AvtPlaneJob.from_buffer_copy(raw, 216).sel) == [8, 4, 0] + [0] * 29
+    assert blocks == 52 and blk2job.dtype == np.int32 and blk2job.tolist() == [0] * 24 + [1] * 12 + [2] * 16
+    raw0, blk0_, blocks0 = train_ops.pack_plane_jobs([])
+    assert raw0 == b"" and blocks0 == 0 and blk2job.dtype == blk0_.dtype and blk0_.shape == (0,)
 
 
 def test_no_torch_types_in_header(avt):

@@ -320,3 +320,104 @@ def test_replay_follows_the_rate():
     # what this guards: torch's SGD under the same replay still applies the rate it was captured with
     _, _, _, frozen_torch = run(True, lambda ps: torch.optim.SGD(ps, lr=0.05, momentum=0.9))
     assert not frozen_torch
+
+
+def test_table_lifetime_across_a_capture(avt, dev):
+    """The job table of ArenaSGD.step() (train_ops._JobTable, shared with GradExchange and the weight-plane refresh): built once while the
+    addresses stand, built under the capture when the gradients moved (its upload a node of the graph: the replays follow gradient VALUES
+    written in place), never launched eagerly afterwards and kept alive.  Every update against torch.optim.SGD on an fp64 CPU copy and
+    torch's fp32 step from the same gradients: the bound of the one-step tests (_errs).  A second capture in a row finds no staging
+    buffer and is refused on the host, before any launch."""
+    from avtex import train_ops
+
+    kw = dict(lr=0.05, momentum=0.9)
+    shapes = [(1,), (4097,), (8, 8, 1, 3, 3)]  # one element; one chunk and one element; a channels-last weight
+
+    def tensor(shape, seed, scale=1.0):
+        t = _rand(int(np.prod(shape)), seed, scale).view(shape)
+        return t.contiguous(memory_format=torch.channels_last_3d) if len(shape) == 5 else t
+
+    p0 = [tensor(s, 1 + i) for i, s in enumerate(shapes)]
+    ph, pt = [torch.nn.Parameter(p.to(dev)) for p in p0], [torch.nn.Parameter(p.to(dev)) for p in p0]
+    p64 = [torch.nn.Parameter(p.double()) for p in p0]
+    assert not ph[2].is_contiguous() and ph[2].is_contiguous(memory_format=torch.channels_last_3d)
+    oh, ot, o64 = train_ops.ArenaSGD(ph, **kw), torch.optim.SGD(pt, **kw), torch.optim.SGD(p64, **kw)
+    for p in ph + pt:
+        p.grad = torch.zeros_like(p)
+    for p in p64:
+        p.grad = torch.zeros_like(p)
+    seed = [100]
+
+    def new_gradients():
+        for i, s in enumerate(shapes):
+            g = tensor(s, seed[0] + i, 0.1)
+            with torch.no_grad():
+                ph[i].grad.copy_(g.to(dev))  # in place: the addresses stand
+                pt[i].grad.copy_(g.to(dev))
+                p64[i].grad.copy_(g.double())
+        seed[0] += 10
+
+    def move_gradients():
+        for p in ph:
+            p.grad = p.grad.clone(memory_format=torch.preserve_format)  # (the old tensor is alive during the clone: a new address)
+
+    def check(what):
+        ot.step()
+        o64.step()
+        torch.cuda.synchronize()
+        for i, s in enumerate(shapes):
+            _errs("%s, shape %s, p" % (what, s), ph[i], pt[i], p64[i].detach())
+            _errs("%s, shape %s, buf" % (what, s), oh.state[ph[i]]["momentum_buffer"], ot.state[pt[i]]["momentum_buffer"],
+                  o64.state[p64[i]]["momentum_buffer"])
+
+    before = train_ops.CALLS["sgd_multi"]
+    new_gradients()
+    oh.step()
+    check("eager step 1")
+    tab = oh._jobs.table
+    new_gradients()
+    oh.step()
+    check("eager step 2")
+    assert oh._jobs.table is tab and not tab.captured and train_ops.CALLS["sgd_multi"] - before == 2
+    # gradients at NEW addresses, as the backward of a captured step leaves them: the table is built under the capture
+    move_gradients()
+    torch.cuda.synchronize()
+    stream = torch.cuda.Stream(device=dev)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=stream):
+        oh.step()
+    assert oh._jobs.table is not tab and oh._jobs.table.captured and train_ops.CALLS["sgd_multi"] - before == 3
+    for k in range(3):
+        new_gradients()
+        graph.replay()
+        check("replay %d" % (k + 1))
+    assert train_ops.CALLS["sgd_multi"] - before == 3  # replays do not pass the host
+    new_gradients()
+    oh.step()  # an eager step after the capture builds a table of its own and leaves the captured one alone
+    check("eager step after the capture")
+    assert not oh._jobs.table.captured and len(oh._jobs.kept) == 1
+
+
+def test_a_second_capture_in_a_row_is_refused(avt, dev):
+    """The staging buffer of a captured table is set aside by an eager step() / sync_hyper(); a capture used it up.  A second capture with
+    the gradients moved again, and nothing eager between, has none: AvtError on the host, before any launch."""
+    from avtex import train_ops
+
+    p = torch.nn.Parameter(torch.zeros(4097, device=dev))
+    opt = train_ops.ArenaSGD([p], lr=0.05, momentum=0.9)
+    p.grad = torch.ones_like(p)
+    mark = torch.zeros(1, device=dev)
+    torch.cuda.synchronize()
+    stream = torch.cuda.Stream(device=dev)
+    first = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(first, stream=stream):
+        opt.step()
+    assert opt._jobs.table.captured
+    p.grad = p.grad.clone()
+    before = train_ops.CALLS["sgd_multi"]
+    second = torch.cuda.CUDAGraph()
+    with pytest.raises(avt._lib.AvtError, match=r"ArenaSGD\.step\(\) under stream capture: no staging buffer is left .*sync_hyper\(\) or step\(\)"):
+        with torch.cuda.graph(second, stream=stream):
+            mark.add_(1)  # (so that the abandoned graph is not an empty one)
+            opt.step()
+    assert train_ops.CALLS["sgd_multi"] == before

@@ -64,15 +64,15 @@ def test_pack_equals_torch_scale_and_stays_in_bounds(avt, dev, world):
     before = train_ops.CALLS["grad_pack_multi"]
     ex.pack()
     _check(ex, params, canary)
-    tab = ex._table
+    tab = ex._jobs.table
     ex.pack()  # the same addresses: the table is built once
-    assert ex._table is tab and train_ops.CALLS["grad_pack_multi"] - before == 2
+    assert ex._jobs.table is tab and train_ops.CALLS["grad_pack_multi"] - before == 2
     _check(ex, params, canary)
     # new gradient tensors: a new table, the same result
     for p in params:
         p.grad = (p.grad * 3 + 1).clone(memory_format=torch.preserve_format)
     ex.pack()
-    assert ex._table is not tab
+    assert ex._jobs.table is not tab
     _check(ex, params, canary)
     # install(): the parameters' gradients ARE the views from then on; packing them onto themselves is refused
     ex.install()
@@ -102,7 +102,7 @@ def test_captured_pack_follows_the_values_and_the_scale(avt, dev):
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph, stream=stream):
         ex.pack()
-    assert train_ops.CALLS["grad_pack_multi"] - before == 1 and ex._table["captured"]
+    assert train_ops.CALLS["grad_pack_multi"] - before == 1 and ex._jobs.table.captured
     for scale, shift in ((0.5, 0.0), (1.0 / 3.0, 2.0), (0.5, -1.0)):
         with torch.no_grad():
             for p in params:
@@ -113,7 +113,7 @@ def test_captured_pack_follows_the_values_and_the_scale(avt, dev):
         _check(ex, params, canary)
     assert train_ops.CALLS["grad_pack_multi"] - before == 1  # replays do not pass the host
     ex.pack()  # an eager launch after the capture builds a table of its own and leaves the captured one alone
-    assert not ex._table["captured"] and len(ex._captured) == 1
+    assert not ex._jobs.table.captured and len(ex._jobs.kept) == 1
     _check(ex, params, canary)
 
 
