@@ -87,6 +87,9 @@ SIGNATURES = {
     "avt_upsample2_bilinear_x3": [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp],
     "avt_interp_mid_input": [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp],
     "avt_interp_final_u8": [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _f32p, _vp, C.c_int, _vp],
+    "avt_resize_u8_ksize": [C.c_int] * 3,
+    "avt_resize_u8_tables": [C.c_int] * 4 + [_vp, _vp],
+    "avt_resize_u8": [_vp, _vp, _vp] + [C.c_int] * 6 + [_vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp],
     "avt_negative_sample_mt19937": [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp],
     "avt_clip_pack_gather_u8": [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                 C.c_int, _vp, _vp, C.c_int, _vp],

@@ -1168,3 +1168,55 @@ def interp_final(img, ft, o_ptrs, h, w, sf, mean, out, plane_dtype):
     _dev(out, "out", torch.uint8)
     _lib.check(_lib.lib().avt_interp_final_u8(_p(img), _p(ft), C.c_void_p(o_ptrs[0]), C.c_void_p(o_ptrs[1]), int(h), int(w), int(sf),
                                               _mean3(mean), _p(out), int(plane_dtype), _stream()), "avt_interp_final_u8")
+
+
+# ---------------------------------------------------------------- Pillow's 8-bit resize on the device (csrc/resize_u8.hip)
+RESIZE_BILINEAR, RESIZE_LANCZOS = 0, 1
+_RESIZE_FILTERS = {"bilinear": RESIZE_BILINEAR, "lanczos": RESIZE_LANCZOS}
+_RESIZE_TABS = {}
+
+
+def resize_u8_tables(in_size, out_size, filt):
+    """Host tables of one axis of Pillow's 8-bit resampler: (k int32 [out, ksize], bounds int32 [out, 2] = (first tap, taps))."""
+    ksize = _lib.lib().avt_resize_u8_ksize(int(in_size), int(out_size), int(filt))
+    if ksize < 0:  # (a status, not a tap count)
+        _lib.check(ksize, "avt_resize_u8_ksize")
+    k, bounds = np.empty((int(out_size), ksize), np.int32), np.empty((int(out_size), 2), np.int32)
+    _lib.check(_lib.lib().avt_resize_u8_tables(int(in_size), int(out_size), int(filt), ksize, k.ctypes.data, bounds.ctypes.data),
+               "avt_resize_u8_tables")
+    return k, bounds
+
+
+def _resize_tabs(in_size, out_size, filt, device):
+    key = (int(in_size), int(out_size), int(filt), str(device))
+    tabs = _RESIZE_TABS.get(key)
+    if tabs is None:
+        k, bounds = resize_u8_tables(in_size, out_size, filt)
+        tabs = _RESIZE_TABS[key] = (torch.from_numpy(k).to(device), torch.from_numpy(bounds).to(device), k.shape[1])
+    return tabs
+
+
+def resize_u8(frames, size, filter):
+    """frames uint8 [B, H, W, 3] RGB (device) -> uint8 [B, h, w, 3] with size = (h, w): PIL's Image.resize((w, h), filter) of every
+    frame, bit for bit, filter "lanczos" or "bilinear".  One launch per axis whose extent changes, on the current stream; the
+    coefficient tables are built on the host once per (in, out, filter) and stay on the device."""
+    _dev(frames, "frames", torch.uint8)
+    if frames.dim() != 4:
+        raise _lib.AvtError("resize_u8: frames must be [B, H, W, 3]")
+    if filter not in _RESIZE_FILTERS:
+        raise _lib.AvtError("resize_u8: filter must be 'lanczos' or 'bilinear' (got %r)" % (filter,))
+    filt = _RESIZE_FILTERS[filter]
+    b, h, w, c = (int(v) for v in frames.shape)
+    oh, ow = int(size[0]), int(size[1])
+    kx = bx = ky = by = tmp = None
+    nx = ny = 0
+    if c == 3 and ow != w:
+        kx, bx, nx = _resize_tabs(w, ow, filt, frames.device)
+    if c == 3 and oh != h:
+        ky, by, ny = _resize_tabs(h, oh, filt, frames.device)
+    if nx and ny:
+        tmp = torch.empty((b, h, ow, 3), dtype=torch.uint8, device=frames.device)
+    out = torch.empty((b, max(oh, 0), max(ow, 0), 3), dtype=torch.uint8, device=frames.device)
+    _lib.check(_lib.lib().avt_resize_u8(_p(frames), _p(tmp), _p(out), b, h, w, oh, ow, c, _p(kx), _p(bx), nx, _p(ky), _p(by), ny, _stream()),
+               "avt_resize_u8")
+    return out

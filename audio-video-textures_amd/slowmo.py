@@ -12,7 +12,9 @@ in validate.py:179-185, called at :588-611; `--interpolation` is ON by default, 
     reads, pooling / upsampling as plane-pair passes (csrc/interp.hip).
   * `Interpolator` is `interpolate.forward`: pack the frame pair, flowComp, then ALL `SF - 1` intermediate times as one
     batch through ArbTimeFlowIntrp (the reference loops over them), back-warps / blend / uint8 conversion fused in two
-    passes.  Frames stay on the device from the source video to the output tensor.
+    passes.  Frames stay on the device from the source video to the output tensor, also when their extents are not
+    multiples of 32: PIL's Lanczos resize down to the networks' size and its bilinear resize back up (interpolate.py:43, 137)
+    are `ops.resize_u8` (csrc/resize_u8.hip), equal to Pillow bit for bit.
 """
 import torch
 import torch.nn as nn
@@ -178,15 +180,6 @@ class Interpolator:
         self.flow_comp.load_state_dict(ck["state_dictFC"])
         self._fc = self._at = None
 
-    def _resize(self, frame, size, lanczos):
-        """PIL's resize for frames whose extents are not multiples of 32 (interpolate.py:43, 137): host round trip, as rare
-        as such videos (the networks' size equals the frame's for 128, 224, 256 ...)."""
-        from PIL import Image
-        img = Image.fromarray(frame.cpu().numpy())
-        img = img.resize(size, Image.LANCZOS if lanczos else Image.BILINEAR)  # (ANTIALIAS = LANCZOS before Pillow 10)
-        import numpy as np
-        return torch.from_numpy(np.array(img.convert("RGB"))).to(self.dev)
-
     def __call__(self, frame0, frame1):
         if self._fc is None:
             self._fc, self._at = UNetX3(self.flow_comp, self.dev), UNetX3(self.arb_time, self.dev)
@@ -194,7 +187,8 @@ class Interpolator:
             raise AvtError("Interpolator: frames must be [%d, %d, 3] uint8" % (self.h, self.w))
         h, w, sf, pd = self.nh, self.nw, self.sf, ops.X3_F16
         if (h, w) != (self.h, self.w):
-            frame0, frame1 = self._resize(frame0, (w, h), True), self._resize(frame1, (w, h), True)
+            # interpolate.py:43: PIL's Lanczos resize of both frames to the networks' size, one call (csrc/resize_u8.hip)
+            frame0, frame1 = ops.resize_u8(torch.stack((frame0, frame1)), (h, w), "lanczos")
         frame0, frame1 = frame0.contiguous(), frame1.contiguous()
         img = torch.empty((2, h, w, 4), dtype=torch.float32, device=self.dev)
         x = new_act(h * w, 8, (1, 1, h, w), self.dev, True)
@@ -208,7 +202,7 @@ class Interpolator:
         out = torch.empty((nt, h, w, 3), dtype=torch.uint8, device=self.dev)
         ops.interp_final(img, ft, o.ptrs, h, w, sf, MEAN, out, pd)
         if (h, w) != (self.h, self.w):
-            out = torch.stack([self._resize(f, (self.w, self.h), False) for f in out])
+            out = ops.resize_u8(out, (self.h, self.w), "bilinear")   # interpolate.py:137: PIL's bilinear resize back, all SF - 1 frames
         return out
 
 

@@ -812,6 +812,34 @@ int avt_interp_mid_input(const float* img, const void* flow_hi, const void* flow
 int avt_interp_final_u8(const float* img, const float* ft, const void* o_hi, const void* o_lo, int height, int width,
                         int sf, const float* mean3, uint8_t* out, int plane_dtype, void* stream);
 
+/* Pillow's Image.resize for 8-bit RGB frames on the device, equal to it bit for bit (csrc/resize_u8.hip): the Lanczos resize of
+ * the two frames of a jump down to the networks' size and the bilinear resize of the interpolated frames back up, for frames
+ * whose extents are not multiples of 32 (interpolate.py:43, 137).  Pillow's 8-bit resampler is integer arithmetic over
+ * fixed-point tables: per axis, scale = in / out, fs = max(scale, 1), support = (1 bilinear, 3 Lanczos) * fs,
+ * ksize = 2 * ceil(support) + 1; output i has centre (i + 0.5) * scale, first tap max(int(centre - support + 0.5), 0),
+ * n = min(int(centre + support + 0.5), in) - first taps with weights filter((x + first - centre + 0.5) * (1 / fs)), summed in
+ * order and divided by the sum in double (sin from libm, as Pillow calls it) and rounded to 22 fractional bits (away from zero at .5).  A pass computes
+ * clamp((2^21 + sum_x k[x] * pixel[first + x]) >> 22, 0, 255) in int32; the horizontal pass runs first, into a uint8 intermediate
+ * whose rounding is part of the result, then the vertical one; a pass whose extent does not change is skipped.
+ * avt_resize_u8_ksize (HOST): the tap count ksize of one axis (> 0), or a negative status.
+ * avt_resize_u8_tables (HOST): fills k [out_size, ksize] int32 (zero beyond a row's n taps) and bounds [out_size, 2] int32
+ *   = (first, n) for one axis; `ksize` must be avt_resize_u8_ksize's answer (the size the caller's buffers were made for).
+ * avt_resize_u8: in [batch, in_h, in_w, 3] -> out [batch, out_h, out_w, 3] uint8 on the device, one launch per pass that
+ *   runs (none: one device-to-device copy).  kx / bx (ksize_x) are the tables of (in_w -> out_w), ky / by (ksize_y) those of
+ *   (in_h -> out_h), copied to the device by the caller; the kernels trust them, so they must be avt_resize_u8_tables' output for
+ *   exactly these extents.  The tables of a pass that does not run may be NULL.  tmp: batch * in_h * out_w * 3 bytes, needed
+ *   (and touched) only when both passes run.  Any ksize; frames need no alignment (rows of w * 3 bytes start anywhere), the
+ *   tables 4 bytes.  Domain, everything else is refused with AVT_ERR_ARG: channels == 3; batch >= 1; every extent in 1..2^20;
+ *   batch * max(in_h, out_h) * max(in_w, out_w) * 3 < 2^31 bytes; in, tmp, out distinct.
+ * Additive symbols: the ABI version stays 8. */
+#define AVT_RESIZE_BILINEAR 0
+#define AVT_RESIZE_LANCZOS  1
+int avt_resize_u8_ksize(int in_size, int out_size, int filter);
+int avt_resize_u8_tables(int in_size, int out_size, int filter, int ksize, int32_t* k, int32_t* bounds);
+int avt_resize_u8(const uint8_t* in, uint8_t* tmp, uint8_t* out, int batch, int in_h, int in_w, int out_h, int out_w,
+                  int channels, const int32_t* kx, const int32_t* bx, int ksize_x, const int32_t* ky, const int32_t* by,
+                  int ksize_y, void* stream);
+
 /* D1[i, j] = || x_i - x_j ||_2 of the classic video-texture baseline (baselines/classic_video_textures/
  * computeD1.py:47-96; BASELINE config 1): x [n, d] fp32 device rows (flattened frames), out [n, n] fp32.
  * fp64 accumulation in a fixed order, one sqrt, one rounding. */
