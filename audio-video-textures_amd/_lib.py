@@ -91,6 +91,7 @@ SIGNATURES = {
     "avt_resize_u8_tables": [C.c_int] * 4 + [_vp, _vp],
     "avt_resize_u8": [_vp, _vp, _vp] + [C.c_int] * 6 + [_vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp],
     "avt_negative_sample_mt19937": [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp],
+    "avt_train_batch_plan": [_vp, _vp] + [C.c_int] * 6 + [_vp, _vp, _vp],
     "avt_clip_pack_gather_u8": [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                 C.c_int, _vp, _vp, C.c_int, _vp],
     "avt_frames_resize_aa_norm_u8": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p, _vp, _vp],

@@ -137,22 +137,32 @@ class DeviceSegmentBatcher:
         3D-ResNets) as the fp32 table [F, 3, hw, hw] the dataset keeps on the host — /255, antialiased resize, per-channel
         normalisation — built once by ops.frames_resize_aa_norm (F * 3 * hw^2 * 4 bytes: 361 MB per 600 frames at 224^2),
         after which the uint8 copy is dropped;
-      * negatives are drawn by the device MT19937 kernel from NumPy's own stream (ops.negative_sample: the state of
+      * negatives are drawn by the device MT19937 kernel from NumPy's own stream (ops.train_batch_plan: the state of
         np.random is uploaded once by `seed_from_numpy()` and can be handed back by `sync_to_numpy()`), with the
-        reference's hard-negative overwrite (dataset.py:183-190);
+        reference's hard-negative overwrite (dataset.py:183-190); the same launch writes the window starts;
       * query / positive / negative windows are packed by the gather kernels (ops.clip_pack_gather for SlowFast,
         ops.clip_gather_frames over the table otherwise), starts read on device.
 
     batch(idx) -> (q_frames, t_frames, q_audio_eg, t_audio_eg) with the shapes the DataLoader would deliver:
     SlowFast: q_frames [slow [B,3,8,hw,hw], fast [B,3,32,hw,hw]], t_frames [slow [B,1+negs,3,8,hw,hw], fast [B,1+negs,3,32,hw,hw]];
     otherwise: q_frames [B,W,3,hw,hw], t_frames [B,1+negs,W,3,hw,hw].
-    loader(batch_size) is the form train() iterates."""
+    loader(batch_size) is the form train() iterates.
 
-    def __init__(self, dataset, device, dtype=torch.float32):
+    Several ranks (rank, world): every rank keeps the whole video resident and is handed the GLOBAL batch's item ids; sample(), _pack()
+    and batch() return the rank's share only — item k of a global batch of world * per items belongs to rank k // per, the contiguous
+    scatter of the reference's DataParallel (main.py:420).  The sampling kernel walks the stream over the whole global batch on every
+    rank and materialises the rank's items, so that all ranks hold the same MT19937 state after every step, and a world-N run sees, item
+    for item and bit for bit, the batches of a one-process run at N times the per-rank batch from the same np.random state
+    (`seed_from_numpy()` broadcasts rank 0's)."""
+
+    def __init__(self, dataset, device, dtype=torch.float32, rank=0, world=1):
         from . import ops
 
         if dataset.split != "train":
             raise ValueError("DeviceSegmentBatcher packs training items")
+        if world < 1 or not 0 <= rank < world:
+            raise ValueError("DeviceSegmentBatcher: rank %d is not one of %d" % (rank, world))
+        self.rank, self.world = int(rank), int(world)
         self.slowfast = dataset.enc_arch == "slowfast"
         if not self.slowfast and dtype != torch.float32:
             raise ValueError("DeviceSegmentBatcher: the frame table of %s is float32, not %s" % (dataset.enc_arch, dtype))
@@ -176,9 +186,21 @@ class DeviceSegmentBatcher:
         self._gauss = (0, 0.0)
 
     def seed_from_numpy(self):
+        """Uploads np.random's state.  With several ranks under an initialised process group it is rank 0's state, its cached gaussian
+        included, that every rank uploads (one broadcast of 2.5 KB — a collective: every rank calls this at the same point)."""
         st = np.random.get_state()
-        self._gauss = (int(st[3]), float(st[4]))  # a cached gaussian of the host stream survives the round trip
         words = np.concatenate([np.asarray(st[1], np.uint32), np.array([st[2]], np.uint32)])
+        gauss = (int(st[3]), float(st[4]))  # a cached gaussian of the host stream survives the round trip
+        dist = torch.distributed
+        if self.world > 1 and dist.is_available() and dist.is_initialized():
+            host = dist.get_backend() == "gloo"  # (gloo moves host tensors, RCCL device tensors: as train_ops.GradExchange.bind)
+            msg = np.concatenate([words.astype(np.int64), np.array([gauss[0]], np.int64), np.array([gauss[1]], np.float64).view(np.int64)])
+            t = torch.from_numpy(msg).to("cpu" if host else self.dev)
+            dist.broadcast(t, src=0)
+            msg = t.cpu().numpy()
+            words = msg[:625].astype(np.uint32)
+            gauss = (int(msg[625]), float(msg[626:627].view(np.float64)[0]))
+        self._gauss = gauss
         self.state = torch.from_numpy(words.view(np.int32).copy()).to(self.dev)
         return self
 
@@ -187,24 +209,41 @@ class DeviceSegmentBatcher:
         words = self.state.cpu().numpy().view(np.uint32)
         np.random.set_state(("MT19937", words[:624].copy(), int(words[624]), self._gauss[0], self._gauss[1]))
 
-    def sample(self, idx):
-        """idx int64 [B] -> (positive ids [B], negative ids [B, n_negs]) on the device."""
+    def share(self, idx):
+        """The rank's items of a global batch: ids [world * per] -> ids [rank * per : (rank + 1) * per] (DataParallel's contiguous
+        scatter)."""
+        b = int(idx.numel())
+        if b % self.world:
+            raise ValueError("DeviceSegmentBatcher: a global batch of %d items does not divide over %d ranks" % (b, self.world))
+        per = b // self.world
+        return idx[self.rank * per : (self.rank + 1) * per]
+
+    def _plan(self, idx):
+        """idx int64 [B] (device, the GLOBAL batch) -> (the rank's ids [b], target segment ids int32 [b, 1 + negs], window starts
+        int32 [b (2 + negs)]): one launch; the stream is advanced past all B items."""
         if self.state is None:
             self.seed_from_numpy()
+        mine = self.share(idx)
+        tgt, starts = self.ops.train_batch_plan(self.state, idx, self.rank * mine.numel(), mine.numel(), len(self.ds), self.ds.n_negs,
+                                                self.ds.stride)
+        return mine, tgt, starts
+
+    def sample(self, idx):
+        """idx int64 [B] (the global batch) -> (positive ids [b], negative ids [b, n_negs]) of the rank's b = B / world items, on the
+        device."""
         idx = torch.as_tensor(idx, dtype=torch.int64).to(self.dev).contiguous()
-        neg = self.ops.negative_sample(self.state, idx, len(self.ds), self.ds.n_negs)
-        return idx + 1, neg
+        mine, tgt, _ = self._plan(idx)
+        return mine + 1, tgt[:, 1:]
 
     def _pack(self, idx):
-        """idx int64 [B] (device) -> (q_frames, t_frames, target segment ids [B, 1 + negs])."""
-        ds, S, W = self.ds, self.ds.stride, self.ds.window
-        b = idx.numel()
-        pos, neg = self.sample(idx)
-        tgt = torch.cat((pos.view(b, 1), neg.to(torch.int64)), 1)  # [B, 1 + negs] segment ids
-        starts = (torch.cat((idx, tgt.reshape(-1))) * S).to(torch.int32).contiguous()
+        """idx int64 [B] (device, the global batch) -> (q_frames, t_frames, target segment ids [b, 1 + negs]) of the rank's b items."""
+        ds, W = self.ds, self.ds.window
+        mine, tgt, starts = self._plan(idx)
+        b = mine.numel()
+        tgt = tgt.to(torch.int64)  # (index tensors of the audio examples)
         hw, n = ds.img_size, tgt.shape[1]
         if not self.slowfast:
-            clips = self.ops.clip_gather_frames(self.table, starts, W)  # [B + B n, W, 3, hw, hw]
+            clips = self.ops.clip_gather_frames(self.table, starts, W)  # [b + b n, W, 3, hw, hw]
             return clips[:b], clips[b:].view(b, n, W, 3, hw, hw), tgt
         slow, fast = self.ops.clip_pack_gather(self.frames, starts, W, out_hw=hw, dtype=self.dtype)
         q_frames = [slow[:b], fast[:b]]
@@ -213,40 +252,80 @@ class DeviceSegmentBatcher:
 
     def batch(self, idx):
         idx = torch.as_tensor(idx, dtype=torch.int64).to(self.dev).contiguous()
-        b = idx.numel()
         q_frames, t_frames, tgt = self._pack(idx)
         q_ae = t_ae = None
         if self.audio_eg is not None:
-            q_ae = self.audio_eg[idx]
-            t_ae = self.audio_eg[tgt.reshape(-1)].view(b, tgt.shape[1], *self.audio_eg.shape[1:])
+            q_ae = self.audio_eg[self.share(idx)]
+            t_ae = self.audio_eg[tgt.reshape(-1)].view(tgt.shape[0], tgt.shape[1], *self.audio_eg.shape[1:])
         return q_frames, t_frames, q_ae, t_ae
 
-    def loader(self, batch_size, shuffle=True, drop_last=True):
+    def loader(self, batch_size, shuffle=True, drop_last=True, seed=None):
         """The DataLoader's place in train(): a re-iterable with __len__ whose epochs yield
-        (q_frames, None, q_audio_eg, t_frames, None, t_audio_eg) — train() never touches the waveform fields."""
-        return _DeviceLoader(self, int(batch_size), shuffle, drop_last)
+        (q_frames, None, q_audio_eg, t_frames, None, t_audio_eg) — train() never touches the waveform fields.
+
+        batch_size is PER RANK: every step draws one global batch of batch_size * world ids and the rank assembles its share.  With
+        several ranks, or with a seed, the order of epoch e is torch.randperm(n, generator=Generator().manual_seed(seed + e)) — the same on
+        every rank (a seed not given is drawn on rank 0 and broadcast), chosen by set_epoch(e) as with DistributedSampler; the loader is
+        its own `.sampler`.  One process without a seed keeps torch.randperm(n) from the global generator.  Several ranks need
+        drop_last: every rank must meet every batch shape at the same iteration.  The tail of an epoch that does not fill a global batch
+        is DROPPED — not padded with repeated items as DistributedSampler pads its shards — so an epoch is n // (batch_size * world)
+        steps and shows every item at most once."""
+        return _DeviceLoader(self, int(batch_size), shuffle, drop_last, seed)
 
 
 class _DeviceLoader:
-    def __init__(self, batcher, batch_size, shuffle, drop_last):
+    def __init__(self, batcher, batch_size, shuffle, drop_last, seed=None):
         if batch_size < 1:
             raise ValueError("DeviceSegmentBatcher.loader: batch_size must be positive")
         self.bat, self.batch_size, self.shuffle, self.drop_last = batcher, batch_size, shuffle, drop_last
+        world = batcher.world
+        self.global_batch = batch_size * world
+        if world > 1 and not drop_last:
+            raise ValueError("DeviceSegmentBatcher.loader: several ranks need drop_last=True (a short last batch would not divide over "
+                             "the ranks, and every rank must meet every batch shape at the same iteration)")
+        if drop_last and len(batcher.ds) < self.global_batch:
+            raise ValueError("DeviceSegmentBatcher.loader: %d items do not fill one global batch of %d (%d per rank x %d ranks)"
+                             % (len(batcher.ds), self.global_batch, batch_size, world))
+        self.epoch, self.seed = 0, seed
+        if shuffle and world > 1 and seed is None:
+            dist = torch.distributed
+            if not (dist.is_available() and dist.is_initialized()):
+                raise ValueError("DeviceSegmentBatcher.loader: several ranks without a process group need a seed (one order for all)")
+            t = torch.randint(0, 2 ** 31 - 1, (1,), dtype=torch.int64)  # (rank 0's draw counts; gloo and RCCL each move their own kind)
+            t = t if dist.get_backend() == "gloo" else t.to(batcher.dev)
+            dist.broadcast(t, src=0)
+            self.seed = int(t.cpu()[0])
+
+    @property
+    def sampler(self):
+        return self  # (main()'s train_loader.sampler.set_epoch(epoch))
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
 
     def __len__(self):
         n = len(self.bat.ds)
-        return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
+        return n // self.global_batch if self.drop_last else -(-n // self.global_batch)
+
+    def order(self):
+        """The item ids of the current epoch, in the order the global batches are cut from."""
+        n = len(self.bat.ds)
+        if not self.shuffle:
+            return torch.arange(n)
+        if self.seed is None:
+            return torch.randperm(n)  # (host order; not RandomSampler's stream)
+        return torch.randperm(n, generator=torch.Generator().manual_seed(self.seed + self.epoch))
 
     def __iter__(self):
         bat = self.bat
         if bat._audio_any is None:
             bat._audio_any = bat.audio_eg if bat.audio_eg is not None else bat.ds.audio_eg.to(bat.dev)
         audio = bat._audio_any
-        n = len(bat.ds)
-        order = torch.randperm(n) if self.shuffle else torch.arange(n)  # (host order; not RandomSampler's stream)
+        order = self.order()
         for i in range(len(self)):
-            idx = order[i * self.batch_size : (i + 1) * self.batch_size].to(bat.dev)
+            idx = order[i * self.global_batch : (i + 1) * self.global_batch].to(bat.dev)
             q_frames, t_frames, tgt = bat._pack(idx)
+            mine = bat.share(idx)
             # audio examples as the dataset indexes them (audio_eg[idx]; audio_eg[idx + 1] then audio_eg[neg]), whatever their rank
-            t_ae = audio[tgt.reshape(-1)].view(idx.numel(), tgt.shape[1], *audio.shape[1:])
-            yield q_frames, None, audio[idx], t_frames, None, t_ae
+            t_ae = audio[tgt.reshape(-1)].view(mine.numel(), tgt.shape[1], *audio.shape[1:])
+            yield q_frames, None, audio[mine], t_frames, None, t_ae

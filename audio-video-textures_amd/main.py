@@ -4,7 +4,9 @@ loop with the fps -> window/stride override (main.py:511-516) and default checkp
 
 Additions (all optional): --stitch_mode {compat,aligned}, --ref_num_gpus, --enc_dtype {fp32,bf16},
 --enc_batch, --train_input {loader,device}, --vcam (the flag validate.py:299 reads but the reference never defines [quirk Q2]).
-Multi-GPU: one process per GPU under torch.distributed.run instead of torch.nn.DataParallel (main.py:420).
+Multi-GPU: one process per GPU under torch.distributed.run instead of torch.nn.DataParallel (main.py:420).  --train_input device works
+there too, with or without --train_graph 1: every rank assembles its share of each global batch in its own HBM
+(dataset.DeviceSegmentBatcher(rank, world)), item for item the batch DataParallel would scatter from one NumPy stream.
 """
 import argparse
 import math
@@ -73,8 +75,10 @@ def build_parser():
     a("--train_input", default="loader", choices=["loader", "device"],
       help="where train() gets its batches: loader = torch DataLoader over AudioVideoSegments (host preprocessing, the reference's "
            "path); device = dataset.DeviceSegmentBatcher: the video resident in HBM (SlowFast: uint8 frames; other encoders: the "
-           "resized and normalised fp32 frame table), negatives drawn and windows gathered by HIP kernels, no per-step host copy; "
-           "one process only (the sharded sampler stays the DataLoader's)")
+           "resized and normalised fp32 frame table), negatives drawn and windows gathered by HIP kernels, no per-step host copy.  "
+           "Under torch.distributed.run every rank keeps the video and assembles its batch_size / world items of each global batch: "
+           "the ranks share rank 0's NumPy stream and one epoch order, so their batches are those of one process at the global batch; "
+           "the tail of an epoch that does not fill a global batch is dropped")
     a("--train_conv", default="x3", choices=["x3", "fp32"],
       help="arithmetic of the training convolutions (with --train_layout ndhwc): x3 = split-plane MFMA kernels, fp32 "
            "accumulation, forward 2^-22 / gradients 2^-16 per product (default; train_ops.py); fp32 = MIOpen's fp32 "
@@ -145,17 +149,7 @@ def main(args, video_name, itr=0):
     torch.cuda.set_device(device)
     if not args.evaluate and not args.visualize_evaluate:
         dataset_train = AudioVideoSegments(args, video_name, split="train")
-        sampler = torch.utils.data.distributed.DistributedSampler(dataset_train) if world > 1 else None
-        train_loader = torch.utils.data.DataLoader(dataset_train, batch_size=max(args.batch_size // world, 1),
-                                                   shuffle=sampler is None, sampler=sampler,
-                                                   num_workers=args.workers, drop_last=True)
-        if getattr(args, "train_input", "loader") == "device":
-            if world > 1:
-                raise ValueError("--train_input device assembles every batch on one GPU and has no sharded sampler: run one process, "
-                                 "or keep --train_input loader under torch.distributed.run")
-            from .dataset import DeviceSegmentBatcher
-
-            train_loader = DeviceSegmentBatcher(dataset_train, device).loader(max(args.batch_size, 1), shuffle=True, drop_last=True)
+        train_loader = build_train_loader(args, dataset_train, device, rank, world)
     print("=> creating model '{}'".format(args.model_type))
     builder = ModelBuilder3D()
     q_image_enc_model, fc_dim = builder.build_network(arch=args.enc_arch, img_size=args.size, window=args.window)
@@ -251,6 +245,24 @@ def main(args, video_name, itr=0):
         if loss < 0.07:
             print("Loss {}. Stopping at epoch {}.".format(loss, epoch))
             break
+
+
+def build_train_loader(args, dataset_train, device, rank, world):
+    """What train() iterates, batch_size // world items per rank and step: the DataLoader over the host dataset (sharded by
+    DistributedSampler across ranks), or with --train_input device the loader of dataset.DeviceSegmentBatcher — on every rank, each
+    assembling its share of one global batch per step from rank 0's NumPy stream and one epoch order."""
+    per = max(args.batch_size // world, 1)
+    if getattr(args, "train_input", "loader") == "device":
+        from .dataset import DeviceSegmentBatcher
+
+        loader = DeviceSegmentBatcher(dataset_train, device, rank=rank, world=world).loader(per, shuffle=True, drop_last=True)
+        if rank == 0:
+            print("training input: batches assembled on the device: world %d, per-rank batch %d, global batch %d, %d steps per epoch"
+                  % (world, per, per * world, len(loader)))
+        return loader
+    sampler = torch.utils.data.distributed.DistributedSampler(dataset_train) if world > 1 else None
+    return torch.utils.data.DataLoader(dataset_train, batch_size=per, shuffle=sampler is None, sampler=sampler,
+                                       num_workers=args.workers, drop_last=True)
 
 
 def wrap_ddp(model, device, local):

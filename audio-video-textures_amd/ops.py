@@ -279,6 +279,21 @@ def negative_sample(mt_state, idx, n_len, n_negs):
     return out
 
 
+def train_batch_plan(mt_state, idx, keep_lo, keep_n, n_len, n_negs, stride):
+    """One rank's share of a global batch: mt_state as in negative_sample, advanced past ALL of idx int64 [B] (the global batch, device);
+    items keep_lo .. keep_lo + keep_n - 1 are materialised -> (target segment ids int32 [keep_n, 1 + n_negs] = [idx + 1, negatives],
+    window starts int32 [keep_n (2 + n_negs)]: the query starts idx * stride, then the target starts, row-major)."""
+    _dev(mt_state, "mt_state", torch.int32)
+    _dev(idx, "idx", torch.int64)
+    keep_n, row = int(keep_n), 1 + int(n_negs)
+    # (an empty share still walks the stream; the entry takes no NULL pointer, so the buffers keep one row)
+    tgt = torch.empty((max(keep_n, 1), row), dtype=torch.int32, device=idx.device)
+    starts = torch.empty(max(keep_n, 1) * (row + 1), dtype=torch.int32, device=idx.device)
+    _lib.check(_lib.lib().avt_train_batch_plan(_p(mt_state), _p(idx), int(idx.numel()), int(keep_lo), keep_n, int(n_len), int(n_negs),
+                                               int(stride), _p(tgt), _p(starts), _stream()), "avt_train_batch_plan")
+    return tgt[:max(keep_n, 0)], starts[:max(keep_n, 0) * (row + 1)]
+
+
 # ---- l2norm --------------------------------------------------------------------
 def l2norm_rows(x0, x1=None, eps=1e-12, want_f32=True, want_split=False):
     """y = [x0|x1] / max(||.||, eps) row-wise -> (y_f32 | None, y_hi | None, y_lo | None)."""

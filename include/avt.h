@@ -517,6 +517,20 @@ int avt_negative_sample_mt19937(uint32_t* mt_state, const int64_t* idx, int batc
 int avt_clip_pack_gather_u8(const uint8_t* frames, int n_frames, int height, int width,
                             const int32_t* win_start, int n_win, int win_len, int out_hw, float mean,
                             float std, int bgr, void* slow, void* fast, int out_dtype, void* stream);
+/* avt_train_batch_plan: one RANK's share of a global batch of the same sampling (dataset.py:128-139, 181-190), for ranks that each
+ * assemble their items on their own device and still draw what ONE process would draw for the whole batch.  The stream is walked
+ * over all `batch` items of idx [batch] in order, exactly as avt_negative_sample_mt19937 walks it, and mt_state is advanced past all
+ * of them: every rank ends the call with the state of a one-process run.  The permutation is materialised for items keep_lo ..
+ * keep_lo + keep_n - 1 only; the others consume their draws (accepted iff (y & mask(i)) <= i, which does not depend on the
+ * permutation) and write nothing.  For kept item r = b - keep_lo:
+ *   tgt_out    int32 [keep_n, 1 + n_negs]:  [idx[b] + 1, negatives...], hard negatives over the head of the negatives;
+ *   starts_out int32 [keep_n (2 + n_negs)]: the window starts avt_clip_pack_gather_u8 / avt_clip_gather_frames_f32 read —
+ *              first the keep_n query starts idx[b] * stride, then the keep_n (1 + n_negs) target starts tgt * stride, row-major.
+ * Needs 0 <= keep_lo, 0 <= keep_n, keep_lo + keep_n <= batch, stride >= 1, (n_len + 1) * stride < 2^31 and the n_len / n_negs
+ * conditions of avt_negative_sample_mt19937.  keep_n == 0 still advances the stream; batch == 0 does nothing.  One wave.  Added
+ * without an ABI bump: a new symbol, no existing entry changed. */
+int avt_train_batch_plan(uint32_t* mt_state, const int64_t* idx, int batch, int keep_lo, int keep_n, int n_len, int n_negs,
+                         int stride, int32_t* tgt_out, int32_t* starts_out, void* stream);
 /* The same path for the 3D-ResNet encoders (csrc/frame_table.hip; the host preprocessing of dataset/dataset.py:44-58 and the
  * per-item slicing of :145-209).  Added without an ABI bump: new symbols, no existing entry changed.
  * avt_frames_resize_aa_norm_u8: frames uint8 [n_frames, height, width, 3] RGB (device) -> out fp32 [n_frames, 3, out_hw, out_hw]
