@@ -46,6 +46,11 @@ SIGNATURES = {
     "avt_diag_filter_f32": [_vp, C.c_int, _vp, C.c_int, _vp, _vp],
     "avt_q_learning_supported": [C.c_int],
     "avt_q_learning_f32": [_vp, C.c_int, C.c_float, C.c_float, C.c_int, _vp, _vp, _vp],
+    "avt_q_learning_wide_supported": [C.c_int],
+    "avt_q_learning_wide_workspace_bytes": [C.c_int],
+    "avt_q_learning_wide_f32": [_vp, C.c_int, C.c_float, C.c_float, C.c_int, _vp, _vp, _vp, C.c_int64, _vp],
+    "avt_classic_p_workspace_bytes": [],
+    "avt_classic_p_f32": [_vp, C.c_int, C.c_float, C.c_int, _vp, C.c_float, _vp, _vp, _vp, C.c_int64, _vp],
     "avt_conv33_c64_supported": [C.c_int] * 3,
     "avt_conv33_c64_bf16": [_vp] * 4 + [C.c_int] * 6 + [_vp],
     "avt_pw_chain_supported": [C.c_int] * 5,
@@ -181,7 +186,8 @@ def lib():
 
 
 ABI_VERSION = 8  # include/avt.h AVT_ABI_VERSION
-_RETURNS_I64 = {"avt_bn_train_ws_bytes", "avt_bn_train_ws_bytes_pre"}  # sizes; every other entry returns an AVT_* status
+_RETURNS_I64 = {"avt_bn_train_ws_bytes", "avt_bn_train_ws_bytes_pre", "avt_q_learning_wide_workspace_bytes",
+                "avt_classic_p_workspace_bytes"}  # sizes; every other entry returns an AVT_* status
 
 
 def check(status, what):

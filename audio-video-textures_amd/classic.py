@@ -1,10 +1,12 @@
-"""Classic (Schoedl-style) video textures — BASELINE config 1, CPU plumbing only.
+"""Classic (Schoedl-style) video textures — BASELINE config 1: the host forms, and the device forms next to them.
 
-`compute_D1_device` runs the distance matrix on the GPU (csrc/pairwise.hip); the rest restates
+`compute_D1_device` runs the distance matrix on the GPU (csrc/pairwise.hip), `compute_D2_device` / `q_learning_device` the
+next two stages (csrc/classic.hip; past 200 rows csrc/classic_wide.hip), `texture_device` the whole chain at any length and
+`texture_walk` the reference's walk over its result; the rest restates
 baselines/classic_video_textures/computeD1.py:47-96 + :240-247 (pairwise L2 D1, sigma,
 P1 shifted by one row and row-normalised), computeD2.py:21-52 (diagonal binomial filter) and
 q_learning.py:27-68 (future-cost iteration) on CPU torch, without the `.cuda()` calls and the missing
-`utils`/`models` modules that make the shipped scripts unrunnable.  Not a GPU target.
+`utils`/`models` modules that make the shipped scripts unrunnable.
 """
 import copy
 
@@ -68,15 +70,56 @@ def compute_D2_device(d1, sigma_factor, filter_size=16):
 
 
 def q_learning_device(d2, sigma_factor, p=0.7, alpha=0.997, thresholding=0.75, max_iter=1000):
-    """q_learning on the MI355X: every sweep inside ONE kernel launch with the matrix resident in LDS (csrc/classic.hip)."""
+    """q_learning on the MI355X: up to 200 rows every sweep inside ONE kernel launch with the matrix resident in LDS
+    (csrc/classic.hip); past that one launch per sweep over the whole card and the two-pass P tail (csrc/classic_wide.hip)."""
     from . import ops
 
+    if d2.shape[0] > 200:
+        d3_new, _ = ops.q_learning_wide((d2 ** p).contiguous(), alpha, 10e-3, max_iter)
+        p3, sigma, p3_new = ops.classic_p(d3_new, sigma_factor, threshold=thresholding)
+        return d3_new, p3, p3_new, sigma
     d3_new, _ = ops.q_learning((d2 ** p).contiguous(), alpha, 10e-3, max_iter)
     p3, sigma = _p_from_d(d3_new, sigma_factor)
     p3_new = p3.clone()
     cut = p3_new.max(dim=1, keepdim=True)[0]
     p3_new[p3_new < (cut - thresholding * cut)] = 0.0
     return d3_new, p3, p3_new, sigma
+
+
+def texture_device(frames, sigma_factor, filter_size=16, p=0.7, alpha=0.997, thresholding=0.75, max_iter=1000, device="cuda"):
+    """The whole classic chain (video_textures.py:266-284, model_type 1) on the MI355X, at any length the matrices fit:
+    pairwise_l2 -> classic_p -> diag_filter -> classic_p -> pow -> q_learning_wide -> classic_p with the threshold.
+    -> dict(d1, p1, sigma1, d2, p2, sigma2, d3, p3, p3_new, sigma3: device tensors; iters: the sweeps run, an int)."""
+    from . import ops
+
+    f = torch.as_tensor(frames).float().reshape(len(frames), -1).contiguous().to(device)
+    d1 = ops.pairwise_l2(f)
+    p1, sigma1 = ops.classic_p(d1, sigma_factor)
+    w = torch.tensor((np.poly1d([0.5, 0.5]) ** (filter_size - 1)).coeffs, dtype=torch.float32, device=d1.device)
+    d2 = ops.diag_filter(d1, w)
+    p2, sigma2 = ops.classic_p(d2, sigma_factor)
+    d3, iters = ops.q_learning_wide((d2 ** p).contiguous(), alpha, 10e-3, max_iter)
+    p3, sigma3, p3_new = ops.classic_p(d3, sigma_factor, threshold=thresholding)
+    return dict(d1=d1, p1=p1, sigma1=sigma1, d2=d2, p2=p2, sigma2=sigma2, d3=d3, p3=p3, p3_new=p3_new, sigma3=sigma3,
+                iters=int(iters.item()))
+
+
+def texture_walk(p3_new, n_steps, start=100, rng=None):
+    """The reference's model_type == 1 walk (video_textures.py:48-51, 73-81, 103, 120) -> (frames list, jump_count).  The next
+    frame is drawn UNIFORMLY among the survivors of the thresholded row, not weighted by P (`random_walk` weights); a step is a
+    jump when next != this + 1.  rng defaults to np.random, so a seeded run consumes the stream as the reference does.  Rows of
+    a device matrix are fetched one at a time."""
+    rng = rng or np.random
+    this, seq, jumps = int(start), [int(start)], 0
+    while len(seq) < n_steps:
+        row = p3_new[this]
+        alive = row.nonzero().view(-1).cpu().numpy() if isinstance(row, torch.Tensor) else np.flatnonzero(np.asarray(row))
+        nxt = int(rng.choice(alive))
+        if nxt != this + 1:
+            jumps += 1
+        seq.append(nxt)
+        this = nxt
+    return seq, jumps
 
 
 def compute_D2(d1, sigma_factor, filter_size=16, stride=1):

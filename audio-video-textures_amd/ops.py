@@ -1083,6 +1083,44 @@ def q_learning(d3, alpha, tol=10e-3, max_iter=1000):
     return out, iters
 
 
+def q_learning_wide(d3, alpha, tol=10e-3, max_iter=1000):
+    """The same sweeps, bit for bit, for 2..65535 rows (csrc/classic_wide.hip: one launch per sweep over many workgroups, the
+    matrix never rewritten) -> (D3_new, sweeps [1] int32 on the device).  Synchronises the stream (include/avt.h)."""
+    _dev(d3, "d3", torch.float32)
+    n = d3.shape[0]
+    if d3.dim() != 2 or d3.shape[1] != n:
+        raise _lib.AvtError("q_learning_wide: d3 must be square, got %s" % (tuple(d3.shape),))
+    lib = _lib.lib()
+    out = torch.empty_like(d3)
+    iters = torch.zeros(1, dtype=torch.int32, device=d3.device)
+    ws = torch.empty(max(int(lib.avt_q_learning_wide_workspace_bytes(int(n))), 16), dtype=torch.uint8, device=d3.device)
+    _lib.check(lib.avt_q_learning_wide_f32(_p(d3), int(n), float(alpha), float(tol), int(max_iter), _p(out), _p(iters), _p(ws),
+                                           int(ws.numel()), _stream()), "avt_q_learning_wide_f32")
+    return out, iters
+
+
+def classic_p(d, sigma_factor, threshold=None, sigma=None):
+    """sigma, exp, one-row shift, row-normalise of d [n, n] (computeD1.py:240-247) in two passes -> (p, sigma[, p_thr]);
+    p_thr (q_learning.py:59-64) only with a threshold.  sigma (a [1] fp32 device tensor) given: the statistics pass is skipped."""
+    _dev(d, "d", torch.float32)
+    n = d.shape[0]
+    if d.dim() != 2 or d.shape[1] != n:
+        raise _lib.AvtError("classic_p: d must be square, got %s" % (tuple(d.shape),))
+    lib = _lib.lib()
+    given = sigma is not None
+    if given:
+        _dev(sigma, "sigma", torch.float32)
+        sigma = sigma.reshape(1)
+    else:
+        sigma = torch.empty(1, dtype=torch.float32, device=d.device)
+    p = torch.empty_like(d)
+    p_thr = torch.empty_like(d) if threshold is not None else None
+    ws = torch.empty(int(lib.avt_classic_p_workspace_bytes()), dtype=torch.uint8, device=d.device)
+    _lib.check(lib.avt_classic_p_f32(_p(d), int(n), float(sigma_factor), int(given), _p(sigma), float(threshold or 0.0), _p(p),
+                                     _p(p_thr), _p(ws), int(ws.numel()), _stream()), "avt_classic_p_f32")
+    return (p, sigma[0]) if p_thr is None else (p, sigma[0], p_thr)
+
+
 # ---- audio front-end ------------------------------------------------------------------------
 def logmel(wave, window, melmat, hop, fft_len, log_offset):
     """wave [n] fp32/fp64, window [win] fp64, melmat [fft_len/2+1, n_mel] fp64 (device) -> log-mel [n_frames, n_mel]

@@ -867,6 +867,35 @@ int avt_diag_filter_f32(const float* d1, int n, const float* w, int fs, float* o
 int avt_q_learning_supported(int n);
 int avt_q_learning_f32(const float* d3, int n, float alpha, float tol, int max_iter, float* out, int* iters,
                        void* stream);
+/* The same iteration for 2 <= n <= 65535 rows, bit for bit (csrc/classic_wide.hip): per sweep
+ *   mins[j] = min_{k != j} old[j, k];  new[i, j] = fl32(d3[i, j] + fl32(alpha * mins[j])) for i >= 1, row 0 stays;
+ *   residual = fl32(sum of fl32(d * d) in fp64 / n^2), d = fl32(new - old);  stop when !(residual > tol) or after max_iter sweeps.
+ * The running matrix is never stored: every row i >= 1 receives the same addend a[j] = fl32(alpha * mins[j]), so a sweep is one
+ * read-only pass over d3 with two n-vectors, many workgroups wide.  One launch per sweep, and the launch boundary is the only
+ * dependency between workgroups (no grid barrier, no spin, no cooperative launch); the fp64 partial sums of the residual go
+ * through a per-workgroup buffer and are reduced in a fixed order, so two runs give the same bits and the same sweep count.
+ * Convergence is a word in the workspace; a launch that finds it set returns at once.  The entry issues at most
+ * max_iter + 2 sweep launches and READS THE WORD BACK AFTER EVERY 16th, which SYNCHRONISES THE STREAM (so it cannot be
+ * captured into a graph); it stops issuing once the word is set.  The last launch, which writes out [n, n] and *iters (device
+ * int, may be NULL) = sweeps run, is not waited for.
+ * ws: device memory of avt_q_learning_wide_workspace_bytes(n) bytes (0 for an n that is refused), 16-byte aligned, contents
+ * arbitrary, owned by the call until the stream has run it.  AVT_ERR_ARG before any launch for a bad n, max_iter outside
+ * 1..2^30, a NULL d3 / out / ws or a short or misaligned workspace. */
+int avt_q_learning_wide_supported(int n);
+int64_t avt_q_learning_wide_workspace_bytes(int n);
+int avt_q_learning_wide_f32(const float* d3, int n, float alpha, float tol, int max_iter, float* out, int* iters, void* ws,
+                            int64_t ws_bytes, void* stream);
+/* The tail every stage of the baseline ends with (computeD1.py:240-247, computeD2.py, q_learning.py:53-64) on d [n, n],
+ * 2 <= n <= 65535, in two passes; fully asynchronous, no host round trip:
+ *   statistics (skipped when sigma_given != 0, *sigma is then an input): S = sum d in fp64 in a fixed order, Z = the number
+ *     of elements != 0 (int64), *sigma (device) = fl32(fl32(sigma_factor) * fl32(fl32(S) / fl32(Z)));
+ *   rows: row i of p from row r = min(i + 1, n - 1) of d (the reference's one-row shift: the last row appears twice):
+ *     e = expf(fl32(-d[r, j] / sigma)), row sum in fp64 rounded once to fp32, p[i, j] = fl32(e / rowsum);
+ *   p_thr (may be NULL): with cut = max_j p[i, j], p_thr[i, j] = p[i, j] < fl32(cut - fl32(threshold * cut)) ? 0 : p[i, j].
+ * ws: avt_classic_p_workspace_bytes() bytes of device memory, 16-byte aligned (not needed when sigma_given). */
+int64_t avt_classic_p_workspace_bytes(void);
+int avt_classic_p_f32(const float* d, int n, float sigma_factor, int sigma_given, float* sigma, float threshold, float* p,
+                      float* p_thr, void* ws, int64_t ws_bytes, void* stream);
 
 /* Conv3d [1,3,3] 64 -> 64, stride 1, pad 1 (+ BN folded, optional ReLU) of the slow res2 blocks with the input
  * strip resident in LDS (csrc/conv33_c64.hip; same model, models/models.py:335, 399).  in [batch, t, h, w, 64],
