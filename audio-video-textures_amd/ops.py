@@ -11,6 +11,7 @@ import torch
 
 from . import _lib
 
+K = _lib.checked  # K.avt_X(...): the entry with its status checked (raises AvtError); queries go through _lib.lib()
 SIM_BF16, SIM_BF16X3, SIM_F32 = 0, 1, 2
 _PREC = {"bf16": SIM_BF16, "bf16x3": SIM_BF16X3, "f32": SIM_F32}
 FAST_T, SLOW_T, SLOTS = 32, 8, 40
@@ -58,7 +59,7 @@ def side_streams(device, n):
 
 def device_check():
     buf = C.create_string_buffer(64)
-    _lib.check(_lib.lib().avt_device_check(buf, 64), "avt_device_check")
+    K.avt_device_check(buf, 64)
     return buf.value.decode()
 
 
@@ -67,8 +68,7 @@ def clip_sample_table(win_len):
     """(fast_idx[32], slow_idx[8]) — torch.linspace(0, W-1, 32).long() and its 8-subsample."""
     fast = np.empty(FAST_T, np.int32)
     slow = np.empty(SLOW_T, np.int32)
-    _lib.check(_lib.lib().avt_clip_sample_table(int(win_len), fast.ctypes.data, slow.ctypes.data),
-               "avt_clip_sample_table")
+    K.avt_clip_sample_table(int(win_len), fast.ctypes.data, slow.ctypes.data)
     return fast, slow
 
 
@@ -78,8 +78,7 @@ def clip_pack_plan(win_start, win_len, n_frames):
     n_win = win_start.shape[0]
     off = np.empty(n_frames + 1, np.int32)
     slot = np.empty(max(n_win * SLOTS, 1), np.int32)
-    _lib.check(_lib.lib().avt_clip_pack_plan(win_start.ctypes.data, n_win, int(win_len), int(n_frames),
-                                             off.ctypes.data, slot.ctypes.data), "avt_clip_pack_plan")
+    K.avt_clip_pack_plan(win_start.ctypes.data, n_win, int(win_len), int(n_frames), off.ctypes.data, slot.ctypes.data)
     return off, slot[: n_win * SLOTS]
 
 
@@ -170,23 +169,19 @@ def clip_pack(frames_u8, win_start, win_len, out_hw=224, mean=0.45, std=0.225, b
         if planes is not None:
             pd = _X3[planes]
             slow, fast = SplitClip(mk(SLOW_T), mk(SLOW_T), pd), SplitClip(mk(FAST_T), mk(FAST_T), pd)
-            _lib.check(_lib.lib().avt_clip_pack_u8_ndhwc4_x3(_p(frames_u8), n_frames, h, w, _p(d_off), _p(d_slot), n_win,
-                                                             int(out_hw), float(mean), float(std), 1 if bgr else 0,
-                                                             _p(slow.hi), _p(slow.lo), _p(fast.hi), _p(fast.lo), pd,
-                                                             _stream()), "avt_clip_pack_u8_ndhwc4_x3")
+            K.avt_clip_pack_u8_ndhwc4_x3(_p(frames_u8), n_frames, h, w, _p(d_off), _p(d_slot), n_win, int(out_hw), float(mean),
+                                         float(std), 1 if bgr else 0, _p(slow.hi), _p(slow.lo), _p(fast.hi), _p(fast.lo), pd, _stream())
             return slow, fast
         slow, fast = mk(SLOW_T), mk(FAST_T)
-        _lib.check(_lib.lib().avt_clip_pack_u8_ndhwc4(_p(frames_u8), n_frames, h, w, _p(d_off), _p(d_slot), n_win,
-                                                      int(out_hw), float(mean), float(std), 1 if bgr else 0, _p(slow),
-                                                      _p(fast), _stream()), "avt_clip_pack_u8_ndhwc4")
+        K.avt_clip_pack_u8_ndhwc4(_p(frames_u8), n_frames, h, w, _p(d_off), _p(d_slot), n_win, int(out_hw), float(mean), float(std),
+                                  1 if bgr else 0, _p(slow), _p(fast), _stream())
         return slow, fast
     if dtype not in (torch.bfloat16, torch.float32):
         raise _lib.AvtError("clip_pack: dtype must be bfloat16 or float32")
     slow = torch.empty((n_win, 3, SLOW_T, out_hw, out_hw), dtype=dtype, device=frames_u8.device)
     fast = torch.empty((n_win, 3, FAST_T, out_hw, out_hw), dtype=dtype, device=frames_u8.device)
-    _lib.check(_lib.lib().avt_clip_pack_u8(_p(frames_u8), n_frames, h, w, _p(d_off), _p(d_slot), n_win, int(out_hw),
-                                           float(mean), float(std), 1 if bgr else 0, _p(slow), _p(fast),
-                                           1 if dtype == torch.bfloat16 else 0, _stream()), "avt_clip_pack_u8")
+    K.avt_clip_pack_u8(_p(frames_u8), n_frames, h, w, _p(d_off), _p(d_slot), n_win, int(out_hw), float(mean), float(std),
+                       1 if bgr else 0, _p(slow), _p(fast), 1 if dtype == torch.bfloat16 else 0, _stream())
     return slow, fast
 
 
@@ -210,9 +205,8 @@ def clip_pack_frames(frames_u8, win_start, win_len, out_hw=224, mean=0.45, std=0
     hi = torch.empty((n_grp * SLOW_T, out_hw, out_hw, 4), dtype=torch.bfloat16, device=dev)
     lo = torch.empty_like(hi)
     d_off, d_slot = torch.from_numpy(off).to(dev, non_blocking=True), torch.from_numpy(slot.astype(np.int32)).to(dev, non_blocking=True)
-    _lib.check(_lib.lib().avt_clip_pack_u8_ndhwc4_x3(_p(frames_u8), n_frames, h, w, _p(d_off), _p(d_slot), n_grp, int(out_hw),
-                                                     float(mean), float(std), 1 if bgr else 0, _p(hi), _p(lo), _p(hi), _p(lo), pd,
-                                                     _stream()), "avt_clip_pack_u8_ndhwc4_x3")
+    K.avt_clip_pack_u8_ndhwc4_x3(_p(frames_u8), n_frames, h, w, _p(d_off), _p(d_slot), n_grp, int(out_hw), float(mean), float(std),
+                                 1 if bgr else 0, _p(hi), _p(lo), _p(hi), _p(lo), pd, _stream())
     fast_off, slow_off = clip_sample_table(win_len)
     idx_f = torch.from_numpy((win_start[:, None] + fast_off[None, :]).astype(np.int32)).to(dev, non_blocking=True)
     idx_s = torch.from_numpy((win_start[:, None] + slow_off[None, :]).astype(np.int32)).to(dev, non_blocking=True)
@@ -231,9 +225,8 @@ def clip_pack_gather(frames_u8, win_start_dev, win_len, out_hw=224, mean=0.45, s
         raise _lib.AvtError("clip_pack_gather: dtype must be bfloat16 or float32")
     slow = torch.empty((n_win, 3, SLOW_T, out_hw, out_hw), dtype=dtype, device=frames_u8.device)
     fast = torch.empty((n_win, 3, FAST_T, out_hw, out_hw), dtype=dtype, device=frames_u8.device)
-    _lib.check(_lib.lib().avt_clip_pack_gather_u8(_p(frames_u8), n_frames, h, w, _p(win_start_dev), n_win, int(win_len),
-                                                  int(out_hw), float(mean), float(std), 1 if bgr else 0, _p(slow), _p(fast),
-                                                  1 if dtype == torch.bfloat16 else 0, _stream()), "avt_clip_pack_gather_u8")
+    K.avt_clip_pack_gather_u8(_p(frames_u8), n_frames, h, w, _p(win_start_dev), n_win, int(win_len), int(out_hw), float(mean),
+                              float(std), 1 if bgr else 0, _p(slow), _p(fast), 1 if dtype == torch.bfloat16 else 0, _stream())
     return slow, fast
 
 
@@ -249,8 +242,7 @@ def frames_resize_aa_norm(frames_u8, out_hw, mean=RESNET_MEAN, std=RESNET_STD):
     n_frames, h, w, _ = frames_u8.shape
     out = torch.empty((n_frames, 3, int(out_hw), int(out_hw)), dtype=torch.float32, device=frames_u8.device)
     m, s = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
-    _lib.check(_lib.lib().avt_frames_resize_aa_norm_u8(_p(frames_u8), n_frames, h, w, int(out_hw), m, s, _p(out), _stream()),
-               "avt_frames_resize_aa_norm_u8")
+    K.avt_frames_resize_aa_norm_u8(_p(frames_u8), n_frames, h, w, int(out_hw), m, s, _p(out), _stream())
     return out
 
 
@@ -263,8 +255,7 @@ def clip_gather_frames(table, win_start_dev, win_len):
         raise _lib.AvtError("clip_gather_frames: table must be [F, 3, hw, hw]")
     n_frames, hw, n_win = int(table.shape[0]), int(table.shape[2]), int(win_start_dev.numel())
     out = torch.empty((n_win, int(win_len), 3, hw, hw), dtype=torch.float32, device=table.device)
-    _lib.check(_lib.lib().avt_clip_gather_frames_f32(_p(table), n_frames, hw, _p(win_start_dev), n_win, int(win_len), _p(out),
-                                                     _stream()), "avt_clip_gather_frames_f32")
+    K.avt_clip_gather_frames_f32(_p(table), n_frames, hw, _p(win_start_dev), n_win, int(win_len), _p(out), _stream())
     return out
 
 
@@ -274,8 +265,7 @@ def negative_sample(mt_state, idx, n_len, n_negs):
     _dev(mt_state, "mt_state", torch.int32)
     _dev(idx, "idx", torch.int64)
     out = torch.empty((idx.numel(), int(n_negs)), dtype=torch.int32, device=idx.device)
-    _lib.check(_lib.lib().avt_negative_sample_mt19937(_p(mt_state), _p(idx), int(idx.numel()), int(n_len), int(n_negs),
-                                                      _p(out), _stream()), "avt_negative_sample_mt19937")
+    K.avt_negative_sample_mt19937(_p(mt_state), _p(idx), int(idx.numel()), int(n_len), int(n_negs), _p(out), _stream())
     return out
 
 
@@ -289,8 +279,8 @@ def train_batch_plan(mt_state, idx, keep_lo, keep_n, n_len, n_negs, stride):
     # (an empty share still walks the stream; the entry takes no NULL pointer, so the buffers keep one row)
     tgt = torch.empty((max(keep_n, 1), row), dtype=torch.int32, device=idx.device)
     starts = torch.empty(max(keep_n, 1) * (row + 1), dtype=torch.int32, device=idx.device)
-    _lib.check(_lib.lib().avt_train_batch_plan(_p(mt_state), _p(idx), int(idx.numel()), int(keep_lo), keep_n, int(n_len), int(n_negs),
-                                               int(stride), _p(tgt), _p(starts), _stream()), "avt_train_batch_plan")
+    K.avt_train_batch_plan(_p(mt_state), _p(idx), int(idx.numel()), int(keep_lo), keep_n, int(n_len), int(n_negs), int(stride),
+                           _p(tgt), _p(starts), _stream())
     return tgt[:max(keep_n, 0)], starts[:max(keep_n, 0) * (row + 1)]
 
 
@@ -308,8 +298,7 @@ def l2norm_rows(x0, x1=None, eps=1e-12, want_f32=True, want_split=False):
     y = torch.empty((n, d), dtype=torch.float32, device=x0.device) if want_f32 else None
     hi = torch.empty((n, d), dtype=torch.bfloat16, device=x0.device) if want_split else None
     lo = torch.empty((n, d), dtype=torch.bfloat16, device=x0.device) if want_split else None
-    _lib.check(_lib.lib().avt_l2norm_rows(_p(x0), d0, _p(x1), d1, n, float(eps), _p(y), _p(hi), _p(lo), _stream()),
-               "avt_l2norm_rows")
+    K.avt_l2norm_rows(_p(x0), d0, _p(x1), d1, n, float(eps), _p(y), _p(hi), _p(lo), _stream())
     return y, hi, lo
 
 
@@ -347,8 +336,8 @@ def sim_gemm_nt(q, t, temp, precision="f32", q_lo=None, t_lo=None, out=None, nq_
             out = torch.empty((nq, nt), dtype=torch.float32, device=q.device)
         else:
             _dev(out, "out", torch.float32, contiguous=False)
-        _lib.check(_lib.lib().avt_gemm_nt_x3_f32out(_p(q), _p(q_lo), d, _p(t), _p(t_lo), _p(out), out.stride(0), nq, nt, d, float(temp),
-                                                    _p(_gemm_ktab(d, d, q.device)), X3_BF16, _stream()), "avt_gemm_nt_x3_f32out")
+        K.avt_gemm_nt_x3_f32out(_p(q), _p(q_lo), d, _p(t), _p(t_lo), _p(out), out.stride(0), nq, nt, d, float(temp),
+                                _p(_gemm_ktab(d, d, q.device)), X3_BF16, _stream())
         return out
     want = torch.float32 if prec == SIM_F32 else torch.bfloat16
     _dev(q, "q", want)
@@ -363,8 +352,7 @@ def sim_gemm_nt(q, t, temp, precision="f32", q_lo=None, t_lo=None, out=None, nq_
         out = torch.empty((nq, nt), dtype=torch.float32, device=q.device)
     else:
         _dev(out, "out", torch.float32)
-    _lib.check(_lib.lib().avt_sim_gemm_nt(_p(q), _p(q_lo), _p(t), _p(t_lo), nq, nt, d, float(temp), prec, _p(out),
-                                          out.stride(0), _stream()), "avt_sim_gemm_nt")
+    K.avt_sim_gemm_nt(_p(q), _p(q_lo), _p(t), _p(t_lo), nq, nt, d, float(temp), prec, _p(out), out.stride(0), _stream())
     return out
 
 
@@ -386,10 +374,8 @@ def row_transition(sim, q_ids=None, sim_a=None, alpha=0.5, threshold=0.0, cap=64
     p = torch.zeros((nq, cap), dtype=torch.float32, device=dev)
     cnt = torch.zeros((nq,), dtype=torch.int32, device=dev)
     stats = torch.zeros((nq, 4), dtype=torch.float32, device=dev)
-    _lib.check(_lib.lib().avt_row_transition(_p(sim), nq, nt, sim.stride(0), _p(q_ids), n_seg, _p(sim_a),
-                                             sim_a.stride(0) if sim_a is not None else 0, float(alpha),
-                                             float(threshold), int(cap), _p(idx), _p(seg), _p(p), _p(cnt), _p(stats),
-                                             _stream()), "avt_row_transition")
+    K.avt_row_transition(_p(sim), nq, nt, sim.stride(0), _p(q_ids), n_seg, _p(sim_a), sim_a.stride(0) if sim_a is not None else 0,
+                         float(alpha), float(threshold), int(cap), _p(idx), _p(seg), _p(p), _p(cnt), _p(stats), _stream())
     return dict(idx=idx, seg=seg, p=p, cnt=cnt, stats=stats)
 
 
@@ -400,8 +386,7 @@ def row_topk(sim, k, self_col=None):
         _dev(self_col, "self_col", torch.int64)
     idx = torch.empty((nq, k), dtype=torch.int32, device=sim.device)
     val = torch.empty((nq, k), dtype=torch.float32, device=sim.device)
-    _lib.check(_lib.lib().avt_row_topk(_p(sim), nq, nt, sim.stride(0), _p(self_col), int(k), _p(idx), _p(val),
-                                       _stream()), "avt_row_topk")
+    K.avt_row_topk(_p(sim), nq, nt, sim.stride(0), _p(self_col), int(k), _p(idx), _p(val), _stream())
     return idx, val
 
 
@@ -413,8 +398,7 @@ def softmax_ce_fwd(logits, label=None):
         _dev(label, "label", torch.int64)
     loss = torch.empty((b,), dtype=torch.float32, device=logits.device)
     prob = torch.empty((b, c), dtype=torch.float32, device=logits.device)
-    _lib.check(_lib.lib().avt_softmax_ce_fwd(_p(logits), b, c, _p(label), _p(loss), _p(prob), _stream()),
-               "avt_softmax_ce_fwd")
+    K.avt_softmax_ce_fwd(_p(logits), b, c, _p(label), _p(loss), _p(prob), _stream())
     return loss, prob
 
 
@@ -422,8 +406,7 @@ def softmax_ce_bwd(prob, label=None, scale=1.0):
     _dev(prob, "prob", torch.float32)
     b, c = prob.shape
     d = torch.empty_like(prob)
-    _lib.check(_lib.lib().avt_softmax_ce_bwd(_p(prob), _p(label), b, c, float(scale), _p(d), _stream()),
-               "avt_softmax_ce_bwd")
+    K.avt_softmax_ce_bwd(_p(prob), _p(label), b, c, float(scale), _p(d), _stream())
     return d
 
 
@@ -433,8 +416,7 @@ def conv3d_ktab(cin, kernel, h, w, ldi):
     kt, kh, kw = kernel
     n_entries = 8 * ((kt * kh * kw * cin + 63) // 64) + 2  # + the 16 zero bytes the kernel reads for OOB chunks
     tab = np.empty((n_entries, 2), np.int32)
-    _lib.check(_lib.lib().avt_conv3d_ktab(int(cin), kt, kh, kw, int(h), int(w), int(ldi), tab.ctypes.data, n_entries),
-               "avt_conv3d_ktab")
+    K.avt_conv3d_ktab(int(cin), kt, kh, kw, int(h), int(w), int(ldi), tab.ctypes.data, n_entries)
     return tab
 
 
@@ -448,30 +430,16 @@ def conv3d_igemm(x_ptr, wt, bias, res_ptr, out_ptr, ktab, dims, cin, cout, kerne
     out_rows = (stride, H, W): output position (f, ho, wo) goes to row (f*H + stride*ho)*W + stride*wo of the output
     buffer (avt_conv3d_igemm_rows_bf16)."""
     b, t, h, w = dims
+    args = (C.c_void_p(x_ptr), _p(wt), _p(bias), C.c_void_p(res_ptr) if res_ptr else None, C.c_void_p(out_ptr), _p(ktab), b, t, h, w,
+            int(cin), int(cout), *kernel, *stride, *pad, *out_dims, int(ldi), int(ldo), int(ldr), 1 if relu else 0)
     if wfrag is not None:  # (fragment-order weights [tiles, nup, 2, 64, 8]: the XB tile, weights bypass the LDS)
         _dev(wfrag, "wfrag", torch.bfloat16)
         orr = out_rows if out_rows is not None else (1, 0, 0)
-        _lib.check(_lib.lib().avt_conv3d_igemm_wfrag_bf16(C.c_void_p(x_ptr), _p(wt), _p(bias),
-                                                          C.c_void_p(res_ptr) if res_ptr else None, C.c_void_p(out_ptr),
-                                                          _p(ktab), b, t, h, w, int(cin), int(cout), *kernel, *stride, *pad,
-                                                          *out_dims, int(ldi), int(ldo), int(ldr), 1 if relu else 0,
-                                                          int(orr[0]), int(orr[1]), int(orr[2]), _p(wfrag),
-                                                          int(wfrag.shape[1]), _stream()),
-                   "avt_conv3d_igemm_wfrag_bf16")
-        return
-    if out_rows is not None:
-        _lib.check(_lib.lib().avt_conv3d_igemm_rows_bf16(C.c_void_p(x_ptr), _p(wt), _p(bias),
-                                                         C.c_void_p(res_ptr) if res_ptr else None, C.c_void_p(out_ptr),
-                                                         _p(ktab), b, t, h, w, int(cin), int(cout), *kernel, *stride, *pad,
-                                                         *out_dims, int(ldi), int(ldo), int(ldr), 1 if relu else 0,
-                                                         int(out_rows[0]), int(out_rows[1]), int(out_rows[2]), _stream()),
-                   "avt_conv3d_igemm_rows_bf16")
-        return
-    _lib.check(_lib.lib().avt_conv3d_igemm_bf16(C.c_void_p(x_ptr), _p(wt), _p(bias),
-                                                C.c_void_p(res_ptr) if res_ptr else None, C.c_void_p(out_ptr), _p(ktab),
-                                                b, t, h, w, int(cin), int(cout), *kernel, *stride, *pad, *out_dims,
-                                                int(ldi), int(ldo), int(ldr), 1 if relu else 0, _stream()),
-               "avt_conv3d_igemm_bf16")
+        K.avt_conv3d_igemm_wfrag_bf16(*args, int(orr[0]), int(orr[1]), int(orr[2]), _p(wfrag), int(wfrag.shape[1]), _stream())
+    elif out_rows is not None:
+        K.avt_conv3d_igemm_rows_bf16(*args, int(out_rows[0]), int(out_rows[1]), int(out_rows[2]), _stream())
+    else:
+        K.avt_conv3d_igemm_bf16(*args, _stream())
 
 
 def conv3d_igemm_x3(x_ptrs, wt_hi, wt_lo, bias, res_ptrs, out_ptrs, ktab, dims, cin, cout, kernel, stride, pad, ldi, ldo,
@@ -484,13 +452,11 @@ def conv3d_igemm_x3(x_ptrs, wt_hi, wt_lo, bias, res_ptrs, out_ptrs, ktab, dims, 
     _dev(wt_lo, "wt_lo", torch.bfloat16)
     orr = out_rows if out_rows is not None else (1, 0, 0)
     rh, rl = res_ptrs if res_ptrs is not None else (0, 0)
-    fn = _lib.lib().avt_conv3d_igemm_x3_wblk if wblk else _lib.lib().avt_conv3d_igemm_x3
-    _lib.check(fn(C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]), _p(wt_hi), _p(wt_lo), _p(bias),
-                                              C.c_void_p(rh) if rh else None, C.c_void_p(rl) if rl else None,
-                                              C.c_void_p(out_ptrs[0]), C.c_void_p(out_ptrs[1]), _p(ktab), b, t, h, w,
-                                              int(cin), int(cout), *kernel, *stride, *pad, *out_dims, int(ldi), int(ldo),
-                                              int(ldr), int(relu), int(orr[0]), int(orr[1]), int(orr[2]),
-                                              int(plane_dtype), _p(wscale), _stream()), "avt_conv3d_igemm_x3_wblk" if wblk else "avt_conv3d_igemm_x3")
+    fn = K.avt_conv3d_igemm_x3_wblk if wblk else K.avt_conv3d_igemm_x3
+    fn(C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]), _p(wt_hi), _p(wt_lo), _p(bias), C.c_void_p(rh) if rh else None,
+       C.c_void_p(rl) if rl else None, C.c_void_p(out_ptrs[0]), C.c_void_p(out_ptrs[1]), _p(ktab), b, t, h, w, int(cin), int(cout),
+       *kernel, *stride, *pad, *out_dims, int(ldi), int(ldo), int(ldr), int(relu), int(orr[0]), int(orr[1]), int(orr[2]),
+       int(plane_dtype), _p(wscale), _stream())
 
 
 def conv3d_igemm_x3_f32(x, wt_hi, wt_lo, wscale, out, ktab, dims, cin, cout, kernel, stride, pad, ldi, ldo, plane_dtype, add=None):
@@ -503,10 +469,9 @@ def conv3d_igemm_x3_f32(x, wt_hi, wt_lo, wscale, out, ktab, dims, cin, cout, ker
     _dev(wt_lo, "wt_lo", torch.bfloat16)
     if add is not None:
         _dev(add, "add", torch.float32)
-    _lib.check(_lib.lib().avt_conv3d_igemm_x3_f32(_p(x), _p(wt_hi), _p(wt_lo), _p(wscale), _p(add), _p(out), _p(ktab), int(b), int(t),
-                                                  int(h), int(w), int(cin), int(cout), *[int(k) for k in kernel],
-                                                  *[int(v) for v in stride], *[int(v) for v in pad], int(ldi), int(ldo),
-                                                  int(cout), int(plane_dtype), _stream()), "avt_conv3d_igemm_x3_f32")
+    K.avt_conv3d_igemm_x3_f32(_p(x), _p(wt_hi), _p(wt_lo), _p(wscale), _p(add), _p(out), _p(ktab), int(b), int(t), int(h), int(w),
+                              int(cin), int(cout), *[int(k) for k in kernel], *[int(v) for v in stride], *[int(v) for v in pad],
+                              int(ldi), int(ldo), int(cout), int(plane_dtype), _stream())
 
 
 def conv3d_igemm_x3_f32_stats(x, wt_hi, wt_lo, wscale, out, ktab, dims, cin, cout, kernel, stride, pad, ldi, ldo, plane_dtype, groups, stat_c):
@@ -524,10 +489,9 @@ def conv3d_igemm_x3_f32_stats(x, wt_hi, wt_lo, wscale, out, ktab, dims, cin, cou
         raise _lib.AvtError("conv3d_igemm_x3_f32_stats: %d rows do not split into %d groups" % (m, groups))
     pre_rows = rows * max(1, int(stat_c) // 1024)
     ws = torch.empty(_lib.lib().avt_bn_train_ws_bytes_pre(int(stat_c), int(groups), pre_rows), dtype=torch.uint8, device=x.device)
-    _lib.check(_lib.lib().avt_conv3d_igemm_x3_f32_stats(_p(x), _p(wt_hi), _p(wt_lo), _p(wscale), _p(out), _p(ktab), int(b), int(t), int(h),
-                                                        int(w), int(cin), int(cout), *[int(v) for v in kernel], *[int(v) for v in stride],
-                                                        *[int(v) for v in pad], int(ldi), int(ldo), int(plane_dtype), _p(ws), int(groups),
-                                                        int(stat_c), _stream()), "avt_conv3d_igemm_x3_f32_stats")
+    K.avt_conv3d_igemm_x3_f32_stats(_p(x), _p(wt_hi), _p(wt_lo), _p(wscale), _p(out), _p(ktab), int(b), int(t), int(h), int(w), int(cin),
+                                    int(cout), *[int(v) for v in kernel], *[int(v) for v in stride], *[int(v) for v in pad], int(ldi),
+                                    int(ldo), int(plane_dtype), _p(ws), int(groups), int(stat_c), _stream())
     return ws, pre_rows
 
 
@@ -545,8 +509,8 @@ def pw_x3_f32(x, k, wt_hi, wt_lo, wscale, out, n, plane_dtype, add=None):
     if add is not None:
         _dev(add, "add", torch.float32)
     m = x.numel() // k
-    _lib.check(_lib.lib().avt_pw_x3_f32(_p(x), int(k), int(k), _p(wt_hi), _p(wt_lo), _p(wscale), _p(add), int(n), _p(out), int(n), int(n),
-                                        int(m), int(plane_dtype), _stream()), "avt_pw_x3_f32")
+    K.avt_pw_x3_f32(_p(x), int(k), int(k), _p(wt_hi), _p(wt_lo), _p(wscale), _p(add), int(n), _p(out), int(n), int(n), int(m),
+                    int(plane_dtype), _stream())
 
 
 def conv3d_igemm_x3_f32_bwdstats(dy, wt_hi, wt_lo, out, ktab, dims, cin, cout, kernel, pad, plane_dtype, bn, groups, stat_c, add=None):
@@ -565,10 +529,10 @@ def conv3d_igemm_x3_f32_bwdstats(dy, wt_hi, wt_lo, out, ktab, dims, cin, cout, k
     bx, mean, invstd, gamma, beta, mask, relu = bn
     pre_rows = rows * max(1, int(stat_c) // 1024)
     ws = torch.empty(_lib.lib().avt_bn_train_ws_bytes_pre(int(stat_c), int(groups), pre_rows), dtype=torch.uint8, device=dy.device)
-    _lib.check(_lib.lib().avt_conv3d_igemm_x3_f32_bwdstats(
+    K.avt_conv3d_igemm_x3_f32_bwdstats(
         _p(dy), _p(wt_hi), _p(wt_lo), None, _p(add), _p(out), _p(ktab), int(b), int(t), int(h), int(w), int(cin), int(cout),
         *[int(v) for v in kernel], *[int(v) for v in pad], int(cin), int(cout), int(cout), int(plane_dtype), _p(bx), _p(mean), _p(invstd),
-        _p(gamma), _p(beta), _p(mask), int(relu), _p(ws), int(groups), int(stat_c), _stream()), "avt_conv3d_igemm_x3_f32_bwdstats")
+        _p(gamma), _p(beta), _p(mask), int(relu), _p(ws), int(groups), int(stat_c), _stream())
     return ws, pre_rows
 
 
@@ -584,9 +548,9 @@ def pw_x3_f32_bwdstats(dy, k, wt_hi, wt_lo, out, n, plane_dtype, bn, groups, add
     bx, mean, invstd, gamma, beta, mask, relu = bn
     pre_rows = rows * max(1, int(n) // 1024)
     ws = torch.empty(_lib.lib().avt_bn_train_ws_bytes_pre(int(n), int(groups), pre_rows), dtype=torch.uint8, device=dy.device)
-    _lib.check(_lib.lib().avt_pw_x3_f32_bwdstats(_p(dy), int(k), int(k), _p(wt_hi), _p(wt_lo), _p(add), int(n), _p(out), int(n), int(n), int(m),
-                                                 int(plane_dtype), _p(bx), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(mask),
-                                                 1 if relu else 0, _p(ws), int(groups), _stream()), "avt_pw_x3_f32_bwdstats")
+    K.avt_pw_x3_f32_bwdstats(_p(dy), int(k), int(k), _p(wt_hi), _p(wt_lo), _p(add), int(n), _p(out), int(n), int(n), int(m),
+                             int(plane_dtype), _p(bx), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(mask), 1 if relu else 0, _p(ws),
+                             int(groups), _stream())
     return ws, pre_rows
 
 
@@ -603,8 +567,8 @@ def pw_x3_f32_stats(x, k, wt_hi, wt_lo, wscale, out, n, plane_dtype, groups):
         return None
     pre_rows = rows * max(1, int(n) // 1024)
     ws = torch.empty(_lib.lib().avt_bn_train_ws_bytes_pre(int(n), int(groups), pre_rows), dtype=torch.uint8, device=x.device)
-    _lib.check(_lib.lib().avt_pw_x3_f32_stats(_p(x), int(k), int(k), _p(wt_hi), _p(wt_lo), _p(wscale), _p(out), int(n), int(n), int(m),
-                                              int(plane_dtype), _p(ws), int(groups), _stream()), "avt_pw_x3_f32_stats")
+    K.avt_pw_x3_f32_stats(_p(x), int(k), int(k), _p(wt_hi), _p(wt_lo), _p(wscale), _p(out), int(n), int(n), int(m), int(plane_dtype),
+                          _p(ws), int(groups), _stream())
     return ws, pre_rows
 
 
@@ -616,11 +580,10 @@ def conv3d_igemm_x3_f32_ex(x, wt_hi, wt_lo, wscale, out, ktab, dims, cin, cout, 
     _dev(x, "x", torch.float32)
     _dev(wt_hi, "wt_hi", torch.bfloat16)
     _dev(wt_lo, "wt_lo", torch.bfloat16)
-    _lib.check(_lib.lib().avt_conv3d_igemm_x3_f32_ex(_p(x), _p(wt_hi), _p(wt_lo), _p(wscale), C.c_void_p(out.data_ptr()), _p(ktab), int(b),
-                                                     int(t), int(h), int(w), int(cin), int(cout), *[int(k) for k in kernel],
-                                                     *[int(v) for v in pad], *[int(v) for v in out_dims], int(ldi), int(ldo),
-                                                     int(out_rows[0]), int(out_rows[1]), int(out_rows[2]), int(plane_dtype), _stream()),
-               "avt_conv3d_igemm_x3_f32_ex")
+    K.avt_conv3d_igemm_x3_f32_ex(_p(x), _p(wt_hi), _p(wt_lo), _p(wscale), C.c_void_p(out.data_ptr()), _p(ktab), int(b), int(t), int(h),
+                                 int(w), int(cin), int(cout), *[int(k) for k in kernel], *[int(v) for v in pad],
+                                 *[int(v) for v in out_dims], int(ldi), int(ldo), int(out_rows[0]), int(out_rows[1]), int(out_rows[2]),
+                                 int(plane_dtype), _stream())
 
 
 def weight_planes_f32(w2d, plane_dtype):
@@ -631,8 +594,7 @@ def weight_planes_f32(w2d, plane_dtype):
     hi = torch.empty((cout, k), dtype=torch.bfloat16, device=w2d.device)
     lo = torch.empty_like(hi)
     ws = torch.empty(cout, dtype=torch.float32, device=w2d.device) if plane_dtype == X3_F16 else None
-    _lib.check(_lib.lib().avt_weight_planes_f32(_p(w2d), int(cout), int(k), _p(hi), _p(lo), _p(ws), int(plane_dtype), _stream()),
-               "avt_weight_planes_f32")
+    K.avt_weight_planes_f32(_p(w2d), int(cout), int(k), _p(hi), _p(lo), _p(ws), int(plane_dtype), _stream())
     return hi, lo, ws
 
 
@@ -645,8 +607,8 @@ def weight_planes_gather_f32(w, idx_map, plane_dtype):
     hi = torch.empty((rows, k), dtype=torch.bfloat16, device=w.device)
     lo = torch.empty_like(hi)
     ws = torch.empty(rows, dtype=torch.float32, device=w.device) if plane_dtype == X3_F16 else None
-    _lib.check(_lib.lib().avt_weight_planes_gather_f32(C.c_void_p(w.data_ptr()), _p(idx_map), int(rows), int(k), _p(hi), _p(lo), _p(ws),
-                                                       int(plane_dtype), _stream()), "avt_weight_planes_gather_f32")
+    K.avt_weight_planes_gather_f32(C.c_void_p(w.data_ptr()), _p(idx_map), int(rows), int(k), _p(hi), _p(lo), _p(ws), int(plane_dtype),
+                                   _stream())
     return hi, lo, ws
 
 
@@ -663,7 +625,7 @@ def weight_planes_multi(jobs, blk2job, nblocks):
     """Every job of a DEVICE table of AvtPlaneJob (include/avt.h) in one launch: the planes of all of a step's weights, in place
     (train_ops._refresh_planes builds the table from the single launches' own arguments)."""
     assert jobs.is_cuda and blk2job.is_cuda and blk2job.dtype == torch.int32 and blk2job.numel() == nblocks
-    _lib.check(_lib.lib().avt_weight_planes_multi(_p(jobs), _p(blk2job), int(nblocks), _stream()), "avt_weight_planes_multi")
+    K.avt_weight_planes_multi(_p(jobs), _p(blk2job), int(nblocks), _stream())
 
 
 def sgd_job_bytes():
@@ -675,7 +637,7 @@ def sgd_multi(jobs, blk2job, nblocks, hyper):
     device tensor `hyper` [groups, 4] = lr, momentum, weight_decay, nesterov (train_ops.ArenaSGD builds the table)."""
     assert jobs.is_cuda and blk2job.is_cuda and blk2job.dtype == torch.int32 and blk2job.numel() == nblocks
     assert hyper.is_cuda and hyper.dtype == torch.float32 and hyper.is_contiguous() and hyper.shape[-1] == 4
-    _lib.check(_lib.lib().avt_sgd_multi(_p(jobs), _p(blk2job), int(nblocks), _p(hyper), _stream()), "avt_sgd_multi")
+    K.avt_sgd_multi(_p(jobs), _p(blk2job), int(nblocks), _p(hyper), _stream())
 
 
 def sgd_upload(dst, src_pinned, nbytes):
@@ -683,7 +645,7 @@ def sgd_upload(dst, src_pinned, nbytes):
     node of the graph, which re-reads the host tensor on every replay (the caller keeps it alive and unchanged)."""
     assert dst.is_cuda and dst.is_contiguous() and not src_pinned.is_cuda and src_pinned.is_pinned() and src_pinned.is_contiguous()
     assert 0 < nbytes <= min(dst.numel() * dst.element_size(), src_pinned.numel() * src_pinned.element_size())
-    _lib.check(_lib.lib().avt_sgd_upload(_p(dst), _p(src_pinned), int(nbytes), _stream()), "avt_sgd_upload")
+    K.avt_sgd_upload(_p(dst), _p(src_pinned), int(nbytes), _stream())
 
 
 def pack_job_bytes():
@@ -695,7 +657,7 @@ def grad_pack_multi(jobs, blk2job, nblocks, scale):
     of one element the kernel loads (train_ops.GradExchange builds the table: every gradient of a step into one flat buffer)."""
     assert jobs.is_cuda and blk2job.is_cuda and blk2job.dtype == torch.int32 and blk2job.numel() == nblocks
     assert scale.is_cuda and scale.dtype == torch.float32 and scale.numel() == 1
-    _lib.check(_lib.lib().avt_grad_pack_multi(_p(jobs), _p(blk2job), int(nblocks), _p(scale), _stream()), "avt_grad_pack_multi")
+    K.avt_grad_pack_multi(_p(jobs), _p(blk2job), int(nblocks), _p(scale), _stream())
 
 
 def weight_planes_t_f32(w3d, sel):
@@ -706,8 +668,7 @@ def weight_planes_t_f32(w3d, sel):
     hi = torch.empty((cin, len(sel) * cout), dtype=torch.bfloat16, device=w3d.device)
     lo = torch.empty_like(hi)
     arr = (C.c_int32 * len(sel))(*[int(v) for v in sel])
-    _lib.check(_lib.lib().avt_weight_planes_t_f32(_p(w3d), int(cout), int(taps), int(cin), arr, len(sel), _p(hi), _p(lo), _stream()),
-               "avt_weight_planes_t_f32")
+    K.avt_weight_planes_t_f32(_p(w3d), int(cout), int(taps), int(cin), arr, len(sel), _p(hi), _p(lo), _stream())
     return hi, lo
 
 
@@ -717,9 +678,8 @@ def conv3d_wgrad_x3_f32(dy, x, dw, dims, cin, cout, kernel, stride, pad, ldx, ld
     _dev(dy, "dy", torch.float32)
     _dev(x, "x", torch.float32)
     _dev(dw, "dw", torch.float32)
-    _lib.check(_lib.lib().avt_conv3d_wgrad_x3_f32(_p(dy), _p(x), _p(dw), int(b), int(t), int(h), int(w), int(cin), int(cout),
-                                                  *[int(k) for k in kernel], *[int(v) for v in stride], *[int(v) for v in pad],
-                                                  int(ldx), int(ldy), _stream()), "avt_conv3d_wgrad_x3_f32")
+    K.avt_conv3d_wgrad_x3_f32(_p(dy), _p(x), _p(dw), int(b), int(t), int(h), int(w), int(cin), int(cout), *[int(k) for k in kernel],
+                              *[int(v) for v in stride], *[int(v) for v in pad], int(ldx), int(ldy), _stream())
 
 
 def conv3d_wgrad_x3_sub_f32(dy, x, dw, dims, cin, cout, kernel, stride, pad, out_dims, ldx, ldy, ldw, zero_dw):
@@ -728,10 +688,9 @@ def conv3d_wgrad_x3_sub_f32(dy, x, dw, dims, cin, cout, kernel, stride, pad, out
     b, t, h, w = dims
     _dev(dy, "dy", torch.float32)
     _dev(x, "x", torch.float32)
-    _lib.check(_lib.lib().avt_conv3d_wgrad_x3_sub_f32(_p(dy), _p(x), C.c_void_p(dw.data_ptr()), int(b), int(t), int(h), int(w),
-                                                      int(cin), int(cout), *[int(k) for k in kernel], *[int(v) for v in stride],
-                                                      *[int(v) for v in pad], *[int(v) for v in out_dims], int(ldx), int(ldy),
-                                                      int(ldw), int(bool(zero_dw)), _stream()), "avt_conv3d_wgrad_x3_sub_f32")
+    K.avt_conv3d_wgrad_x3_sub_f32(_p(dy), _p(x), C.c_void_p(dw.data_ptr()), int(b), int(t), int(h), int(w), int(cin), int(cout),
+                                  *[int(k) for k in kernel], *[int(v) for v in stride], *[int(v) for v in pad],
+                                  *[int(v) for v in out_dims], int(ldx), int(ldy), int(ldw), int(bool(zero_dw)), _stream())
 
 
 def stem_conv_x3(x_ptrs, wt_hi, wt_lo, bias, wscale, out_ptrs, batch, t, h, pw, cout, kt, st, pt, plane_dtype, relu=True,
@@ -745,11 +704,9 @@ def stem_conv_x3(x_ptrs, wt_hi, wt_lo, bias, wscale, out_ptrs, batch, t, h, pw, 
         _dev(frame_idx, "frame_idx", torch.int32)
         if frame_idx.numel() != batch * t:
             raise _lib.AvtError("stem_conv_x3: frame_idx has %d entries, expected batch * t = %d" % (frame_idx.numel(), batch * t))
-    _lib.check(_lib.lib().avt_stem_conv_x3(C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]), _p(wt_hi), _p(wt_lo), _p(bias),
-                                           _p(wscale), C.c_void_p(out_ptrs[0]), C.c_void_p(out_ptrs[1]), int(batch), int(t),
-                                           int(h), int(pw), int(cout), int(kt), int(st), int(pt), int(bool(relu)),
-                                           int(plane_dtype), int(frames_per_tile), _p(frame_idx), int(table_frames), _stream()),
-               "avt_stem_conv_x3")
+    K.avt_stem_conv_x3(C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]), _p(wt_hi), _p(wt_lo), _p(bias), _p(wscale), C.c_void_p(out_ptrs[0]),
+                       C.c_void_p(out_ptrs[1]), int(batch), int(t), int(h), int(pw), int(cout), int(kt), int(st), int(pt), int(bool(relu)),
+                       int(plane_dtype), int(frames_per_tile), _p(frame_idx), int(table_frames), _stream())
 
 
 def lateral_x3_supported(cin, cout, kt):
@@ -761,10 +718,9 @@ def lateral_x3(x_ptrs, ldx, cin, w_hi, w_lo, bias, wscale, y_ptrs, ldy, cout, ba
     temporal-tap form): SlowFast's lateral connections; w_* = fused_slowfast.pack_pw_planes of the conv's [cout -> 32 k, kt * cin] rows."""
     _dev(w_hi, "w_hi", torch.bfloat16)
     _dev(w_lo, "w_lo", torch.bfloat16)
-    _lib.check(_lib.lib().avt_lateral_x3(C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]), int(ldx), int(cin), _p(w_hi), _p(w_lo), _p(bias),
-                                         _p(wscale), C.c_void_p(y_ptrs[0]), C.c_void_p(y_ptrs[1]), int(ldy), int(cout), int(batch),
-                                         int(t), int(hw), int(kt), int(st), int(pt), int(relu), int(plane_dtype), _stream()),
-               "avt_lateral_x3")
+    K.avt_lateral_x3(C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]), int(ldx), int(cin), _p(w_hi), _p(w_lo), _p(bias), _p(wscale),
+                     C.c_void_p(y_ptrs[0]), C.c_void_p(y_ptrs[1]), int(ldy), int(cout), int(batch), int(t), int(hw), int(kt), int(st),
+                     int(pt), int(relu), int(plane_dtype), _stream())
 
 
 def stem_conv_x3_merged(x_ptrs, wt_hi, wt_lo, bias, wscale, out_ptrs, batch, t, h, pw, cout, kt, st, pt, plane_dtype, tap_frames,
@@ -774,11 +730,10 @@ def stem_conv_x3_merged(x_ptrs, wt_hi, wt_lo, bias, wscale, out_ptrs, batch, t, 
     _dev(wt_lo, "wt_lo", torch.bfloat16)
     _dev(tap_frames, "tap_frames", torch.int32)
     _dev(tap_tiles, "tap_tiles", torch.int32)
-    _lib.check(_lib.lib().avt_stem_conv_x3_merged(C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]), _p(wt_hi), _p(wt_lo), _p(bias),
-                                                  _p(wscale), C.c_void_p(out_ptrs[0]), C.c_void_p(out_ptrs[1]), int(batch), int(t),
-                                                  int(h), int(pw), int(cout), int(kt), int(st), int(pt), int(bool(relu)),
-                                                  int(plane_dtype), _p(tap_frames), _p(tap_tiles), int(ktm), int(table_frames),
-                                                  _stream()), "avt_stem_conv_x3_merged")
+    K.avt_stem_conv_x3_merged(C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]), _p(wt_hi), _p(wt_lo), _p(bias), _p(wscale),
+                              C.c_void_p(out_ptrs[0]), C.c_void_p(out_ptrs[1]), int(batch), int(t), int(h), int(pw), int(cout), int(kt),
+                              int(st), int(pt), int(bool(relu)), int(plane_dtype), _p(tap_frames), _p(tap_tiles), int(ktm),
+                              int(table_frames), _stream())
 
 
 def clip_planes_f32(x, plane_dtype):
@@ -791,8 +746,7 @@ def clip_planes_f32(x, plane_dtype):
     hi = torch.empty((b, t, h, w, 4), dtype=torch.bfloat16, device=x.device)
     lo = torch.empty_like(hi)
     sb, sc, st, sh, sw = x.stride()
-    _lib.check(_lib.lib().avt_clip_planes_f32(_p(x), b, t, h, w, sb, sc, st, sh, sw, _p(hi), _p(lo), int(plane_dtype), _stream()),
-               "avt_clip_planes_f32")
+    K.avt_clip_planes_f32(_p(x), b, t, h, w, sb, sc, st, sh, sw, _p(hi), _p(lo), int(plane_dtype), _stream())
     return hi, lo
 
 
@@ -801,9 +755,8 @@ def stem_conv_x3_f32(x_hi, x_lo, wt_hi, wt_lo, wscale, out, batch, t, h, pw, cou
     _dev(wt_hi, "wt_hi", torch.bfloat16)
     _dev(wt_lo, "wt_lo", torch.bfloat16)
     _dev(out, "out", torch.float32, contiguous=False)
-    _lib.check(_lib.lib().avt_stem_conv_x3_f32(_p(x_hi), _p(x_lo), _p(wt_hi), _p(wt_lo), _p(wscale), _p(out), int(batch), int(t),
-                                               int(h), int(pw), int(cout), int(kt), int(st), int(pt), int(tgroup),
-                                               int(plane_dtype), int(frames_per_tile), _stream()), "avt_stem_conv_x3_f32")
+    K.avt_stem_conv_x3_f32(_p(x_hi), _p(x_lo), _p(wt_hi), _p(wt_lo), _p(wscale), _p(out), int(batch), int(t), int(h), int(pw), int(cout),
+                           int(kt), int(st), int(pt), int(tgroup), int(plane_dtype), int(frames_per_tile), _stream())
 
 
 def stem_wgrad_x3_supported(h, pw, cout, kt):
@@ -815,8 +768,7 @@ def stem_wgrad_x3(x_hi, x_lo, dy, batch, t, h, pw, cout, kt, pt):
     of clip_planes_f32, dy = fp32 NDHWC rows [batch, to, h/2, pw, cout] (dense)."""
     _dev(dy, "dy", torch.float32, contiguous=False)
     dw = torch.zeros((cout, kt, 7, 4, 8), dtype=torch.float32, device=dy.device)
-    _lib.check(_lib.lib().avt_stem_wgrad_x3(_p(x_hi), _p(x_lo), _p(dy), _p(dw), int(batch), int(t), int(h), int(pw), int(cout),
-                                            int(kt), int(pt), _stream()), "avt_stem_wgrad_x3")
+    K.avt_stem_wgrad_x3(_p(x_hi), _p(x_lo), _p(dy), _p(dw), int(batch), int(t), int(h), int(pw), int(cout), int(kt), int(pt), _stream())
     return dw
 
 
@@ -829,10 +781,9 @@ def pw_x3(x_ptrs, ldx, k, w_hi, w_lo, bias, wscale, res_ptrs, ldr, y_ptrs, ldy, 
     _dev(w_hi, "w_hi", torch.bfloat16)
     _dev(w_lo, "w_lo", torch.bfloat16)
     rh, rl = res_ptrs if res_ptrs is not None else (0, 0)
-    _lib.check(_lib.lib().avt_pw_x3(C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]), int(ldx), int(k), _p(w_hi), _p(w_lo),
-                                    _p(bias), _p(wscale), C.c_void_p(rh) if rh else None, C.c_void_p(rl) if rl else None,
-                                    int(ldr), C.c_void_p(y_ptrs[0]), C.c_void_p(y_ptrs[1]), int(ldy), int(n), int(m),
-                                    1 if relu else 0, int(plane_dtype), _stream()), "avt_pw_x3")
+    K.avt_pw_x3(C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]), int(ldx), int(k), _p(w_hi), _p(w_lo), _p(bias), _p(wscale),
+                C.c_void_p(rh) if rh else None, C.c_void_p(rl) if rl else None, int(ldr), C.c_void_p(y_ptrs[0]), C.c_void_p(y_ptrs[1]),
+                int(ldy), int(n), int(m), 1 if relu else 0, int(plane_dtype), _stream())
 
 
 def pw_chain_x3_supported(k1, n1, n2):
@@ -844,12 +795,10 @@ def pw_chain_x3(x_ptrs, ldx, k1, w1, bias1, wscale1, res_ptrs, ldr, y_ptrs, ldy,
     """y = act(W1 x + b1 [+ res]), z = relu(W2 y + b2) in one pass on plane pairs (csrc/pw_x3.hip); w1 / w2 = (hi, lo) fragment
     planes (fused_slowfast.pack_pw_planes)."""
     rh, rl = res_ptrs if res_ptrs is not None else (0, 0)
-    _lib.check(_lib.lib().avt_pw_chain_x3(C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]), int(ldx), int(k1), _p(w1[0]), _p(w1[1]),
-                                          _p(bias1), _p(wscale1), C.c_void_p(rh) if rh else None, C.c_void_p(rl) if rl else None,
-                                          int(ldr), C.c_void_p(y_ptrs[0]), C.c_void_p(y_ptrs[1]), int(ldy), int(n1),
-                                          1 if relu1 else 0, _p(w2[0]), _p(w2[1]), _p(bias2), _p(wscale2), C.c_void_p(z_ptrs[0]),
-                                          C.c_void_p(z_ptrs[1]), int(ldz), int(n2), int(m), int(plane_dtype), _stream()),
-               "avt_pw_chain_x3")
+    K.avt_pw_chain_x3(C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]), int(ldx), int(k1), _p(w1[0]), _p(w1[1]), _p(bias1), _p(wscale1),
+                      C.c_void_p(rh) if rh else None, C.c_void_p(rl) if rl else None, int(ldr), C.c_void_p(y_ptrs[0]),
+                      C.c_void_p(y_ptrs[1]), int(ldy), int(n1), 1 if relu1 else 0, _p(w2[0]), _p(w2[1]), _p(bias2), _p(wscale2),
+                      C.c_void_p(z_ptrs[0]), C.c_void_p(z_ptrs[1]), int(ldz), int(n2), int(m), int(plane_dtype), _stream())
 
 
 def maxpool_hw3s2_x3(x_ptrs, out_ptrs, bt, h, w, c, ldi, ldo, plane_dtype, tgroup=1, frame_idx=None):
@@ -858,38 +807,32 @@ def maxpool_hw3s2_x3(x_ptrs, out_ptrs, bt, h, w, c, ldi, ldo, plane_dtype, tgrou
         _dev(frame_idx, "frame_idx", torch.int32)
         if frame_idx.numel() != bt:
             raise _lib.AvtError("maxpool_hw3s2_x3: frame_idx has %d entries, expected %d" % (frame_idx.numel(), bt))
-    _lib.check(_lib.lib().avt_maxpool_hw3s2_ndhwc_x3(C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]), C.c_void_p(out_ptrs[0]),
-                                                     C.c_void_p(out_ptrs[1]), int(bt), int(h), int(w), int(c), int(ldi),
-                                                     int(ldo), int(tgroup), int(plane_dtype), _p(frame_idx), _stream()),
-               "avt_maxpool_hw3s2_ndhwc_x3")
+    K.avt_maxpool_hw3s2_ndhwc_x3(C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]), C.c_void_p(out_ptrs[0]), C.c_void_p(out_ptrs[1]), int(bt),
+                                 int(h), int(w), int(c), int(ldi), int(ldo), int(tgroup), int(plane_dtype), _p(frame_idx), _stream())
 
 
 def maxpool_hw2s2_x3(x_ptrs, out_ptrs, bt, h, w, c, ldi, ldo, plane_dtype):
     """MaxPool2d(2, 2), floor mode, on plane pairs (NHWC rows): the contract-grade VGGish."""
-    _lib.check(_lib.lib().avt_maxpool_hw2s2_ndhwc_x3(C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]), C.c_void_p(out_ptrs[0]),
-                                                     C.c_void_p(out_ptrs[1]), int(bt), int(h), int(w), int(c), int(ldi),
-                                                     int(ldo), int(plane_dtype), _stream()), "avt_maxpool_hw2s2_ndhwc_x3")
+    K.avt_maxpool_hw2s2_ndhwc_x3(C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]), C.c_void_p(out_ptrs[0]), C.c_void_p(out_ptrs[1]), int(bt),
+                                 int(h), int(w), int(c), int(ldi), int(ldo), int(plane_dtype), _stream())
 
 
 def maxpool3d_k3s2_x3(x_ptrs, out_ptrs, batch, t, h, w, c, ldi, ldo, plane_dtype):
     """MaxPool3d(3, 2, 1) over T, H and W on plane pairs (NDHWC rows): the 3D ResNets' stem pool."""
-    _lib.check(_lib.lib().avt_maxpool3d_k3s2_ndhwc_x3(C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]), C.c_void_p(out_ptrs[0]),
-                                                      C.c_void_p(out_ptrs[1]), int(batch), int(t), int(h), int(w), int(c),
-                                                      int(ldi), int(ldo), int(plane_dtype), _stream()), "avt_maxpool3d_k3s2_ndhwc_x3")
+    K.avt_maxpool3d_k3s2_ndhwc_x3(C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]), C.c_void_p(out_ptrs[0]), C.c_void_p(out_ptrs[1]),
+                                  int(batch), int(t), int(h), int(w), int(c), int(ldi), int(ldo), int(plane_dtype), _stream())
 
 
 def mean_positions_x3(x_ptrs, batch, p, c, ldi, out, col0, plane_dtype):
     _dev(out, "out", torch.float32)
-    _lib.check(_lib.lib().avt_mean_positions_x3(C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]), int(batch), int(p), int(c),
-                                                int(ldi), C.c_void_p(out.data_ptr() + 4 * int(col0)), int(out.shape[1]),
-                                                int(plane_dtype), _stream()), "avt_mean_positions_x3")
+    K.avt_mean_positions_x3(C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]), int(batch), int(p), int(c), int(ldi),
+                            C.c_void_p(out.data_ptr() + 4 * int(col0)), int(out.shape[1]), int(plane_dtype), _stream())
 
 
 def maxpool_hw3s2(x_ptr, out_ptr, bt, h, w, c, ldi, ldo, tgroup=1):
     """MaxPool3d((1,3,3),(1,2,2),(0,1,1)) on NDHWC bf16 rows (raw device addresses)."""
-    _lib.check(_lib.lib().avt_maxpool_hw3s2_ndhwc_bf16(C.c_void_p(x_ptr), C.c_void_p(out_ptr), int(bt), int(h), int(w),
-                                                       int(c), int(ldi), int(ldo), int(tgroup), _stream()),
-               "avt_maxpool_hw3s2_ndhwc_bf16")
+    K.avt_maxpool_hw3s2_ndhwc_bf16(C.c_void_p(x_ptr), C.c_void_p(out_ptr), int(bt), int(h), int(w), int(c), int(ldi), int(ldo),
+                                   int(tgroup), _stream())
 
 
 def stem_conv_supported(h, pw, cout):
@@ -901,18 +844,16 @@ def stem_conv(x_ptr, wt, bias, out_ptr, batch, t, h, pw, cout, kt, st, pt, relu=
     activations, wt = fused_slowfast.stem_lds_image(packed weights) bf16, bias [cout] fp32."""
     _dev(wt, "wt", torch.bfloat16)
     _dev(bias, "bias", torch.float32)
-    _lib.check(_lib.lib().avt_stem_conv_bf16(C.c_void_p(x_ptr), _p(wt), _p(bias), C.c_void_p(out_ptr), int(batch), int(t),
-                                             int(h), int(pw), int(cout), int(kt), int(st), int(pt), int(bool(relu)),
-                                             _stream()), "avt_stem_conv_bf16")
+    K.avt_stem_conv_bf16(C.c_void_p(x_ptr), _p(wt), _p(bias), C.c_void_p(out_ptr), int(batch), int(t), int(h), int(pw), int(cout),
+                         int(kt), int(st), int(pt), int(bool(relu)), _stream())
 
 
 def stem_conv_pool(x_ptr, wt, bias, out_ptr, batch, t, h, pw, cout, kt, st, pt, tgroup, ldo):
     """stem_conv + ReLU + MaxPool3d((1,3,3),(1,2,2),(0,1,1)) in one kernel; out = pooled rows (stride ldo elements)."""
     _dev(wt, "wt", torch.bfloat16)
     _dev(bias, "bias", torch.float32)
-    _lib.check(_lib.lib().avt_stem_conv_pool_bf16(C.c_void_p(x_ptr), _p(wt), _p(bias), C.c_void_p(out_ptr), int(batch),
-                                                  int(t), int(h), int(pw), int(cout), int(kt), int(st), int(pt),
-                                                  int(tgroup), int(ldo), _stream()), "avt_stem_conv_pool_bf16")
+    K.avt_stem_conv_pool_bf16(C.c_void_p(x_ptr), _p(wt), _p(bias), C.c_void_p(out_ptr), int(batch), int(t), int(h), int(pw), int(cout),
+                              int(kt), int(st), int(pt), int(tgroup), int(ldo), _stream())
 
 
 def bottleneck_fused_supported(c, w):
@@ -923,9 +864,8 @@ def bottleneck_fused(x_ptr, out_ptr, packed, batch, t, h, w, c, tchunk=8):
     """One fast-pathway identity bottleneck (a [3,1,1] -> b [1,3,3] -> c [1,1,1] + x, ReLUs, BN folded) in one kernel;
     packed = fused_slowfast.pack_bottleneck(...) = (wa, ba, wb, bb, wc, bc) device tensors; raw activation addresses."""
     wa, ba, wb, bb, wc, bc = packed
-    _lib.check(_lib.lib().avt_bottleneck_fused_bf16(C.c_void_p(x_ptr), C.c_void_p(out_ptr), _p(wa), _p(ba), _p(wb), _p(bb),
-                                                    _p(wc), _p(bc), int(batch), int(t), int(h), int(w), int(c),
-                                                    int(tchunk), _stream()), "avt_bottleneck_fused_bf16")
+    K.avt_bottleneck_fused_bf16(C.c_void_p(x_ptr), C.c_void_p(out_ptr), _p(wa), _p(ba), _p(wb), _p(bb), _p(wc), _p(bc), int(batch),
+                                int(t), int(h), int(w), int(c), int(tchunk), _stream())
 
 
 def conv3d_igemm_x3_xl_picked(cout, k, m):
@@ -942,9 +882,8 @@ def conv33_x3(x_ptrs, packed, out_ptrs, batch, t, h, w, ldi, ldo, plane_dtype, r
     wfrag, coef = packed
     _dev(wfrag, "wfrag", torch.bfloat16)
     _dev(coef, "coef", torch.float32)
-    _lib.check(_lib.lib().avt_conv33_x3(C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]), _p(wfrag), _p(coef), C.c_void_p(out_ptrs[0]),
-                                        C.c_void_p(out_ptrs[1]), int(batch), int(t), int(h), int(w), int(ldi), int(ldo),
-                                        int(bool(relu)), int(plane_dtype), _stream()), "avt_conv33_x3")
+    K.avt_conv33_x3(C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]), _p(wfrag), _p(coef), C.c_void_p(out_ptrs[0]), C.c_void_p(out_ptrs[1]),
+                    int(batch), int(t), int(h), int(w), int(ldi), int(ldo), int(bool(relu)), int(plane_dtype), _stream())
 
 
 def res2_x3_supported(c, cm, w):
@@ -969,9 +908,8 @@ def res2_x3(x_ptrs, ldi, out_ptrs, ldo, packed, batch, t, h, w, plane_dtype):
     for b0 in range(0, int(batch), max(per, 1)):
         nb = min(per, int(batch) - b0)
         xo, oo = b0 * t * h * w * int(ldi) * 2, b0 * t * h * w * int(ldo) * 2
-        _lib.check(_lib.lib().avt_res2_x3(C.c_void_p(x_ptrs[0] + xo), C.c_void_p(x_ptrs[1] + xo), C.c_void_p(out_ptrs[0] + oo),
-                                          C.c_void_p(out_ptrs[1] + oo), _p(wfrag), _p(coef), nb, int(t), int(h), int(w), int(ldi), int(ldo),
-                                          int(plane_dtype), _stream()), "avt_res2_x3")
+        K.avt_res2_x3(C.c_void_p(x_ptrs[0] + xo), C.c_void_p(x_ptrs[1] + xo), C.c_void_p(out_ptrs[0] + oo), C.c_void_p(out_ptrs[1] + oo),
+                      _p(wfrag), _p(coef), nb, int(t), int(h), int(w), int(ldi), int(ldo), int(plane_dtype), _stream())
 
 
 def bneck_x3_supported(cin, c, w):
@@ -984,17 +922,15 @@ def bneck_x3(x_ptrs, out_ptrs, packed, batch, t, h, w, cin, c, plane_dtype, tchu
     wfrag, coef = packed
     _dev(wfrag, "wfrag", torch.bfloat16)
     _dev(coef, "coef", torch.float32)
-    _lib.check(_lib.lib().avt_bneck_x3(C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]), C.c_void_p(out_ptrs[0]),
-                                       C.c_void_p(out_ptrs[1]), _p(wfrag), _p(coef), int(batch), int(t), int(h), int(w),
-                                       int(cin), int(c), int(tchunk), int(plane_dtype), _stream()), "avt_bneck_x3")
+    K.avt_bneck_x3(C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]), C.c_void_p(out_ptrs[0]), C.c_void_p(out_ptrs[1]), _p(wfrag), _p(coef),
+                   int(batch), int(t), int(h), int(w), int(cin), int(c), int(tchunk), int(plane_dtype), _stream())
 
 
 def mean_positions(x_ptr, batch, p, c, ldi, out, col0=0):
     """Head average pool: bf16 rows [batch*p, ldi] (raw address) -> out[:, col0:col0+c] fp32 (device tensor [batch, D])."""
     _dev(out, "out", torch.float32)
-    _lib.check(_lib.lib().avt_mean_positions_bf16(C.c_void_p(x_ptr), int(batch), int(p), int(c), int(ldi),
-                                                  C.c_void_p(out.data_ptr() + 4 * int(col0)), int(out.shape[1]), _stream()),
-               "avt_mean_positions_bf16")
+    K.avt_mean_positions_bf16(C.c_void_p(x_ptr), int(batch), int(p), int(c), int(ldi), C.c_void_p(out.data_ptr() + 4 * int(col0)),
+                              int(out.shape[1]), _stream())
 
 
 def bottleneck_first_supported(cin, c, w):
@@ -1005,9 +941,8 @@ def bottleneck_first(x_ptr, out_ptr, packed, batch, t, h, w, cin, c, tchunk=8):
     """First fast-pathway block of res2 (8 -> 32 channels, shortcut conv) in one kernel; packed =
     fused_slowfast.pack_bottleneck(..., shortcut=(wsc, bsc)) = (wa, ba, wb, bb, wc, bc, wsc)."""
     wa, ba, wb, bb, wc, bc, wsc = packed
-    _lib.check(_lib.lib().avt_bottleneck_first_bf16(C.c_void_p(x_ptr), C.c_void_p(out_ptr), _p(wa), _p(ba), _p(wb), _p(bb),
-                                                    _p(wc), _p(wsc), _p(bc), int(batch), int(t), int(h), int(w), int(cin),
-                                                    int(c), int(tchunk), _stream()), "avt_bottleneck_first_bf16")
+    K.avt_bottleneck_first_bf16(C.c_void_p(x_ptr), C.c_void_p(out_ptr), _p(wa), _p(ba), _p(wb), _p(bb), _p(wc), _p(wsc), _p(bc),
+                                int(batch), int(t), int(h), int(w), int(cin), int(c), int(tchunk), _stream())
 
 
 def conv33_c64_supported(cin, cout, w):
@@ -1018,8 +953,8 @@ def conv33_c64(x_ptr, wb, bias, out_ptr, batch, t, h, w, ldo, relu=True):
     """[1,3,3] 64 -> 64 conv with the input strip resident in LDS; wb = fused_slowfast.pack_c33(...)."""
     _dev(wb, "wb", torch.bfloat16)
     _dev(bias, "bias", torch.float32)
-    _lib.check(_lib.lib().avt_conv33_c64_bf16(C.c_void_p(x_ptr), _p(wb), _p(bias), C.c_void_p(out_ptr), int(batch), int(t),
-                                              int(h), int(w), int(ldo), int(bool(relu)), _stream()), "avt_conv33_c64_bf16")
+    K.avt_conv33_c64_bf16(C.c_void_p(x_ptr), _p(wb), _p(bias), C.c_void_p(out_ptr), int(batch), int(t), int(h), int(w), int(ldo),
+                          int(bool(relu)), _stream())
 
 
 def pw_chain_supported(k1, n1, n2, has_res, k2x=0):
@@ -1033,18 +968,14 @@ def pw_chain(x1_ptr, ldx, k1, w1, b1, res_ptr, ldr, y_ptr, ldy, n1, w2, b2, z_pt
     _dev(w2, "w2", torch.bfloat16)
     _dev(b1, "b1", torch.float32)
     _dev(b2, "b2", torch.float32)
-    _lib.check(_lib.lib().avt_pw_chain_bf16(C.c_void_p(x1_ptr), int(ldx), int(k1), _p(w1), _p(b1),
-                                            C.c_void_p(res_ptr) if res_ptr else None, int(ldr), C.c_void_p(y_ptr), int(ldy),
-                                            int(n1), C.c_void_p(x2_ptr) if x2_ptr else None, int(ldx2), int(k2x), _p(w2),
-                                            _p(b2), C.c_void_p(z_ptr), int(ldz), int(n2), int(m), _stream()),
-               "avt_pw_chain_bf16")
+    K.avt_pw_chain_bf16(C.c_void_p(x1_ptr), int(ldx), int(k1), _p(w1), _p(b1), C.c_void_p(res_ptr) if res_ptr else None, int(ldr),
+                        C.c_void_p(y_ptr), int(ldy), int(n1), C.c_void_p(x2_ptr) if x2_ptr else None, int(ldx2), int(k2x), _p(w2), _p(b2),
+                        C.c_void_p(z_ptr), int(ldz), int(n2), int(m), _stream())
 
 
 def maxpool_hw2s2(x_ptr, out_ptr, bt, h, w, c, ldi, ldo):
     """MaxPool2d(2, 2), floor mode, on NHWC bf16 rows (raw device addresses) — VGGish (audio_models/vggish.py:15-33)."""
-    _lib.check(_lib.lib().avt_maxpool_hw2s2_ndhwc_bf16(C.c_void_p(x_ptr), C.c_void_p(out_ptr), int(bt), int(h), int(w),
-                                                       int(c), int(ldi), int(ldo), _stream()),
-               "avt_maxpool_hw2s2_ndhwc_bf16")
+    K.avt_maxpool_hw2s2_ndhwc_bf16(C.c_void_p(x_ptr), C.c_void_p(out_ptr), int(bt), int(h), int(w), int(c), int(ldi), int(ldo), _stream())
 
 
 # ---- classic baseline -----------------------------------------------------------------------
@@ -1053,7 +984,7 @@ def pairwise_l2(x):
     _dev(x, "x", torch.float32)
     n, d = x.shape
     out = torch.empty((n, n), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().avt_pairwise_l2_f32(_p(x), int(n), int(d), _p(out), _stream()), "avt_pairwise_l2_f32")
+    K.avt_pairwise_l2_f32(_p(x), int(n), int(d), _p(out), _stream())
     return out
 
 
@@ -1063,7 +994,7 @@ def diag_filter(d1, w):
     _dev(w, "w", torch.float32)
     n, fs = d1.shape[0], int(w.numel())
     out = torch.empty((n - fs + 1, n - fs + 1), dtype=torch.float32, device=d1.device)
-    _lib.check(_lib.lib().avt_diag_filter_f32(_p(d1), int(n), _p(w), fs, _p(out), _stream()), "avt_diag_filter_f32")
+    K.avt_diag_filter_f32(_p(d1), int(n), _p(w), fs, _p(out), _stream())
     return out
 
 
@@ -1078,8 +1009,7 @@ def q_learning(d3, alpha, tol=10e-3, max_iter=1000):
     assert d3.shape[1] == n
     out = torch.empty_like(d3)
     iters = torch.zeros(1, dtype=torch.int32, device=d3.device)
-    _lib.check(_lib.lib().avt_q_learning_f32(_p(d3), int(n), float(alpha), float(tol), int(max_iter), _p(out), _p(iters),
-                                             _stream()), "avt_q_learning_f32")
+    K.avt_q_learning_f32(_p(d3), int(n), float(alpha), float(tol), int(max_iter), _p(out), _p(iters), _stream())
     return out, iters
 
 
@@ -1090,12 +1020,11 @@ def q_learning_wide(d3, alpha, tol=10e-3, max_iter=1000):
     n = d3.shape[0]
     if d3.dim() != 2 or d3.shape[1] != n:
         raise _lib.AvtError("q_learning_wide: d3 must be square, got %s" % (tuple(d3.shape),))
-    lib = _lib.lib()
     out = torch.empty_like(d3)
     iters = torch.zeros(1, dtype=torch.int32, device=d3.device)
-    ws = torch.empty(max(int(lib.avt_q_learning_wide_workspace_bytes(int(n))), 16), dtype=torch.uint8, device=d3.device)
-    _lib.check(lib.avt_q_learning_wide_f32(_p(d3), int(n), float(alpha), float(tol), int(max_iter), _p(out), _p(iters), _p(ws),
-                                           int(ws.numel()), _stream()), "avt_q_learning_wide_f32")
+    ws = torch.empty(max(int(_lib.lib().avt_q_learning_wide_workspace_bytes(int(n))), 16), dtype=torch.uint8, device=d3.device)
+    K.avt_q_learning_wide_f32(_p(d3), int(n), float(alpha), float(tol), int(max_iter), _p(out), _p(iters), _p(ws), int(ws.numel()),
+                              _stream())
     return out, iters
 
 
@@ -1106,7 +1035,6 @@ def classic_p(d, sigma_factor, threshold=None, sigma=None):
     n = d.shape[0]
     if d.dim() != 2 or d.shape[1] != n:
         raise _lib.AvtError("classic_p: d must be square, got %s" % (tuple(d.shape),))
-    lib = _lib.lib()
     given = sigma is not None
     if given:
         _dev(sigma, "sigma", torch.float32)
@@ -1115,9 +1043,9 @@ def classic_p(d, sigma_factor, threshold=None, sigma=None):
         sigma = torch.empty(1, dtype=torch.float32, device=d.device)
     p = torch.empty_like(d)
     p_thr = torch.empty_like(d) if threshold is not None else None
-    ws = torch.empty(int(lib.avt_classic_p_workspace_bytes()), dtype=torch.uint8, device=d.device)
-    _lib.check(lib.avt_classic_p_f32(_p(d), int(n), float(sigma_factor), int(given), _p(sigma), float(threshold or 0.0), _p(p),
-                                     _p(p_thr), _p(ws), int(ws.numel()), _stream()), "avt_classic_p_f32")
+    ws = torch.empty(int(_lib.lib().avt_classic_p_workspace_bytes()), dtype=torch.uint8, device=d.device)
+    K.avt_classic_p_f32(_p(d), int(n), float(sigma_factor), int(given), _p(sigma), float(threshold or 0.0), _p(p), _p(p_thr), _p(ws),
+                        int(ws.numel()), _stream())
     return (p, sigma[0]) if p_thr is None else (p, sigma[0], p_thr)
 
 
@@ -1136,9 +1064,8 @@ def logmel(wave, window, melmat, hop, fft_len, log_offset):
     n = int(wave.numel())
     n_frames = 1 + (n - win) // hop if n >= win else 0
     out = torch.empty((n_frames, n_mel), dtype=torch.float64, device=wave.device)
-    _lib.check(_lib.lib().avt_logmel_f64(_p(wave), int(wave.dtype == torch.float64), n, _p(window), win, int(hop),
-                                         int(fft_len), _p(melmat), n_mel, float(log_offset), _p(out), _stream()),
-               "avt_logmel_f64")
+    K.avt_logmel_f64(_p(wave), int(wave.dtype == torch.float64), n, _p(window), win, int(hop), int(fft_len), _p(melmat), n_mel,
+                     float(log_offset), _p(out), _stream())
     return out
 
 
@@ -1149,8 +1076,7 @@ def logmel_examples(lm, ex_len, ex_hop):
     n_frames, n_mel = int(lm.shape[0]), int(lm.shape[1])
     n_ex = 1 + (n_frames - ex_len) // ex_hop if n_frames >= ex_len else 0
     out = torch.empty((n_ex, ex_len, n_mel), dtype=torch.float32, device=lm.device)
-    _lib.check(_lib.lib().avt_logmel_examples_f32(_p(lm), n_frames, n_mel, int(ex_len), int(ex_hop), _p(out),
-                                                  _stream()), "avt_logmel_examples_f32")
+    K.avt_logmel_examples_f32(_p(lm), n_frames, n_mel, int(ex_len), int(ex_hop), _p(out), _stream())
     return out
 
 
@@ -1163,8 +1089,7 @@ def infonce_fwd(q, t, temp, eps=1e-12):
     logits = torch.empty((b, n), dtype=torch.float32, device=q.device)
     inv_q = torch.empty((b,), dtype=torch.float32, device=q.device)
     inv_t = torch.empty((b, n), dtype=torch.float32, device=q.device)
-    _lib.check(_lib.lib().avt_infonce_fwd(_p(q), _p(t), b, n, d, float(temp), float(eps), _p(logits), _p(inv_q), _p(inv_t),
-                                          _stream()), "avt_infonce_fwd")
+    K.avt_infonce_fwd(_p(q), _p(t), b, n, d, float(temp), float(eps), _p(logits), _p(inv_q), _p(inv_t), _stream())
     return logits, inv_q, inv_t
 
 
@@ -1172,9 +1097,8 @@ def infonce_bwd(q, t, logits, dlogits, inv_q, inv_t, temp):
     b, n, d = t.shape
     dq = torch.empty_like(q)
     dt = torch.empty_like(t)
-    _lib.check(_lib.lib().avt_infonce_bwd(_p(q), _p(t), _p(logits), _p(_dev(dlogits.contiguous(), "dlogits", torch.float32)),
-                                          _p(inv_q), _p(inv_t), b, n, d, float(temp), _p(dq), _p(dt), _stream()),
-               "avt_infonce_bwd")
+    K.avt_infonce_bwd(_p(q), _p(t), _p(logits), _p(_dev(dlogits.contiguous(), "dlogits", torch.float32)), _p(inv_q), _p(inv_t), b, n, d,
+                      float(temp), _p(dq), _p(dt), _stream())
     return dq, dt
 
 
@@ -1189,38 +1113,35 @@ def interp_pack_pair(frame0, frame1, mean, img, x_ptrs, plane_dtype):
     _dev(frame1, "frame1", torch.uint8)
     _dev(img, "img", torch.float32)
     h, w = frame0.shape[0], frame0.shape[1]
-    _lib.check(_lib.lib().avt_interp_pack_pair_u8(_p(frame0), _p(frame1), int(h), int(w), _mean3(mean), _p(img), C.c_void_p(x_ptrs[0]),
-                                                  C.c_void_p(x_ptrs[1]), int(plane_dtype), _stream()), "avt_interp_pack_pair_u8")
+    K.avt_interp_pack_pair_u8(_p(frame0), _p(frame1), int(h), int(w), _mean3(mean), _p(img), C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]),
+                              int(plane_dtype), _stream())
 
 
 def avgpool2_x3(x_ptrs, dims, c, ldi, y_ptrs, ldo, plane_dtype):
     b, h, w = dims
-    _lib.check(_lib.lib().avt_avgpool2_x3(C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]), int(b), int(h), int(w), int(c), int(ldi),
-                                          C.c_void_p(y_ptrs[0]), C.c_void_p(y_ptrs[1]), int(ldo), int(plane_dtype), _stream()),
-               "avt_avgpool2_x3")
+    K.avt_avgpool2_x3(C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]), int(b), int(h), int(w), int(c), int(ldi), C.c_void_p(y_ptrs[0]),
+                      C.c_void_p(y_ptrs[1]), int(ldo), int(plane_dtype), _stream())
 
 
 def upsample2_bilinear_x3(x_ptrs, dims, c, ldi, y_ptrs, ldo, plane_dtype):
     b, h, w = dims
-    _lib.check(_lib.lib().avt_upsample2_bilinear_x3(C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]), int(b), int(h), int(w), int(c),
-                                                    int(ldi), C.c_void_p(y_ptrs[0]), C.c_void_p(y_ptrs[1]), int(ldo), int(plane_dtype),
-                                                    _stream()), "avt_upsample2_bilinear_x3")
+    K.avt_upsample2_bilinear_x3(C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]), int(b), int(h), int(w), int(c), int(ldi),
+                                C.c_void_p(y_ptrs[0]), C.c_void_p(y_ptrs[1]), int(ldo), int(plane_dtype), _stream())
 
 
 def interp_mid_input(img, flow_ptrs, h, w, sf, x_ptrs, ft, plane_dtype):
     _dev(img, "img", torch.float32)
     _dev(ft, "ft", torch.float32)
-    _lib.check(_lib.lib().avt_interp_mid_input(_p(img), C.c_void_p(flow_ptrs[0]), C.c_void_p(flow_ptrs[1]), int(h), int(w), int(sf),
-                                               C.c_void_p(x_ptrs[0]), C.c_void_p(x_ptrs[1]), _p(ft), int(plane_dtype), _stream()),
-               "avt_interp_mid_input")
+    K.avt_interp_mid_input(_p(img), C.c_void_p(flow_ptrs[0]), C.c_void_p(flow_ptrs[1]), int(h), int(w), int(sf), C.c_void_p(x_ptrs[0]),
+                           C.c_void_p(x_ptrs[1]), _p(ft), int(plane_dtype), _stream())
 
 
 def interp_final(img, ft, o_ptrs, h, w, sf, mean, out, plane_dtype):
     _dev(img, "img", torch.float32)
     _dev(ft, "ft", torch.float32)
     _dev(out, "out", torch.uint8)
-    _lib.check(_lib.lib().avt_interp_final_u8(_p(img), _p(ft), C.c_void_p(o_ptrs[0]), C.c_void_p(o_ptrs[1]), int(h), int(w), int(sf),
-                                              _mean3(mean), _p(out), int(plane_dtype), _stream()), "avt_interp_final_u8")
+    K.avt_interp_final_u8(_p(img), _p(ft), C.c_void_p(o_ptrs[0]), C.c_void_p(o_ptrs[1]), int(h), int(w), int(sf), _mean3(mean), _p(out),
+                          int(plane_dtype), _stream())
 
 
 # ---------------------------------------------------------------- Pillow's 8-bit resize on the device (csrc/resize_u8.hip)
@@ -1235,8 +1156,7 @@ def resize_u8_tables(in_size, out_size, filt):
     if ksize < 0:  # (a status, not a tap count)
         _lib.check(ksize, "avt_resize_u8_ksize")
     k, bounds = np.empty((int(out_size), ksize), np.int32), np.empty((int(out_size), 2), np.int32)
-    _lib.check(_lib.lib().avt_resize_u8_tables(int(in_size), int(out_size), int(filt), ksize, k.ctypes.data, bounds.ctypes.data),
-               "avt_resize_u8_tables")
+    K.avt_resize_u8_tables(int(in_size), int(out_size), int(filt), ksize, k.ctypes.data, bounds.ctypes.data)
     return k, bounds
 
 
@@ -1270,6 +1190,5 @@ def resize_u8(frames, size, filter):
     if nx and ny:
         tmp = torch.empty((b, h, ow, 3), dtype=torch.uint8, device=frames.device)
     out = torch.empty((b, max(oh, 0), max(ow, 0), 3), dtype=torch.uint8, device=frames.device)
-    _lib.check(_lib.lib().avt_resize_u8(_p(frames), _p(tmp), _p(out), b, h, w, oh, ow, c, _p(kx), _p(bx), nx, _p(ky), _p(by), ny, _stream()),
-               "avt_resize_u8")
+    K.avt_resize_u8(_p(frames), _p(tmp), _p(out), b, h, w, oh, ow, c, _p(kx), _p(bx), nx, _p(ky), _p(by), ny, _stream())
     return out

@@ -31,7 +31,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib, ops
-from .ops import _RAW_STREAM, _p, _stream
+from .ops import _RAW_STREAM, K, _p, _stream
 
 # Which passes of the training step run on the hand-written kernels.  Module constants (no environment switches since round 4);
 # `set_conv_mode` (main.py --train_conv) is the user-facing switch, tests set some of these to 0 for the stock-op reference path.
@@ -250,16 +250,14 @@ class _BNAct(torch.autograd.Function):
         if pre is not None:  # (workspace, rows of partials per group): the producing convolution's epilogue has summed the rows
             ws, pre_rows = pre
             CALLS["bn_fwd_pre"] += 1
-            _lib.check(_lib.lib().avt_bn_train_fwd_pre(_p(x), _p(res), _p(y), m, c, _p(weight), _p(bias), float(eps), float(momentum),
-                                                       1 if relu else 0, groups, _p(ws), ws.numel(), _p(save_mean), _p(save_invstd),
-                                                       _p(running_mean), _p(running_var), _p(tracked), _p(mask), ldy, int(pre_rows),
-                                                       _stream()), "avt_bn_train_fwd_pre")
+            K.avt_bn_train_fwd_pre(_p(x), _p(res), _p(y), m, c, _p(weight), _p(bias), float(eps), float(momentum), 1 if relu else 0,
+                                   groups, _p(ws), ws.numel(), _p(save_mean), _p(save_invstd), _p(running_mean), _p(running_var),
+                                   _p(tracked), _p(mask), ldy, int(pre_rows), _stream())
         else:
             ws = _workspace(m, c, groups, x.device)
-            _lib.check(_lib.lib().avt_bn_train_fwd(_p(x), _p(res), _p(y), m, c, _p(weight), _p(bias), float(eps), float(momentum),
-                                                   1 if relu else 0, groups, _p(ws), ws.numel(), _p(save_mean), _p(save_invstd),
-                                                   _p(running_mean), _p(running_var), _p(tracked), _p(mask), ldy, _stream()),
-                       "avt_bn_train_fwd")
+            K.avt_bn_train_fwd(_p(x), _p(res), _p(y), m, c, _p(weight), _p(bias), float(eps), float(momentum), 1 if relu else 0, groups,
+                               _p(ws), ws.numel(), _p(save_mean), _p(save_invstd), _p(running_mean), _p(running_var), _p(tracked),
+                               _p(mask), ldy, _stream())
         ctx.save_for_backward(x, mask, weight, bias, save_mean, save_invstd)
         ctx.has_res = res is not None
         ctx.relu = bool(relu)
@@ -290,9 +288,8 @@ class _BNAct(torch.autograd.Function):
             dbeta = torch.empty(c, dtype=torch.float32, device=x.device)
             CALLS["bn_bwd"] += 1
             CALLS["bn_bwd_pre"] += 1
-            _lib.check(_lib.lib().avt_bn_train_bwd_pre(_p(dy), _p(x), m, c, _p(weight), _p(save_mean), _p(save_invstd), ctx.groups,
-                                                       _p(pre[0]), pre[0].numel(), int(pre[1]), _p(dx), _p(dgamma), _p(dbeta), _stream()),
-                       "avt_bn_train_bwd_pre")
+            K.avt_bn_train_bwd_pre(_p(dy), _p(x), m, c, _p(weight), _p(save_mean), _p(save_invstd), ctx.groups, _p(pre[0]),
+                                   pre[0].numel(), int(pre[1]), _p(dx), _p(dgamma), _p(dbeta), _stream())
             return dx, dgamma, dbeta, None, None, (dy if ctx.has_res else None), None, None, None, None, None, None, None
         ld_dy = _row_ld(dy)  # a slice of a concatenation's gradient is read in place (rows with a pitch)
         if ld_dy is None:
@@ -303,9 +300,8 @@ class _BNAct(torch.autograd.Function):
         dgamma = torch.empty(c, dtype=torch.float32, device=x.device)
         dbeta = torch.empty(c, dtype=torch.float32, device=x.device)
         CALLS["bn_bwd"] += 1
-        _lib.check(_lib.lib().avt_bn_train_bwd(_p(dy), None, _p(x), m, c, _p(weight), _p(bias), _p(save_mean), _p(save_invstd),
-                                               1 if ctx.relu else 0, ctx.groups, _p(mask), _p(ws), ws.numel(), _p(dx), _p(dres),
-                                               _p(dgamma), _p(dbeta), ld_dy, _stream()), "avt_bn_train_bwd")
+        K.avt_bn_train_bwd(_p(dy), None, _p(x), m, c, _p(weight), _p(bias), _p(save_mean), _p(save_invstd), 1 if ctx.relu else 0,
+                           ctx.groups, _p(mask), _p(ws), ws.numel(), _p(dx), _p(dres), _p(dgamma), _p(dbeta), ld_dy, _stream())
         return dx, dgamma, dbeta, None, None, dres, None, None, None, None, None, None, None
 
 
@@ -1624,7 +1620,7 @@ class _MaxPoolHW(torch.autograd.Function):
             y, ldy = _alias(cat[0], cat[1], c), cat[0].shape[1]
         tap = torch.empty(y.numel() // 2, dtype=torch.uint8, device=x.device)
         CALLS["maxpool_hip"] += 1
-        _lib.check(_lib.lib().avt_maxpool_train_fwd(_p(x), _p(y), _p(tap), b * t, h, w, c, ldy, _stream()), "avt_maxpool_train_fwd")
+        K.avt_maxpool_train_fwd(_p(x), _p(y), _p(tap), b * t, h, w, c, ldy, _stream())
         ctx.save_for_backward(tap)
         ctx.dims = (b, c, t, h, w)
         return y
@@ -1637,7 +1633,7 @@ class _MaxPoolHW(torch.autograd.Function):
         if ld_dy is None:
             dy, ld_dy = dy.contiguous(memory_format=torch.channels_last_3d), c
         dx = torch.empty((b, c, t, h, w), dtype=torch.float32, device=dy.device, memory_format=torch.channels_last_3d)
-        _lib.check(_lib.lib().avt_maxpool_train_bwd(_p(dy), _p(tap), _p(dx), b * t, h, w, c, ld_dy, _stream()), "avt_maxpool_train_bwd")
+        K.avt_maxpool_train_bwd(_p(dy), _p(tap), _p(dx), b * t, h, w, c, ld_dy, _stream())
         return dx, None
 
 
@@ -1669,7 +1665,7 @@ class _MaxPool3d(torch.autograd.Function):
         y = torch.empty((b, c, to, ho, wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last_3d)
         tap = torch.empty(y.numel(), dtype=torch.uint8, device=x.device)
         CALLS["maxpool3d_hip"] += 1
-        _lib.check(_lib.lib().avt_maxpool3d_train_fwd(_p(x), _p(y), _p(tap), b, t, h, w, c, 0, _stream()), "avt_maxpool3d_train_fwd")
+        K.avt_maxpool3d_train_fwd(_p(x), _p(y), _p(tap), b, t, h, w, c, 0, _stream())
         ctx.save_for_backward(tap)
         ctx.dims = (b, c, t, h, w)
         return y
@@ -1682,7 +1678,7 @@ class _MaxPool3d(torch.autograd.Function):
         if ld_dy is None:
             dy, ld_dy = dy.contiguous(memory_format=torch.channels_last_3d), c
         dx = torch.empty((b, c, t, h, w), dtype=torch.float32, device=dy.device, memory_format=torch.channels_last_3d)
-        _lib.check(_lib.lib().avt_maxpool3d_train_bwd(_p(dy), _p(tap), _p(dx), b, t, h, w, c, ld_dy, _stream()), "avt_maxpool3d_train_bwd")
+        K.avt_maxpool3d_train_bwd(_p(dy), _p(tap), _p(dx), b, t, h, w, c, ld_dy, _stream())
         return dx
 
 

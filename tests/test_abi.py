@@ -1,5 +1,5 @@
 """The C-ABI library loads on a box without a GPU and exports every symbol include/avt.h declares; the ctypes
-binding table covers the header one to one; host-only entry points behave.  No device calls here."""
+binding table is parsed from the header and covers it one to one; host-only entry points behave.  No device calls here."""
 import ctypes
 import os
 import re
@@ -23,6 +23,71 @@ def test_library_exports_every_declared_symbol(avt):
         assert hasattr(handle, n), "libavt_hip.so does not export %s" % n
     assert sorted(list(avt._lib.SIGNATURES) + ["avt_last_error"]) == names
     assert avt._lib.lib().avt_abi_version() == avt._lib.ABI_VERSION == 8
+
+
+def test_parsed_signatures_of_each_declaration_shape(avt):
+    """The ctypes table is parse_header(include/avt.h): one entry pinned for every shape of declaration the parser has to read."""
+    C = ctypes
+    i, i64, vp = C.c_int, C.c_int64, C.c_void_p
+    with open(avt._lib.HEADER_PATH) as f:
+        table = avt._lib.parse_header(f.read())
+    assert len(table) == 122
+    assert table["avt_device_check"] == (i, [C.c_char_p, C.c_size_t])
+    assert table["avt_logmel_f64"] == (i, [vp, i, i64, vp, i, i, i, vp, i, C.c_double, vp, vp])
+    assert table["avt_pw_x3_f32"] == (i, [vp, i, i, vp, vp, vp, vp, i, vp, i, i, i64, i, vp])  # int64_t m: the 12th argument
+    assert table["avt_weight_planes_t_f32"] == (i, [vp, i, i, i, vp, i, vp, vp, vp])  # const int32_t* sel: a host array
+    assert table["avt_frames_resize_aa_norm_u8"] == (i, [vp, i, i, i, i, vp, vp, vp, vp])  # const float* mean / std: host arrays
+    assert table["avt_abi_version"] == (i, [])
+    assert table["avt_bn_train_ws_bytes_pre"] == (i64, [i, i, i])
+    assert table["avt_last_error"] == (C.c_char_p, [])
+    assert {n: a for n, (_, a) in table.items() if n != "avt_last_error"} == avt._lib.SIGNATURES
+    fn = avt._lib.lib().avt_pw_x3_f32
+    assert (fn.restype, list(fn.argtypes)) == table["avt_pw_x3_f32"]
+    assert avt._lib.lib().avt_bn_train_ws_bytes_pre.restype is i64 and avt._lib.lib().avt_last_error.restype is C.c_char_p
+
+
+@pytest.mark.parametrize("text", [
+    "int avt_x(unsigned long n);",                            # a scalar outside the ABI's vocabulary
+    "int avt_x(int n, long m);",
+    "int avt_x(const float* x, int (*done)(int), void* stream);",  # a function pointer
+    "int avt_a(int n), avt_b(int m);",                        # two declarators: the strict pattern reads neither
+    "int avt_a(int n);\nvoid avt_b(int n);",                  # a return type outside the ABI's: avt_b is seen, not read
+    "int avt_a(int n);\nint avt_b(int n)\n/* ; */ { return n; }",  # no terminating semicolon
+], ids=["unsigned-long", "long", "function-pointer", "two-declarators", "void-return", "no-semicolon"])
+def test_parser_refuses_what_it_cannot_read(avt, text):
+    with pytest.raises(avt._lib.AvtError):
+        avt._lib.parse_header(text)
+
+
+def test_parser_reads_arrays_and_unnamed_parameters(avt):
+    C = ctypes
+    table = avt._lib.parse_header("#define AVT_X (1)\n/* avt_gone(int) */\nint64_t avt_y(const float mean[3], int, double* out,\n"
+                                  "              const char *name /* avt_z( */);")
+    assert table == {"avt_y": (C.c_int64, [C.c_void_p, C.c_int, C.c_void_p, C.c_char_p])}
+
+
+def test_checked_entries_raise_and_raw_entries_return_the_status(avt):
+    """_lib.checked.avt_X and _lib.lib().avt_X are two ctypes functions of one symbol: the first raises check()'s error under the
+    entry's own name, the second keeps returning the status.  Host-only entries: no device is touched."""
+    lib, checked = avt._lib.lib(), avt._lib.checked
+    k, b = np.zeros((32, 11), np.int32), np.zeros((32, 2), np.int32)
+    with pytest.raises(avt._lib.AvtError) as e:
+        checked.avt_resize_u8_tables(45, 32, 1, 9, k.ctypes.data, b.ctypes.data)  # Lanczos 45 -> 32 has 11 taps, not 9
+    assert lib.avt_resize_u8_tables(45, 32, 1, 9, k.ctypes.data, b.ctypes.data) == -1
+    message = lib.avt_last_error().decode()
+    assert "11 taps" in message and str(e.value) == "avt_resize_u8_tables failed (-1): " + message
+    with pytest.raises(avt._lib.AvtError) as e2:
+        avt._lib.check(-1, "avt_resize_u8_tables")
+    assert str(e2.value) == str(e.value)
+    assert lib.avt_resize_u8_tables.errcheck is not checked.avt_resize_u8_tables.errcheck
+    assert checked.avt_resize_u8_tables is checked.avt_resize_u8_tables and "avt_resize_u8_tables" in vars(checked)
+    assert list(checked.avt_resize_u8_tables.argtypes) == list(lib.avt_resize_u8_tables.argtypes)
+    with pytest.raises(AttributeError):
+        checked.avt_no_such_entry
+    fast, slow = np.full(32, -1, np.int32), np.full(8, -1, np.int32)
+    assert checked.avt_clip_sample_table(20, fast.ctypes.data, slow.ctypes.data) == 0
+    want_fast, want_slow = avt.ops.clip_sample_table(20)
+    assert np.array_equal(fast, want_fast) and np.array_equal(slow, want_slow)
 
 
 def test_plane_job_table_layout_matches_the_header(avt):
