@@ -459,25 +459,39 @@ def conv3d_igemm_x3(x_ptrs, wt_hi, wt_lo, bias, res_ptrs, out_ptrs, ktab, dims, 
        int(plane_dtype), _p(wscale), _stream())
 
 
+def _geom(dims, cin, cout, *triples):
+    """The integer run every avt_conv3d_igemm_x3_f32* entry takes after its pointers: b, t, h, w, cin, cout, then the (t, h, w) triples
+    in the entry's own order (kernel, stride, pad, output extent).  (One list and map(int): cheaper on the host than a conversion and a
+    list per field — these wrappers are called ~600 times in a launch-bound training step.)"""
+    run = [*dims, cin, cout]
+    for tr in triples:
+        run += tr
+    return map(int, run)
+
+
+def _stat_ws(rows, stat_c, groups, device):
+    """-> (ws, pre_rows): the BatchNorm workspace (avt_bn_train_fwd_pre / avt_bn_train_bwd_pre) that a convolution's epilogue heads with
+    its partial sums — `rows` rows of them per replica group, as the kernel's *_rows query answered, for stat_c channels."""
+    pre_rows = rows * max(1, int(stat_c) // 1024)
+    return torch.empty(_lib.lib().avt_bn_train_ws_bytes_pre(int(stat_c), int(groups), pre_rows), dtype=torch.uint8, device=device), pre_rows
+
+
 def conv3d_igemm_x3_f32(x, wt_hi, wt_lo, wscale, out, ktab, dims, cin, cout, kernel, stride, pad, ldi, ldo, plane_dtype, add=None):
     """fp32 rows in / fp32 rows out on the split-plane kernel (training forward / stride-1 dgrad); add = fp32 rows [M, cout]
     summed into the result; see include/avt.h."""
-    b, t, h, w = dims
     _dev(x, "x", torch.float32)
     _dev(out, "out", torch.float32)
     _dev(wt_hi, "wt_hi", torch.bfloat16)
     _dev(wt_lo, "wt_lo", torch.bfloat16)
     if add is not None:
         _dev(add, "add", torch.float32)
-    K.avt_conv3d_igemm_x3_f32(_p(x), _p(wt_hi), _p(wt_lo), _p(wscale), _p(add), _p(out), _p(ktab), int(b), int(t), int(h), int(w),
-                              int(cin), int(cout), *[int(k) for k in kernel], *[int(v) for v in stride], *[int(v) for v in pad],
+    K.avt_conv3d_igemm_x3_f32(_p(x), _p(wt_hi), _p(wt_lo), _p(wscale), _p(add), _p(out), _p(ktab), *_geom(dims, cin, cout, kernel, stride, pad),
                               int(ldi), int(ldo), int(cout), int(plane_dtype), _stream())
 
 
 def conv3d_igemm_x3_f32_stats(x, wt_hi, wt_lo, wscale, out, ktab, dims, cin, cout, kernel, stride, pad, ldi, ldo, plane_dtype, groups, stat_c):
     """conv3d_igemm_x3_f32 that also leaves the train-mode BatchNorm statistics of its output behind (include/avt.h): -> (ws, pre_rows),
     the BatchNorm workspace with the per-tile partial sums at its head, for avt_bn_train_fwd_pre."""
-    b, t, h, w = dims
     _dev(x, "x", torch.float32)
     _dev(out, "out", torch.float32)
     _dev(wt_hi, "wt_hi", torch.bfloat16)
@@ -487,11 +501,9 @@ def conv3d_igemm_x3_f32_stats(x, wt_hi, wt_lo, wscale, out, ktab, dims, cin, cou
     rows = _lib.lib().avt_conv3d_igemm_x3_f32_stat_rows(int(cout), k, int(m), int(groups))
     if rows <= 0:
         raise _lib.AvtError("conv3d_igemm_x3_f32_stats: %d rows do not split into %d groups" % (m, groups))
-    pre_rows = rows * max(1, int(stat_c) // 1024)
-    ws = torch.empty(_lib.lib().avt_bn_train_ws_bytes_pre(int(stat_c), int(groups), pre_rows), dtype=torch.uint8, device=x.device)
-    K.avt_conv3d_igemm_x3_f32_stats(_p(x), _p(wt_hi), _p(wt_lo), _p(wscale), _p(out), _p(ktab), int(b), int(t), int(h), int(w), int(cin),
-                                    int(cout), *[int(v) for v in kernel], *[int(v) for v in stride], *[int(v) for v in pad], int(ldi),
-                                    int(ldo), int(plane_dtype), _p(ws), int(groups), int(stat_c), _stream())
+    ws, pre_rows = _stat_ws(rows, stat_c, groups, x.device)
+    K.avt_conv3d_igemm_x3_f32_stats(_p(x), _p(wt_hi), _p(wt_lo), _p(wscale), _p(out), _p(ktab), *_geom(dims, cin, cout, kernel, stride, pad),
+                                    int(ldi), int(ldo), int(plane_dtype), _p(ws), int(groups), int(stat_c), _stream())
     return ws, pre_rows
 
 
@@ -518,7 +530,6 @@ def conv3d_igemm_x3_f32_bwdstats(dy, wt_hi, wt_lo, out, ktab, dims, cin, cout, k
     gradient of a train-mode BatchNorm: out = mask * (conv + add), and the BatchNorm's backward statistics as per-tile partials
     (include/avt.h).  bn = (x, save_mean, save_invstd, gamma, beta | None, mask | None, relu).  -> (ws, pre_rows) for
     avt_bn_train_bwd_pre, or None where the kernel does not apply (the 256 x 256 tile's layers): nothing was launched."""
-    b, t, h, w = dims
     _dev(dy, "dy", torch.float32)
     _dev(out, "out", torch.float32)
     k = int(kernel[0]) * int(kernel[1]) * int(kernel[2]) * int(cin)
@@ -527,12 +538,10 @@ def conv3d_igemm_x3_f32_bwdstats(dy, wt_hi, wt_lo, out, ktab, dims, cin, cout, k
     if rows <= 0:
         return None
     bx, mean, invstd, gamma, beta, mask, relu = bn
-    pre_rows = rows * max(1, int(stat_c) // 1024)
-    ws = torch.empty(_lib.lib().avt_bn_train_ws_bytes_pre(int(stat_c), int(groups), pre_rows), dtype=torch.uint8, device=dy.device)
+    ws, pre_rows = _stat_ws(rows, stat_c, groups, dy.device)
     K.avt_conv3d_igemm_x3_f32_bwdstats(
-        _p(dy), _p(wt_hi), _p(wt_lo), None, _p(add), _p(out), _p(ktab), int(b), int(t), int(h), int(w), int(cin), int(cout),
-        *[int(v) for v in kernel], *[int(v) for v in pad], int(cin), int(cout), int(cout), int(plane_dtype), _p(bx), _p(mean), _p(invstd),
-        _p(gamma), _p(beta), _p(mask), int(relu), _p(ws), int(groups), int(stat_c), _stream())
+        _p(dy), _p(wt_hi), _p(wt_lo), None, _p(add), _p(out), _p(ktab), *_geom(dims, cin, cout, kernel, pad), int(cin), int(cout), int(cout),
+        int(plane_dtype), _p(bx), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(mask), int(relu), _p(ws), int(groups), int(stat_c), _stream())
     return ws, pre_rows
 
 
@@ -546,8 +555,7 @@ def pw_x3_f32_bwdstats(dy, k, wt_hi, wt_lo, out, n, plane_dtype, bn, groups, add
     if rows <= 0 or plane_dtype != X3_BF16:
         return None
     bx, mean, invstd, gamma, beta, mask, relu = bn
-    pre_rows = rows * max(1, int(n) // 1024)
-    ws = torch.empty(_lib.lib().avt_bn_train_ws_bytes_pre(int(n), int(groups), pre_rows), dtype=torch.uint8, device=dy.device)
+    ws, pre_rows = _stat_ws(rows, n, groups, dy.device)
     K.avt_pw_x3_f32_bwdstats(_p(dy), int(k), int(k), _p(wt_hi), _p(wt_lo), _p(add), int(n), _p(out), int(n), int(n), int(m),
                              int(plane_dtype), _p(bx), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(mask), 1 if relu else 0, _p(ws),
                              int(groups), _stream())
@@ -565,8 +573,7 @@ def pw_x3_f32_stats(x, k, wt_hi, wt_lo, wscale, out, n, plane_dtype, groups):
     rows = _lib.lib().avt_pw_x3_f32_stat_rows(int(k), int(n), int(m), int(groups))
     if rows <= 0 or n & (n - 1):
         return None
-    pre_rows = rows * max(1, int(n) // 1024)
-    ws = torch.empty(_lib.lib().avt_bn_train_ws_bytes_pre(int(n), int(groups), pre_rows), dtype=torch.uint8, device=x.device)
+    ws, pre_rows = _stat_ws(rows, n, groups, x.device)
     K.avt_pw_x3_f32_stats(_p(x), int(k), int(k), _p(wt_hi), _p(wt_lo), _p(wscale), _p(out), int(n), int(n), int(m), int(plane_dtype),
                           _p(ws), int(groups), _stream())
     return ws, pre_rows
@@ -576,14 +583,12 @@ def conv3d_igemm_x3_f32_ex(x, wt_hi, wt_lo, wscale, out, ktab, dims, cin, cout, 
                            out_rows=(1, 0, 0)):
     """conv3d_igemm_x3_f32 at stride 1 with an explicit output extent and the output-row remap (out_rows = (stride, grid h, grid w));
     `out` is the first element the class writes (a view into the full gradient); see include/avt.h."""
-    b, t, h, w = dims
     _dev(x, "x", torch.float32)
     _dev(wt_hi, "wt_hi", torch.bfloat16)
     _dev(wt_lo, "wt_lo", torch.bfloat16)
-    K.avt_conv3d_igemm_x3_f32_ex(_p(x), _p(wt_hi), _p(wt_lo), _p(wscale), C.c_void_p(out.data_ptr()), _p(ktab), int(b), int(t), int(h),
-                                 int(w), int(cin), int(cout), *[int(k) for k in kernel], *[int(v) for v in pad],
-                                 *[int(v) for v in out_dims], int(ldi), int(ldo), int(out_rows[0]), int(out_rows[1]), int(out_rows[2]),
-                                 int(plane_dtype), _stream())
+    K.avt_conv3d_igemm_x3_f32_ex(_p(x), _p(wt_hi), _p(wt_lo), _p(wscale), C.c_void_p(out.data_ptr()), _p(ktab),
+                                 *_geom(dims, cin, cout, kernel, pad, out_dims), int(ldi), int(ldo), *[int(v) for v in out_rows], int(plane_dtype),
+                                 _stream())
 
 
 def weight_planes_f32(w2d, plane_dtype):

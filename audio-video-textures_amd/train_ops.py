@@ -1113,10 +1113,19 @@ _PW_F32 = 1         # pointwise layers (forward / stride-1 input gradient) on th
 _GROUP_IDX = {}
 
 
-def _group_factor(cin, cout, kernel, stride, pad, w):
+_PW_FORM = 0  # _conv_form's answer for the streaming pointwise kernel (1: the general tile, g > 1: g pixels grouped)
+
+
+def _conv_form(cin, cout, kernel, stride, pad, w):
+    """The form a convolution of rows [.., cin] -> [.., cout] runs in — the one place that decides it, asked once per convolution and
+    direction: _PW_FORM = the streaming pointwise kernel takes the layer as it is, g > 1 = g adjacent pixels along W grouped into
+    g * C channels, 1 = the general tile."""
     if _PW_F32 and tuple(kernel) == (1, 1, 1) and tuple(stride) == (1, 1, 1) and tuple(pad) == (0, 0, 0):
+        # (the kernel's 32-bit row count, rows < 2^31 - 16, needs no check of its own: every caller holds a tensor with at least as
+        #  many ELEMENTS as these rows below 2^30 - 64 — conv_fusable and conv2d the input, of which a stem's zero-padded 8-channel
+        #  copy has one row per position; _conv_dgrad the output gradient)
         if ops.pw_x3_f32_supported(cin, cout):
-            return 1  # (a pointwise layer the streaming kernel takes as it is: _conv_x3_rows)
+            return _PW_FORM
     if not _GROUP or tuple(stride) != (1, 1, 1) or pad[2] != kernel[2] // 2 or kernel[2] % 2 == 0 or cin % 8 or cout % 8:
         return 1
     small = min(cin, cout)
@@ -1188,6 +1197,19 @@ def _grouped_planes(weight, g, transposed, plane_dtype):
     return planes
 
 
+def _conv_planes(weight, transposed, cin, cout, kernel, stride, pad, w):
+    """The weight planes of one direction of a convolution of rows [.., cin] -> [.., cout] of width w, in the form it runs in
+    (_conv_form) — forward: fp16 planes; transposed, the input gradient as a convolution of dY: bf16 planes of the flipped filter.
+    -> planes, form: (g, grouped kernel, rg) for the pixel-grouped form, _PW_FORM for the streaming pointwise kernel, None for the
+    general tile: what _conv_x3_rows takes."""
+    g = _conv_form(cin, cout, kernel, stride, pad, w)
+    # (grouped planes are a gather of the weight itself: a stem's zero-padded 8-channel rows keep the plain planes, padded to match)
+    if g > 1 and cin == weight.shape[0 if transposed else 1]:
+        planes, gk, rg = _grouped_planes(weight, g, transposed, ops.X3_BF16 if transposed else ops.X3_F16)
+        return planes, (g, gk, rg)
+    return _weight_planes(weight, transposed), (_PW_FORM if g == _PW_FORM else None)
+
+
 _STAT_GROUP_COLS = 128  # widest pixel-grouped output (g * cout columns) whose BatchNorm statistics ride on the epilogue: the copies of
 #                         a channel must share one N tile (csrc/conv_args.h stat_fold_store; conv_x3.hip rejects wider forms)
 _LAST_STATS = None  # (output data_ptr, workspace, rows of partials per group, groups, channels) of the last convolution that left
@@ -1198,76 +1220,61 @@ def _bwd_bn_args(h):
     return (h.x, h.mean, h.invstd, h.weight, None if h.mask is not None else h.bias, h.mask, h.relu)
 
 
-def _conv_x3_rows(x, planes, plane_dtype, cin, cout, kernel, stride, pad, add=None, group=None, stats=0, bwd_bn=None):
+def _conv_x3_rows(x, planes, plane_dtype, cin, cout, kernel, stride, pad, add=None, form=None, stats=0, bwd_bn=None):
     """x [B, Cin, T, H, W] channels-last fp32 -> [B, Cout, To, Ho, Wo] channels-last fp32 (+ add, same shape, in the epilogue).
+    planes, form: of _conv_planes.
     stats = n > 0: the output feeds a train-mode BatchNorm of n replica groups — the kernel's epilogue leaves its statistics'
-    partial sums (ops.conv3d_igemm_x3_f32_stats / ops.pw_x3_f32_stats; recorded in _LAST_STATS)."""
+    partial sums (ops.conv3d_igemm_x3_f32_stats / ops.pw_x3_f32_stats; recorded in _LAST_STATS).
+    bwd_bn = a _BnHandle: x is an output gradient and the result the output gradient of that BatchNorm — masked on the way out, the
+    BatchNorm's backward statistics summed in the epilogue (ops.conv3d_igemm_x3_f32_bwdstats / ops.pw_x3_f32_bwdstats; recorded in
+    _BWD_STATS)."""
     global _LAST_STATS
     b, _, t, h, w = x.shape
     od = [(n + 2 * p - k) // s_ + 1 for n, p, k, s_ in zip((t, h, w), pad, kernel, stride)]
     y = torch.empty((b, cout, od[0], od[1], od[2]), dtype=torch.float32, device=x.device, memory_format=torch.channels_last_3d)
     stats = int(stats) if (stats and add is None and (cout & (cout - 1)) == 0 and cout >= 8 and b % int(stats) == 0) else 0
-    if bwd_bn is not None:
-        # an input gradient that is the output gradient of the BatchNorm `bwd_bn` (a _BnHandle): masked on the way out, that
-        # BatchNorm's backward statistics summed in the epilogue (ops.conv3d_igemm_x3_f32_bwdstats / ops.pw_x3_f32_bwdstats; the
-        # 256 x 256 tile does not: st is None, the plain launch below runs)
-        st = None
-        addr = None if add is None else add.permute(0, 2, 3, 4, 1)
-        if group is not None:
-            g, gk, rg = group
-            # (pixel-grouped statistics fold a channel's pixel copies inside ONE N tile of <= 128 columns: wider forms keep the pass)
-            st = None if g * cout > _STAT_GROUP_COLS else ops.conv3d_igemm_x3_f32_bwdstats(x.permute(0, 2, 3, 4, 1), planes[0], planes[1], y.permute(0, 2, 3, 4, 1),
-                                                  _ktab(g * cin, gk, h, w // g, g * cin, x.device), (b, t, h, w // g), g * cin, g * cout, gk,
-                                                  (pad[0], pad[1], rg), plane_dtype, _bwd_bn_args(bwd_bn), bwd_bn.groups, cout, add=addr)
-        elif (_PW_F32 and tuple(kernel) == (1, 1, 1) and tuple(pad) == (0, 0, 0) and x.numel() // cin < (1 << 31) - 16 and
-              ops.pw_x3_f32_supported(cin, cout)):
-            st = ops.pw_x3_f32_bwdstats(x.permute(0, 2, 3, 4, 1), cin, planes[0], planes[1], y.permute(0, 2, 3, 4, 1), cout, plane_dtype,
-                                        _bwd_bn_args(bwd_bn), bwd_bn.groups, add=addr)
-            if st is not None:
-                CALLS["pw_f32"] += 1
+    # ---- the form: the rows the kernel sees, and whether statistics can ride on its epilogue
+    xr, yr, addr = x.permute(0, 2, 3, 4, 1), y.permute(0, 2, 3, 4, 1), None if add is None else add.permute(0, 2, 3, 4, 1)
+    pw = form == _PW_FORM
+    if pw:
+        # the pointwise layers with few K-steps and many outputs (the bottlenecks' expanding convolutions, the input gradients of the
+        # reducing ones) on the streaming kernel: the 128 x 128 tile spent 55 % of a workgroup in its prologue + epilogue on them
+        CALLS["pw_f32"] += 1  # (whichever epilogue it ends on: each of the three is a launch of csrc/pw_x3.hip)
+        rides = True
+    else:
+        # pixel-grouped (g, grouped kernel, rg): the same memory as [.., w / g, g * C] rows, block-Toeplitz planes (stride 1 only:
+        # _conv_form); the general tile is g = 1.  Grouped statistics fold a channel's pixel copies inside ONE N tile of <= 128 columns:
+        # wider forms keep the BatchNorm's own pass
+        g, kern, pad_e = (1, kernel, pad) if form is None else (form[0], form[1], (pad[0], pad[1], form[2]))
+        wg, cin_e, cout_e = w // g, g * cin, g * cout
+        dims, tab = (b, t, h, wg), _ktab(cin_e, kern, h, wg, cin_e, x.device)
+        rides = g == 1 or cout_e <= _STAT_GROUP_COLS
+    # ---- the epilogue: backward statistics, else forward statistics, else none (+ add); an attempt may decline (None: nothing was
+    # launched — the 256 x 256 tile's layers and group counts outside a kernel's domain), and the next one runs
+    if bwd_bn is not None and rides:
+        if pw:
+            st = ops.pw_x3_f32_bwdstats(xr, cin, planes[0], planes[1], yr, cout, plane_dtype, _bwd_bn_args(bwd_bn), bwd_bn.groups, add=addr)
         else:
-            st = ops.conv3d_igemm_x3_f32_bwdstats(x.permute(0, 2, 3, 4, 1), planes[0], planes[1], y.permute(0, 2, 3, 4, 1),
-                                                  _ktab(cin, kernel, h, w, cin, x.device), (b, t, h, w), cin, cout, kernel, pad, plane_dtype,
+            st = ops.conv3d_igemm_x3_f32_bwdstats(xr, planes[0], planes[1], yr, tab, dims, cin_e, cout_e, kern, pad_e, plane_dtype,
                                                   _bwd_bn_args(bwd_bn), bwd_bn.groups, cout, add=addr)
         if st is not None:
             CALLS["dgrad_bwdstats"] += 1
             _BWD_STATS[y.data_ptr()] = (st[0], st[1], bwd_bn, y._version)
             return y
-    if group is not None:  # (g, grouped kernel, rg): the same memory as [.., w / g, g * C] rows, block-Toeplitz planes
-        g, gk, rg = group
-        if stats and g * cout <= _STAT_GROUP_COLS:
-            ws, pre_rows = ops.conv3d_igemm_x3_f32_stats(x.permute(0, 2, 3, 4, 1), planes[0], planes[1], planes[2], y.permute(0, 2, 3, 4, 1),
-                                                         _ktab(g * cin, gk, h, w // g, g * cin, x.device), (b, t, h, w // g), g * cin, g * cout,
-                                                         gk, (1, 1, 1), (pad[0], pad[1], rg), g * cin, g * cout, plane_dtype, stats, cout)
-            _LAST_STATS = (y.data_ptr(), ws, pre_rows, stats, cout)
+    if stats and rides:
+        if pw:
+            st = ops.pw_x3_f32_stats(xr, cin, planes[0], planes[1], planes[2], yr, cout, plane_dtype, stats)
+        else:
+            st = ops.conv3d_igemm_x3_f32_stats(xr, planes[0], planes[1], planes[2], yr, tab, dims, cin_e, cout_e, kern, stride, pad_e,
+                                               cin_e, cout_e, plane_dtype, stats, cout)
+        if st is not None:
+            _LAST_STATS = (y.data_ptr(), st[0], st[1], stats, cout)
             return y
-        ops.conv3d_igemm_x3_f32(x.permute(0, 2, 3, 4, 1), planes[0], planes[1], planes[2], y.permute(0, 2, 3, 4, 1),
-                                _ktab(g * cin, gk, h, w // g, g * cin, x.device), (b, t, h, w // g), g * cin, g * cout, gk, (1, 1, 1),
-                                (pad[0], pad[1], rg), g * cin, g * cout, plane_dtype, add=None if add is None else add.permute(0, 2, 3, 4, 1))
-        return y
-    if (_PW_F32 and tuple(kernel) == (1, 1, 1) and tuple(stride) == (1, 1, 1) and tuple(pad) == (0, 0, 0) and x.numel() // cin < (1 << 31) - 16 and
-            ops.pw_x3_f32_supported(cin, cout)):
-        # the pointwise layers with few K-steps and many outputs (the bottlenecks' expanding convolutions, the input gradients of the
-        # reducing ones) on the streaming kernel: the 128 x 128 tile spent 55 % of a workgroup in its prologue + epilogue on them
-        CALLS["pw_f32"] += 1
-        if stats:
-            st = ops.pw_x3_f32_stats(x.permute(0, 2, 3, 4, 1), cin, planes[0], planes[1], planes[2], y.permute(0, 2, 3, 4, 1), cout,
-                                     plane_dtype, stats)
-            if st is not None:
-                _LAST_STATS = (y.data_ptr(), st[0], st[1], stats, cout)
-                return y
-        ops.pw_x3_f32(x.permute(0, 2, 3, 4, 1), cin, planes[0], planes[1], planes[2], y.permute(0, 2, 3, 4, 1), cout, plane_dtype,
-                      add=None if add is None else add.permute(0, 2, 3, 4, 1))
-        return y
-    if stats:
-        ws, pre_rows = ops.conv3d_igemm_x3_f32_stats(x.permute(0, 2, 3, 4, 1), planes[0], planes[1], planes[2], y.permute(0, 2, 3, 4, 1),
-                                                     _ktab(cin, kernel, h, w, cin, x.device), (b, t, h, w), cin, cout, kernel, stride, pad,
-                                                     cin, cout, plane_dtype, stats, cout)
-        _LAST_STATS = (y.data_ptr(), ws, pre_rows, stats, cout)
-        return y
-    ops.conv3d_igemm_x3_f32(x.permute(0, 2, 3, 4, 1), planes[0], planes[1], planes[2], y.permute(0, 2, 3, 4, 1),
-                            _ktab(cin, kernel, h, w, cin, x.device), (b, t, h, w), cin, cout, kernel, stride, pad, cin, cout, plane_dtype,
-                            add=None if add is None else add.permute(0, 2, 3, 4, 1))
+    if pw:
+        ops.pw_x3_f32(xr, cin, planes[0], planes[1], planes[2], yr, cout, plane_dtype, add=addr)
+    else:
+        ops.conv3d_igemm_x3_f32(xr, planes[0], planes[1], planes[2], yr, tab, dims, cin_e, cout_e, kern, stride, pad_e, cin_e, cout_e,
+                                plane_dtype, add=addr)
     return y
 
 
@@ -1295,11 +1302,8 @@ class _ConvX3(torch.autograd.Function):
         # (the stems keep the padded channels-last copy: their weight gradient reads it 4 channels at a time)
         ctx.save_for_backward(xin if (cin % 8 and (_STEM_WGRAD_X3 or cin != 3)) else x, weight)
         CALLS["conv_fwd_x3"] += 1
-        g = _group_factor(xin.shape[1], cout, kernel, stride, padding, xin.shape[4]) if xin is x else 1
-        if g > 1:
-            planes, gk, rg = _grouped_planes(weight, g, False, ops.X3_F16)
-            return _conv_x3_rows(xin, planes, ops.X3_F16, cin, cout, kernel, stride, padding, group=(g, gk, rg), stats=stats)
-        return _conv_x3_rows(xin, _weight_planes(weight, False), ops.X3_F16, xin.shape[1], cout, kernel, stride, padding, stats=stats)
+        planes, form = _conv_planes(weight, False, xin.shape[1], cout, kernel, stride, padding, xin.shape[4])
+        return _conv_x3_rows(xin, planes, ops.X3_F16, xin.shape[1], cout, kernel, stride, padding, form=form, stats=stats)
 
     @staticmethod
     def backward(ctx, dy):
@@ -1322,29 +1326,26 @@ def _conv_wgrad(ctx, dy, x, weight, stride, padding, kernel, cin, cout):
     """dW of the convolution (split-plane weight-gradient kernels; MIOpen for the shapes they do not cover)."""
     dw = None
     taps = kernel[0] * kernel[1] * kernel[2]
+    dims = (x.shape[0], x.shape[2], x.shape[3], x.shape[4])
+    xr, dyr = x.permute(0, 2, 3, 4, 1), dy.permute(0, 2, 3, 4, 1)  # (views: channels-last memory as rows)
     if (_WGRAD_X3 and cin % 8 == 0 and taps <= 28 and max(x.numel(), dy.numel()) < (1 << 31) - 64 and
             weight.is_contiguous(memory_format=torch.channels_last_3d)):
         CALLS["wgrad_x3"] += 1
-        dims = (x.shape[0], x.shape[2], x.shape[3], x.shape[4])
         flat = _ARENA.take(weight.numel(), weight.device) if _ARENA is not None else None
         if flat is not None:  # a zeroed slice of the micro-batch's gradient arena: no memset launch per convolution
             # (the weight's OWN strides, size-1 dimensions included: torch's multi-tensor optimizer kernels take their fast path only for
             #  gradients whose strides equal the parameters' — a permuted view differs in the stride of a one-tap dimension, and a
             #  foreach SGD then ran one launch per tensor: +4.8 ms on a 47 ms step, profiles/r06/train_one_item_arena_sgd_ab.log)
             dw = torch.as_strided(flat, tuple(weight.shape), tuple(weight.stride()))
-            ops.conv3d_wgrad_x3_sub_f32(dy.permute(0, 2, 3, 4, 1), x.permute(0, 2, 3, 4, 1), flat, dims, cin, cout, kernel, stride,
-                                        padding, (0, 0, 0), cin, cout, taps * cin, False)
+            ops.conv3d_wgrad_x3_sub_f32(dyr, xr, flat, dims, cin, cout, kernel, stride, padding, (0, 0, 0), cin, cout, taps * cin, False)
         else:
             dw = torch.empty_like(weight)  # channels-last strides: memory [cout][kt][kh][kw][cin], the kernel's order
-            ops.conv3d_wgrad_x3_f32(dy.permute(0, 2, 3, 4, 1), x.permute(0, 2, 3, 4, 1), dw.permute(0, 2, 3, 4, 1), dims, cin, cout,
-                                    kernel, stride, padding, cin, cout)
+            ops.conv3d_wgrad_x3_f32(dyr, xr, dw.permute(0, 2, 3, 4, 1), dims, cin, cout, kernel, stride, padding, cin, cout)
     elif (_WGRAD_X3 and cin % 8 and cin != 3 and x.shape[1] == 8 and taps <= 28 and max(x.numel(), dy.numel()) < (1 << 31) - 64):
         # a few-channel first layer (VGGish: 1 mel channel) on its zero-padded 8-channel copy; the padded taps' gradient is dropped
         CALLS["wgrad_x3"] += 1
-        dims = (x.shape[0], x.shape[2], x.shape[3], x.shape[4])
         dw8 = torch.empty((cout, 8) + tuple(kernel), dtype=torch.float32, device=dy.device, memory_format=torch.channels_last_3d)
-        ops.conv3d_wgrad_x3_f32(dy.permute(0, 2, 3, 4, 1), x.permute(0, 2, 3, 4, 1), dw8.permute(0, 2, 3, 4, 1), dims, 8, cout, kernel,
-                                stride, padding, 8, cout)
+        ops.conv3d_wgrad_x3_f32(dyr, xr, dw8.permute(0, 2, 3, 4, 1), dims, 8, cout, kernel, stride, padding, 8, cout)
         dw = torch.empty_like(weight)
         dw.copy_(dw8[:, :cin])
     elif (_WGRAD_X3 and _STEM_WGRAD_X3 and cin == 3 and x.shape[1] == 8 and kernel[1] * kernel[2] <= 49 and
@@ -1353,8 +1354,6 @@ def _conv_wgrad(ctx, dy, x, weight, stride, padding, kernel, cin, cout):
         # 49 taps, each a weight-gradient problem of its own with the temporal padding shifted by its frame tap
         kt, kh, kw = kernel
         acc = torch.zeros((cout, kt, kh * kw, 4), dtype=torch.float32, device=dy.device)
-        xr, dyr = x.permute(0, 2, 3, 4, 1), dy.permute(0, 2, 3, 4, 1)
-        dims = (x.shape[0], x.shape[2], x.shape[3], x.shape[4])
         for dt in range(kt):
             ops.conv3d_wgrad_x3_sub_f32(dyr, xr, acc[:, dt], dims, 4, cout, (1, kh, kw), stride, (padding[0] - dt, padding[1], padding[2]),
                                         (dy.shape[2], dy.shape[3], dy.shape[4]), 8, cout, kt * kh * kw * 4, False)
@@ -1382,13 +1381,8 @@ def _conv_dgrad(ctx, dy, dalias, x, weight, stride, padding, kernel, cin, cout):
             ctx.bn_in = None  # (the handle holds that BatchNorm's input and mask: not past this backward)
             if hb is not None and not (_EPI_BWD and hb.c == cin and tuple(hb.x.shape) == tuple(x.shape) and x.shape[0] % hb.groups == 0):
                 hb = None
-            g = _group_factor(cout, cin, kernel, (1, 1, 1), padding, dy.shape[4])
-            if g > 1:
-                planes, gk, rg = _grouped_planes(weight, g, True, ops.X3_BF16)
-                dx = _conv_x3_rows(dy, planes, ops.X3_BF16, cout, cin, kernel, (1, 1, 1), padding, add=dalias, group=(g, gk, rg), bwd_bn=hb)
-            else:
-                dx = _conv_x3_rows(dy, _weight_planes(weight, True), ops.X3_BF16, cout, cin, kernel, (1, 1, 1), padding, add=dalias,
-                                   bwd_bn=hb)
+            planes, form = _conv_planes(weight, True, cout, cin, kernel, (1, 1, 1), padding, dy.shape[4])
+            dx = _conv_x3_rows(dy, planes, ops.X3_BF16, cout, cin, kernel, (1, 1, 1), padding, add=dalias, form=form, bwd_bn=hb)
         else:
             dx = _dgrad_strided(dy, weight, stride, padding, kernel, tuple(x.shape)) if (_DGRAD_S_X3 and cin % 8 == 0) else None
             if dx is not None:
