@@ -1,7 +1,9 @@
-"""ctypes loader of the gfx950 C-ABI library (include/avt.h).
+"""ctypes loader of the gfx950 C-ABI library (include/avt.h, and the extension entries of include/avt_ext.h).
 
 The ABI is written down once, in the header: every csrc/*.hip includes it, so the compiler holds the definitions to it, and the
 ctypes table here is parsed from it (parse_header) — a declaration the parser cannot read is an error, never a default conversion.
+include/avt.h is the pinned table (SIGNATURES, ABI_VERSION); entries added since live in include/avt_ext.h, in the same grammar and
+read by the same parser (EXT_SIGNATURES, EXT_VERSION); lib() and `checked` bind and serve both.
 
 There is no CPU fallback: if libavt_hip.so is missing or a call fails, the
 product path raises.  Build it with `python -c "import __graft_entry__ as g; g.build()"`
@@ -15,6 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # AVT_HIP_LIB selects another build of the same ABI (the diagnostic libavt_hip_stamp.so of `make stamp`); default = the product
 LIB_PATH = os.environ.get("AVT_HIP_LIB") or os.path.join(_HERE, "libavt_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "avt.h")
+EXT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "avt_ext.h")
 
 
 class AvtError(RuntimeError):
@@ -55,12 +58,19 @@ with open(HEADER_PATH) as _f:
     _ABI = parse_header(_f.read())
 SIGNATURES = {name: argtypes for name, (_, argtypes) in _ABI.items() if name != "avt_last_error"}  # name -> argtypes
 ABI_VERSION = 8  # include/avt.h AVT_ABI_VERSION
+with open(EXT_HEADER_PATH) as _f:
+    _EXT_ABI = parse_header(_f.read())
+if set(_EXT_ABI) & set(_ABI):
+    raise AvtError("include/avt_ext.h declares again what include/avt.h declares: %s" % ", ".join(sorted(set(_EXT_ABI) & set(_ABI))))
+EXT_SIGNATURES = {name: argtypes for name, (_, argtypes) in _EXT_ABI.items()}  # name -> argtypes, the extension header's entries
+EXT_VERSION = 1  # include/avt_ext.h AVT_EXT_VERSION
+_ALL = dict(_ABI, **_EXT_ABI)
 
 _lib = None
 
 
 def _bind(fn):
-    fn.restype, fn.argtypes = _ABI[fn.__name__]
+    fn.restype, fn.argtypes = _ALL[fn.__name__]
     return fn
 
 
@@ -78,6 +88,14 @@ def lib():
         if handle.avt_abi_version() != ABI_VERSION:
             raise AvtError("libavt_hip.so ABI version %d, expected %d: rebuild with `make -C %s`"
                            % (handle.avt_abi_version(), ABI_VERSION, os.path.join(_HERE, "csrc")))
+        for name in _EXT_ABI:
+            if not hasattr(handle, name):
+                raise AvtError("libavt_hip.so does not export %s (include/avt_ext.h): rebuild with `make -C %s`"
+                               % (name, os.path.join(_HERE, "csrc")))
+            _bind(getattr(handle, name))
+        if handle.avt_ext_version() != EXT_VERSION:
+            raise AvtError("libavt_hip.so extension version %d, expected %d: rebuild with `make -C %s`"
+                           % (handle.avt_ext_version(), EXT_VERSION, os.path.join(_HERE, "csrc")))
         if os.environ.get("AVT_SMALL_TILE", "") == "0":  # (A/Bs: the training convolutions' 64-row tile at small batches off)
             handle.avt_conv_x3_set_small_tile(0)
         if os.environ.get("AVT_WGRAD_ROUNDS", "") == "0":  # (A/Bs: the weight gradient's round-aware split over positions off)
@@ -109,7 +127,7 @@ class _Checked:
     go through lib().  Each function is a ctypes object of its own, so lib()'s raw entries keep returning the status."""
 
     def __getattr__(self, name):  # (first use only: the function then sits in the instance's dict)
-        if name not in _ABI:
+        if name not in _ALL:
             raise AttributeError(name)
         fn = _bind(lib()[name])
         fn.errcheck = _errcheck

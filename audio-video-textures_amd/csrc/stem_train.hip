@@ -24,6 +24,7 @@
 // is read once per step and used by every (output row r, row tap dh) with 2 r + dh = j.
 // Roofline: MFMA (3 x the bf16 work; the padded columns 112 -> 128 and the sixth frame tap are issued work, not algorithmic).
 #include "avt_common.h"
+#include "../../include/avt_ext.h"
 #include "launch.h"
 #include "mfma.h"
 #include "split_planes.h"
@@ -83,7 +84,10 @@ struct SwArgs {
 
 // KT frame taps; CO = output channels a workgroup owns per position row in the LDS (8: the fast stem; 16: a 16-channel slice
 // of the slow stem's 64, blockIdx.y walks the slices)
-template <int KT, int CO>
+// DET (include/avt_ext.h): the waves meet in red[] in ordered rounds instead of LDS atomics, and the workgroup STORES its partial
+// filter to slot blockIdx.x of a workspace [gridDim.x][Cout][KT * 7 * 32] (a.dw) for wgrad_reduce.hip to sum in ascending order.
+// A compile-time flag: the atomic form is unchanged.
+template <int KT, int CO, bool DET = false>
 __global__ __launch_bounds__(NTHR, 2) void stem_wgrad_kernel(SwArgs a) {
   constexpr int FP = CO == 8 ? 2 : 1;           // frame taps per MFMA (N = FP x CO = 16)
   constexpr int NP = (KT + FP - 1) / FP;        // steps over the frame taps
@@ -196,26 +200,56 @@ __global__ __launch_bounds__(NTHR, 2) void stem_wgrad_kernel(SwArgs a) {
   // n = co (CO = 16) or (frame tap of the pair) * 8 + co (CO = 8)
   __syncthreads();
   float* const red = reinterpret_cast<float*>(lds);
-  for (int i = tid; i < RED / 4; i += NTHR) red[i] = 0.0f;
-  __syncthreads();
-  if (kb < nkb) {
-    const int n = lane & 15, q = lane >> 4;
-#pragma unroll
-    for (int pp = 0; pp < NP; ++pp)
-#pragma unroll
-      for (int dh = 0; dh < 7; ++dh)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) atomicAdd(&red[((n * NP + pp) * 7 + dh) * 32 + at * 16 + 4 * q + i], acc[pp][dh][i]);
-  }
-  __syncthreads();
   constexpr int PER_CO = KT * 7 * 32;
-  for (int i = tid; i < CO * PER_CO; i += NTHR) {  // dW[co][dt][dh][32]: consecutive threads walk consecutive floats
-    const int co = i / PER_CO, rest = i - co * PER_CO;
-    const int dt = rest / (7 * 32), tail = rest - dt * (7 * 32);
-    const int n = CO == 8 ? (dt % FP) * 8 + co : co, pp = dt / FP;
-    if (co0 + co < a.Cout) unsafeAtomicAdd(a.dw + (int64_t)(co0 + co) * PER_CO + rest, red[(n * NP + pp) * (7 * 32) + tail]);
+  if constexpr (!DET) {
+    for (int i = tid; i < RED / 4; i += NTHR) red[i] = 0.0f;
+    __syncthreads();
+    if (kb < nkb) {
+      const int n = lane & 15, q = lane >> 4;
+#pragma unroll
+      for (int pp = 0; pp < NP; ++pp)
+#pragma unroll
+        for (int dh = 0; dh < 7; ++dh)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) atomicAdd(&red[((n * NP + pp) * 7 + dh) * 32 + at * 16 + 4 * q + i], acc[pp][dh][i]);
+    }
+    __syncthreads();
+    for (int i = tid; i < CO * PER_CO; i += NTHR) {  // dW[co][dt][dh][32]: consecutive threads walk consecutive floats
+      const int co = i / PER_CO, rest = i - co * PER_CO;
+      const int dt = rest / (7 * 32), tail = rest - dt * (7 * 32);
+      const int n = CO == 8 ? (dt % FP) * 8 + co : co, pp = dt / FP;
+      if (co0 + co < a.Cout) unsafeAtomicAdd(a.dw + (int64_t)(co0 + co) * PER_CO + rest, red[(n * NP + pp) * (7 * 32) + tail]);
+    }
+  } else {
+    // ordered rounds over the ONE flush buffer: the two waves of column block 0 (pair-tap halves at = 0 / 1: disjoint elements, and a
+    // lane's (n, q, i, pp, dh) name an element once) store, barrier, block 1's waves add, ... — one copy of red[] per column block
+    // (4 x 43 KB for the fast stem) would not fit a CU's 160 KB, and need not: the rounds reuse the one buffer.  Block 0 always has
+    // columns (Wo >= 8), so every element is written before it is read; blocks past Wo hold zeros and sit their round out.
+    const int n = lane & 15, q = lane >> 4;
+    for (int round = 0; round < KBLK; ++round) {
+      if (kb == round && kb < nkb) {
+#pragma unroll
+        for (int pp = 0; pp < NP; ++pp)
+#pragma unroll
+          for (int dh = 0; dh < 7; ++dh)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              float* const r = &red[((n * NP + pp) * 7 + dh) * 32 + at * 16 + 4 * q + i];
+              *r = round == 0 ? acc[pp][dh][i] : *r + acc[pp][dh][i];
+            }
+      }
+      __syncthreads();
+    }
+    float* const slot = a.dw + (int64_t)blockIdx.x * a.Cout * PER_CO;
+    for (int i = tid; i < CO * PER_CO; i += NTHR) {
+      const int co = i / PER_CO, rest = i - co * PER_CO;
+      const int dt = rest / (7 * 32), tail = rest - dt * (7 * 32);
+      const int nn = CO == 8 ? (dt % FP) * 8 + co : co, pp = dt / FP;
+      if (co0 + co < a.Cout) slot[(int64_t)(co0 + co) * PER_CO + rest] = red[(nn * NP + pp) * (7 * 32) + tail];
+    }
   }
 }
+
 
 // ---- the stems' MaxPool3d((1,3,3),(1,2,2),(0,1,1)) in the training step ---------------------------------------------------------
 // fp32 NDHWC rows.  Forward: the max of the window and WHICH tap held it (4 bits per element, first maximum in row-major tap
@@ -500,16 +534,53 @@ constexpr int CU_LDS_BYTES = 160 * 1024;
 static_assert(stem_wgrad_lds_bytes(1, 16) <= CU_LDS_BYTES && stem_wgrad_lds_bytes(5, 8) <= CU_LDS_BYTES,
               "the two SlowFast stems' weight-gradient instances fit a CU's LDS");
 
-template <int KT, int CO>
-int launch_wgrad(SwArgs& a, hipStream_t st) {
-  constexpr int lds_bytes = stem_wgrad_lds_bytes(KT, CO);
+// persistent workgroups per 16-channel slice: from the shapes alone (the deterministic form's workspace has one slot per workgroup)
+int stem_wgrad_gx(const SwArgs& a) {
   const int slices = (a.Cout + 15) / 16;
   constexpr int wgs = 256;  // persistent workgroups (one per CU: up to 150 KB of LDS)
   int gx = wgs / slices;
   if (gx < 1) gx = 1;
   if (gx > a.nunit) gx = a.nunit;
-  return avt::launch<stem_wgrad_kernel<KT, CO>>("avt_stem_wgrad_x3", dim3((unsigned)gx, (unsigned)slices), dim3(NTHR), lds_bytes, lds_bytes,
-                                                st, a);
+  return gx;
+}
+
+int64_t g_stem_det_launches[2][2];  // [kt 1 / 5][CO 8 / 16]: avt_stem_wgrad_x3_det_launches
+
+template <int KT, int CO, bool DET = false>
+int launch_wgrad(SwArgs& a, hipStream_t st) {
+  constexpr int lds_bytes = stem_wgrad_lds_bytes(KT, CO);
+  const int slices = (a.Cout + 15) / 16;
+  const int gx = stem_wgrad_gx(a);
+  if constexpr (DET) __atomic_fetch_add(&g_stem_det_launches[KT == 5][CO == 16], 1, __ATOMIC_RELAXED);
+  return avt::launch<stem_wgrad_kernel<KT, CO, DET>>(DET ? "avt_stem_wgrad_x3_det" : "avt_stem_wgrad_x3", dim3((unsigned)gx, (unsigned)slices),
+                                                     dim3(NTHR), lds_bytes, lds_bytes, st, a);
+}
+
+// the checks and derived fields the atomic and the deterministic entries share; ptrs = false: the workspace query
+int stem_wgrad_args(SwArgs& a, bool ptrs, const void* x_hi, const void* x_lo, const float* dy, float* dw, int batch, int t, int h, int pw,
+                    int cout, int kt, int pt) {
+  AVT_REQUIRE(!ptrs || (x_hi && x_lo && dy && dw), "avt_stem_wgrad_x3: NULL pointer");
+  AVT_REQUIRE(batch > 0 && t > 0 && pt >= 0 && pt < kt, "avt_stem_wgrad_x3: bad sizes");
+  AVT_REQUIRE(avt_stem_wgrad_x3_supported(h, pw, cout, kt),
+              "avt_stem_wgrad_x3: unsupported shape h=%d pairs=%d cout=%d kt=%d (rows/2 %% 4 == 0, 8..128 pairs, kt 1 or 5, "
+              "cout 8 or a multiple of 16; use avt_conv3d_wgrad_x3_sub_f32)", h, pw, cout, kt);
+  AVT_REQUIRE(!ptrs || (avt::aligned16(x_hi) && avt::aligned16(x_lo) && avt::aligned16(dy) && avt::aligned16(dw)),
+              "avt_stem_wgrad_x3: pointers must be 16-byte aligned");
+  a.x_hi = static_cast<const uint16_t*>(x_hi);
+  a.x_lo = static_cast<const uint16_t*>(x_lo);
+  a.dy = dy;
+  a.dw = dw;
+  a.B = batch; a.T = t; a.H = h; a.PW = pw;
+  a.To = t + 2 * pt - kt + 1;
+  a.Ho = h / 2; a.Wo = pw;
+  a.Cout = cout; a.pt = pt;
+  AVT_REQUIRE(a.To > 0, "avt_stem_wgrad_x3: no output frames");
+  const int64_t xb = (int64_t)batch * t * h * pw * 16;
+  AVT_REQUIRE(xb < (1ll << 32) - 64 && (int64_t)batch * a.To * a.Ho * a.Wo * cout < (1ll << 40), "avt_stem_wgrad_x3: tensor too large");
+  a.x_bytes = (unsigned)xb;
+  a.hgroups = a.Ho / RB;
+  a.nunit = batch * t * a.hgroups;
+  return AVT_OK;
 }
 
 }  // namespace
@@ -542,31 +613,54 @@ extern "C" int avt_stem_wgrad_x3_supported(int h, int pw, int cout, int kt) {
 
 extern "C" int avt_stem_wgrad_x3(const void* x_hi, const void* x_lo, const float* dy, float* dw, int batch, int t, int h, int pw,
                                  int cout, int kt, int pt, void* stream) {
-  AVT_REQUIRE(x_hi && x_lo && dy && dw, "avt_stem_wgrad_x3: NULL pointer");
-  AVT_REQUIRE(batch > 0 && t > 0 && pt >= 0 && pt < kt, "avt_stem_wgrad_x3: bad sizes");
-  AVT_REQUIRE(avt_stem_wgrad_x3_supported(h, pw, cout, kt),
-              "avt_stem_wgrad_x3: unsupported shape h=%d pairs=%d cout=%d kt=%d (rows/2 %% 4 == 0, 8..128 pairs, kt 1 or 5, "
-              "cout 8 or a multiple of 16; use avt_conv3d_wgrad_x3_sub_f32)", h, pw, cout, kt);
-  AVT_REQUIRE(avt::aligned16(x_hi) && avt::aligned16(x_lo) && avt::aligned16(dy) && avt::aligned16(dw),
-              "avt_stem_wgrad_x3: pointers must be 16-byte aligned");
   SwArgs a;
-  a.x_hi = static_cast<const uint16_t*>(x_hi);
-  a.x_lo = static_cast<const uint16_t*>(x_lo);
-  a.dy = dy;
-  a.dw = dw;
-  a.B = batch; a.T = t; a.H = h; a.PW = pw;
-  a.To = t + 2 * pt - kt + 1;
-  a.Ho = h / 2; a.Wo = pw;
-  a.Cout = cout; a.pt = pt;
-  AVT_REQUIRE(a.To > 0, "avt_stem_wgrad_x3: no output frames");
-  const int64_t xb = (int64_t)batch * t * h * pw * 16;
-  AVT_REQUIRE(xb < (1ll << 32) - 64 && (int64_t)batch * a.To * a.Ho * a.Wo * cout < (1ll << 40), "avt_stem_wgrad_x3: tensor too large");
-  a.x_bytes = (unsigned)xb;
-  a.hgroups = a.Ho / RB;
-  a.nunit = batch * t * a.hgroups;
+  if (int rc = stem_wgrad_args(a, true, x_hi, x_lo, dy, dw, batch, t, h, pw, cout, kt, pt)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (kt == 5) return cout == 8 ? launch_wgrad<5, 8>(a, s) : launch_wgrad<5, 16>(a, s);
   return cout == 8 ? launch_wgrad<1, 8>(a, s) : launch_wgrad<1, 16>(a, s);
+}
+
+// ---- the deterministic form (include/avt_ext.h): ordered LDS rounds, one workspace slot per workgroup, wgrad_reduce.hip's sum ----
+namespace avt {
+int wgrad_reduce(const char* who, const float* ws, float* dw, int nchunk, int cout, int E, int ldw, hipStream_t st);  // wgrad_reduce.hip
+}
+
+// kt = 5 with 16-channel slices would stage 5 x 4 dY rows of 16 channels: 214 KB with the patch, more than a CU's LDS
+static int stem_det_fits(int cout, int kt) {
+  AVT_REQUIRE(kt != 5 || cout == 8, "avt_stem_wgrad_x3_det: kt = 5 with cout = %d needs %d bytes of LDS (a CU has %d): cout must be 8", cout,
+              stem_wgrad_lds_bytes(5, 16), CU_LDS_BYTES);
+  return AVT_OK;
+}
+
+extern "C" int64_t avt_stem_wgrad_x3_det_launches(int kt, int co) {
+  if (!(kt == 1 || kt == 5) || !(co == 8 || co == 16)) return -1;
+  return __atomic_load_n(&g_stem_det_launches[kt == 5][co == 16], __ATOMIC_RELAXED);
+}
+
+extern "C" int64_t avt_stem_wgrad_x3_det_ws_bytes(int batch, int t, int h, int pw, int cout, int kt, int pt) {
+  SwArgs a;
+  if (stem_wgrad_args(a, false, nullptr, nullptr, nullptr, nullptr, batch, t, h, pw, cout, kt, pt)) return 0;
+  if (stem_det_fits(cout, kt)) return 0;
+  return (int64_t)stem_wgrad_gx(a) * cout * kt * 7 * 32 * 4;
+}
+
+extern "C" int avt_stem_wgrad_x3_det(const void* x_hi, const void* x_lo, const float* dy, float* dw, int batch, int t, int h, int pw,
+                                     int cout, int kt, int pt, void* ws, int64_t ws_bytes, void* stream) {
+  SwArgs a;
+  if (int rc = stem_wgrad_args(a, true, x_hi, x_lo, dy, dw, batch, t, h, pw, cout, kt, pt)) return rc;
+  if (int rc = stem_det_fits(cout, kt)) return rc;
+  const int gx = stem_wgrad_gx(a), per_co = kt * 7 * 32;
+  const int64_t need = (int64_t)gx * cout * per_co * 4;
+  AVT_REQUIRE(ws && avt::aligned16(ws), "avt_stem_wgrad_x3_det: the workspace must be a 16-byte aligned device pointer");
+  AVT_REQUIRE(ws_bytes >= need, "avt_stem_wgrad_x3_det: workspace of %lld bytes, %lld needed (avt_stem_wgrad_x3_det_ws_bytes)",
+              (long long)ws_bytes, (long long)need);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  a.dw = static_cast<float*>(ws);  // the workgroups store [blockIdx.x][co][kt * 7 * 32]
+  int rc;
+  if (kt == 5) rc = launch_wgrad<5, 8, true>(a, s);
+  else rc = cout == 8 ? launch_wgrad<1, 8, true>(a, s) : launch_wgrad<1, 16, true>(a, s);
+  if (rc != AVT_OK) return rc;
+  return avt::wgrad_reduce("avt_stem_wgrad_x3_det", static_cast<const float*>(ws), dw, gx, cout, per_co, per_co, s);
 }
 
 // MaxPool3d((1,3,3),(1,2,2),(0,1,1)) of the training step on fp32 NDHWC rows (see include/avt.h)

@@ -17,7 +17,8 @@
 // float4 of x is fetched from the row its tap points at (per-slab table of 64 positions x taps offsets, padding = -1) —
 // so an 8-channel 3x3 layer fills 72 of a tile's 128 rows and reads dY once, not 8 of 128 nine times over.
 // Work split: one workgroup = (chunk of slabs, 128 of the longer axis, BN of the shorter one); partial tiles are added into
-// dW with hardware fp32 atomics (dW is zeroed first; the order is not deterministic, as MIOpen's is not).  Strides,
+// dW with hardware fp32 atomics (dW is zeroed first; the order is not deterministic, as MIOpen's is not — the opt-in deterministic
+// form, include/avt_ext.h, stores the partial tiles to a workspace instead and wgrad_reduce.hip sums them in a fixed order).  Strides,
 // padding and ragged edges live in the table; input channels in multiples of 4 (a float4 per tap), output channels of 8; at most
 // 28 taps (3x3x3, 7x1x1) with two workgroups per CU, up to 49 ([1,7,7]: the SlowFast stems, whose 3 input channels travel as
 // 4 — the stems' weight gradient was the last MIOpen kernel of weight in the step, 77 ms of 730) with one; a frame-tap slice
@@ -27,6 +28,7 @@
 #include <type_traits>
 
 #include "avt_common.h"
+#include "../../include/avt_ext.h"
 #include "launch.h"
 #include "conv_args.h"
 #include "mfma.h"
@@ -87,7 +89,9 @@ __device__ __forceinline__ void put4(char* lds, int hi_base, int off, float4 v) 
 }
 
 // SWAP = false: the 128-wide axis is x's (tap, ci), the BN-wide one dy's co; true: the other way round (Cout > taps * Cin).
-template <int BN, bool SWAP, bool BUF>
+// DET (include/avt_ext.h): the epilogue STORES the partial tile to slot `chunk` of a workspace [nchunk][Cout][E] (a.dw, a.ldw = E)
+// instead of adding it into dW; wgrad_reduce.hip sums the slots in ascending order.  A compile-time flag: the atomic form is unchanged.
+template <int BN, bool SWAP, bool BUF, bool DET = false>
 __global__ __launch_bounds__(256, 2) void wgrad_x3_kernel(WgArgs a) {
   constexpr int BM = 128;
   constexpr int WTM = BN == 32 ? 32 : 64;
@@ -310,6 +314,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_x3_kernel(WgArgs a) {
   // D layout: column (lane & 31) = index on the 128-wide axis, rows (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) = index on the other.
   // dW is [co][e]: consecutive lanes must walk e for the atomics to coalesce.  Not swapped, they do.  Swapped, lanes walk co
   // (rows 4 E bytes apart): the tile goes through the LDS first.
+  // DET: a.dw is the workspace [nchunk][Cout][E] (a.ldw = E) and this workgroup's slot is `chunk`
   if constexpr (!SWAP) {
 #pragma unroll
     for (int i = 0; i < NT; ++i)
@@ -319,7 +324,11 @@ __global__ __launch_bounds__(256, 2) void wgrad_x3_kernel(WgArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int co = s0 + wn * WN + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          if (e < a.E && co < a.Cout) unsafeAtomicAdd(a.dw + (int64_t)co * a.ldw + e, acc[i][j][r]);
+          if constexpr (DET) {
+            if (e < a.E && co < a.Cout) a.dw[((int64_t)chunk * a.Cout + co) * a.ldw + e] = acc[i][j][r];
+          } else {
+            if (e < a.E && co < a.Cout) unsafeAtomicAdd(a.dw + (int64_t)co * a.ldw + e, acc[i][j][r]);
+          }
         }
       }
   } else {
@@ -338,14 +347,19 @@ __global__ __launch_bounds__(256, 2) void wgrad_x3_kernel(WgArgs a) {
     for (int idx = tid; idx < BM * BN; idx += 256) {
       const int col = idx / BN, el = idx % BN;
       const int co = r0 + col, e = s0 + el;
-      if (e < a.E && co < a.Cout) unsafeAtomicAdd(a.dw + (int64_t)co * a.ldw + e, stage[col * ES + el]);
+      if constexpr (DET) {
+        if (e < a.E && co < a.Cout) a.dw[((int64_t)chunk * a.Cout + co) * a.ldw + e] = stage[col * ES + el];
+      } else {
+        if (e < a.E && co < a.Cout) unsafeAtomicAdd(a.dw + (int64_t)co * a.ldw + e, stage[col * ES + el]);
+      }
     }
   }
   (void)y0;
 }
 
+
 extern int g_wgrad_buf;
-template <int BN, bool SWAP, bool BUF>
+template <int BN, bool SWAP, bool BUF, bool DET>
 int launch_b(WgArgs& a, int s_count, hipStream_t st);
 
 // The split over positions.  Every workgroup of a launch walks the same number of slabs and `slots` of them run at a time (two per CU
@@ -379,22 +393,34 @@ static int pick_chunks(int tiles, int nslab, int slots, int min_slabs, bool even
   return best;
 }
 
-template <int BN, bool SWAP>
+template <int BN, bool SWAP, bool DET = false>
 int launch(WgArgs& a, int s_count, hipStream_t st) {
   const bool fits32 = g_wgrad_buf && a.x_bytes != 0u && a.dy_bytes != 0u && a.ldx < (1 << 17) && a.ldy < (1 << 17);
-  return fits32 ? launch_b<BN, SWAP, true>(a, s_count, st) : launch_b<BN, SWAP, false>(a, s_count, st);
+  return fits32 ? launch_b<BN, SWAP, true, DET>(a, s_count, st) : launch_b<BN, SWAP, false, DET>(a, s_count, st);
 }
 
-template <int BN, bool SWAP, bool BUF>
-int launch_b(WgArgs& a, int s_count, hipStream_t st) {
-  a.s_tiles = (s_count + BN - 1) / BN;
+// the phase-serial tile's split (r_tiles set by the caller): s_tiles, slabs_per_chunk, nchunk — from the shapes alone, which is
+// what lets the deterministic entry size its workspace before the launch
+// min_slabs: 16 for the atomic epilogue (below); 2 for the deterministic one, a coalesced store of the tile that no other workgroup
+// contends for — the few-position layers (res5: 49 slabs at 8 items) then split over the chip instead of running as one or two chunks,
+// at the price of their partial tiles' traffic through the workspace (at most ~2 x 512 slots x one 64 KB tile per launch)
+static void plan_chunks(WgArgs& a, int bn, int s_count, int min_slabs = 16) {
+  a.s_tiles = (s_count + bn - 1) / bn;
   const int tiles = a.r_tiles * a.s_tiles;
   // split over positions: enough workgroups to fill the chip (256 CUs x 2), but at least 16 slabs each — a workgroup's
   // epilogue is 128 x BN atomics, and with 3 slabs apiece the pointwise layers spent their time there
   // (profiles/r02/probe_wgrad_v2.log: 16 TFLOP/s on 256 -> 1024 channels)
-  const int chunks = pick_chunks(tiles, a.nslab, 512, 16, false);
+  const int chunks = pick_chunks(tiles, a.nslab, 512, min_slabs, false);
   a.slabs_per_chunk = (a.nslab + chunks - 1) / chunks;
   a.nchunk = (a.nslab + a.slabs_per_chunk - 1) / a.slabs_per_chunk;
+}
+
+int64_t g_det_launches[3][2][2];  // [BN 32 / 64 / 128][SWAP][BUF]: avt_conv3d_wgrad_x3_det_launches
+
+template <int BN, bool SWAP, bool BUF, bool DET>
+int launch_b(WgArgs& a, int s_count, hipStream_t st) {
+  if constexpr (!DET) plan_chunks(a, BN, s_count);  // (DET: planned once by det_plan, which sized the workspace from it)
+  const int tiles = a.r_tiles * a.s_tiles;
   constexpr int lds_small = 4 * kPlane + 2 * 64 * 4 + 2 * 64 * kMaxTaps * 4 + 64 * 4;  // (+ the tap table)
   constexpr int lds_big = 4 * kPlane + 2 * 64 * 4 + 2 * 64 * kMaxTapsBig * 4 + 64 * 4;
   static_assert(128 * (BN + 1) * 4 <= lds_small, "the swapped epilogue stages its tile over the operand planes (and tables)");
@@ -402,7 +428,9 @@ int launch_b(WgArgs& a, int s_count, hipStream_t st) {
   const int lds_bytes = a.tapcap > kMaxTaps ? lds_big : lds_small;
   const int64_t grid = (int64_t)tiles * a.nchunk;
   AVT_REQUIRE(grid < (1ll << 31), "avt_conv3d_wgrad_x3_f32: grid too large");
-  return avt::launch<wgrad_x3_kernel<BN, SWAP, BUF>>("avt_conv3d_wgrad_x3_f32", dim3((unsigned)grid), dim3(256), lds_big, lds_bytes, st, a);
+  if constexpr (DET) __atomic_fetch_add(&g_det_launches[BN == 32 ? 0 : (BN == 64 ? 1 : 2)][SWAP][BUF], 1, __ATOMIC_RELAXED);
+  return avt::launch<wgrad_x3_kernel<BN, SWAP, BUF, DET>>(DET ? "avt_conv3d_wgrad_x3_det_sub_f32" : "avt_conv3d_wgrad_x3_f32", dim3((unsigned)grid),
+                                                          dim3(256), lds_big, lds_bytes, st, a);
 }
 
 
@@ -727,20 +755,32 @@ int dispatch(WgArgs& a, int r_count, int s_count, hipStream_t s) {
   return launch<128, SWAP>(a, s_count, s);
 }
 
-}  // namespace
+// The deterministic entry always takes the phase-serial tile (see avt_conv3d_wgrad_x3_det_sub_f32 below).
+// plan_only: fill r_tiles / s_tiles / nchunk and launch nothing (the workspace query and the entry's own size check).
+template <bool SWAP>
+int dispatch_det(WgArgs& a, int r_count, int s_count, bool plan_only, hipStream_t s) {
+  a.r_tiles = (r_count + 127) / 128;
+  const int bn = s_count <= 32 ? 32 : (s_count <= 64 ? 64 : 128);
+  if (plan_only) {
+    plan_chunks(a, bn, s_count, 2);
+    return AVT_OK;
+  }
+  if (bn == 32) return launch<32, SWAP, true>(a, s_count, s);
+  if (bn == 64) return launch<64, SWAP, true>(a, s_count, s);
+  return launch<128, SWAP, true>(a, s_count, s);
+}
 
-// The general entry: explicit output extent (to, ho, wo; 0 = the symmetric-padding formula), any pt / ph / pw (a slice of a
-// longer filter is the same convolution with a shifted padding), dW rows ldw elements apart, zeroed here or by the caller.
-extern "C" int avt_conv3d_wgrad_x3_sub_f32(const float* dy, const float* x, float* dw, int batch, int t, int h, int w, int cin, int cout,
-                                           int kt, int kh, int kw, int st, int sh, int sw, int pt, int ph, int pw, int to, int ho, int wo,
-                                           int ldx, int ldy, int ldw, int zero_dw, void* stream) {
-  AVT_REQUIRE(dy && x && dw, "avt_conv3d_wgrad_x3_f32: NULL pointer");
+// the checks and derived fields that the atomic and the deterministic entries share, in the atomic entry's order.  ptrs = false: the
+// workspace query, which has the geometry only
+int fill_args(WgArgs& a, bool ptrs, const float* dy, const float* x, float* dw, int batch, int t, int h, int w, int cin, int cout, int kt, int kh,
+              int kw, int st, int sh, int sw, int pt, int ph, int pw, int to, int ho, int wo, int ldx, int ldy, int ldw) {
+  AVT_REQUIRE(!ptrs || (dy && x && dw), "avt_conv3d_wgrad_x3_f32: NULL pointer");
   AVT_REQUIRE(cin > 0 && cin % 4 == 0 && cout > 0 && cout % 8 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= cin && ldy >= cout,
               "avt_conv3d_wgrad_x3_f32: input channels in multiples of 4, output channels of 8, row strides in multiples of 4 covering them");
   AVT_REQUIRE(kt >= 1 && kh >= 1 && kw >= 1 && kt * kh * kw <= kMaxTapsBig && st >= 1 && sh >= 1 && sw >= 1,
               "avt_conv3d_wgrad_x3_f32: 1..%d kernel taps, strides >= 1", kMaxTapsBig);
-  AVT_REQUIRE(avt::aligned16(dy) && avt::aligned16(x) && avt::aligned16(dw), "avt_conv3d_wgrad_x3_f32: pointers must be 16-byte aligned");
-  WgArgs a = {};
+  AVT_REQUIRE(!ptrs || (avt::aligned16(dy) && avt::aligned16(x) && avt::aligned16(dw)), "avt_conv3d_wgrad_x3_f32: pointers must be 16-byte aligned");
+  a = {};
   a.dy = dy; a.x = x; a.dw = dw;
   a.B = batch; a.T = t; a.H = h; a.W = w;
   a.To = to > 0 ? to : (t + 2 * pt - kt) / st + 1;
@@ -766,6 +806,22 @@ extern "C" int avt_conv3d_wgrad_x3_sub_f32(const float* dy, const float* x, floa
   a.nslab = (int)((M + 63) / 64);
   a.dWo = make_fastdiv((uint32_t)a.Wo); a.dHo = make_fastdiv((uint32_t)a.Ho); a.dTo = make_fastdiv((uint32_t)a.To);
   a.dKW = make_fastdiv((uint32_t)kw); a.dKH = make_fastdiv((uint32_t)kh);
+  return AVT_OK;
+}
+
+}  // namespace
+
+namespace avt {
+int wgrad_reduce(const char* who, const float* ws, float* dw, int nchunk, int cout, int E, int ldw, hipStream_t st);  // wgrad_reduce.hip
+}
+
+// The general entry: explicit output extent (to, ho, wo; 0 = the symmetric-padding formula), any pt / ph / pw (a slice of a
+// longer filter is the same convolution with a shifted padding), dW rows ldw elements apart, zeroed here or by the caller.
+extern "C" int avt_conv3d_wgrad_x3_sub_f32(const float* dy, const float* x, float* dw, int batch, int t, int h, int w, int cin, int cout,
+                                           int kt, int kh, int kw, int st, int sh, int sw, int pt, int ph, int pw, int to, int ho, int wo,
+                                           int ldx, int ldy, int ldw, int zero_dw, void* stream) {
+  WgArgs a;
+  if (int rc = fill_args(a, true, dy, x, dw, batch, t, h, w, cin, cout, kt, kh, kw, st, sh, sw, pt, ph, pw, to, ho, wo, ldx, ldy, ldw)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (zero_dw) {
     AVT_REQUIRE(a.ldw == a.E, "avt_conv3d_wgrad_x3_f32: a slice of a longer dW is zeroed by the caller (zero_dw = 0)");
@@ -777,6 +833,49 @@ extern "C" int avt_conv3d_wgrad_x3_sub_f32(const float* dy, const float* x, floa
   // the longer axis — x's (tap, ci) or dy's co — takes the 128-wide side of the tile
   if (cout > a.E) return dispatch<true>(a, cout, a.E, s);
   return dispatch<false>(a, a.E, cout, s);
+}
+
+// ---- the deterministic form (include/avt_ext.h) -----------------------------------------------------------------------------------
+// Two stream-ordered launches: the phase-serial tile with its storing epilogue (slot = chunk, a function of the shapes), then the
+// ascending-order sum of wgrad_reduce.hip.  The pipelined 256 x 128 tile is NOT used here: its value is the overlap of its phases on
+// the large pointwise layers, where the deterministic mode's cost is the workspace traffic anyway, and one tile family means one
+// epilogue to keep bit-stable and one chunk rule for the workspace query.
+static int64_t det_plan(WgArgs& a) {  // -> workspace bytes; a.nchunk / tiles are set
+  if (a.Cout > a.E) dispatch_det<true>(a, a.Cout, a.E, true, nullptr);
+  else dispatch_det<false>(a, a.E, a.Cout, true, nullptr);
+  return (int64_t)a.nchunk * a.Cout * a.E * 4;
+}
+
+extern "C" int64_t avt_conv3d_wgrad_x3_det_ws_bytes(int batch, int t, int h, int w, int cin, int cout, int kt, int kh, int kw, int st,
+                                                    int sh, int sw, int pt, int ph, int pw, int to, int ho, int wo, int ldx, int ldy,
+                                                    int ldw) {
+  WgArgs a;
+  if (fill_args(a, false, nullptr, nullptr, nullptr, batch, t, h, w, cin, cout, kt, kh, kw, st, sh, sw, pt, ph, pw, to, ho, wo, ldx, ldy, ldw))
+    return 0;
+  return det_plan(a);
+}
+
+extern "C" int64_t avt_conv3d_wgrad_x3_det_launches(int bn, int swap, int buf) {
+  if (!(bn == 32 || bn == 64 || bn == 128) || (swap | buf) & ~1) return -1;
+  return __atomic_load_n(&g_det_launches[bn == 32 ? 0 : (bn == 64 ? 1 : 2)][swap][buf], __ATOMIC_RELAXED);
+}
+
+extern "C" int avt_conv3d_wgrad_x3_det_sub_f32(const float* dy, const float* x, float* dw, int batch, int t, int h, int w, int cin,
+                                               int cout, int kt, int kh, int kw, int st, int sh, int sw, int pt, int ph, int pw, int to,
+                                               int ho, int wo, int ldx, int ldy, int ldw, void* ws, int64_t ws_bytes, void* stream) {
+  WgArgs a;
+  if (int rc = fill_args(a, true, dy, x, dw, batch, t, h, w, cin, cout, kt, kh, kw, st, sh, sw, pt, ph, pw, to, ho, wo, ldx, ldy, ldw)) return rc;
+  const int64_t need = det_plan(a);
+  AVT_REQUIRE(ws && avt::aligned16(ws), "avt_conv3d_wgrad_x3_det_sub_f32: the workspace must be a 16-byte aligned device pointer");
+  AVT_REQUIRE(ws_bytes >= need, "avt_conv3d_wgrad_x3_det_sub_f32: workspace of %lld bytes, %lld needed (avt_conv3d_wgrad_x3_det_ws_bytes)",
+              (long long)ws_bytes, (long long)need);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int ldw_out = a.ldw;
+  a.dw = static_cast<float*>(ws);  // the tiles store [chunk][co][e]
+  a.ldw = a.E;
+  const int rc = cout > a.E ? dispatch_det<true>(a, cout, a.E, false, s) : dispatch_det<false>(a, a.E, cout, false, s);
+  if (rc != AVT_OK) return rc;
+  return avt::wgrad_reduce("avt_conv3d_wgrad_x3_det_sub_f32", static_cast<const float*>(ws), dw, a.nchunk, cout, a.E, ldw_out, s);
 }
 
 // 1 (default): the layers the 256 x 128 pipelined tile measured faster on take it; 2: every layer it can take; 0: none (A/Bs, tests)

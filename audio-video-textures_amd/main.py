@@ -84,6 +84,12 @@ def build_parser():
            "accumulation, forward 2^-22 / gradients 2^-16 per product (default; train_ops.py); fp32 = MIOpen's fp32 "
            "convolutions, the reference's arithmetic (train.py:114-141), with the fused BatchNorm / pool passes kept; both for SlowFast "
            "and for the 3D-ResNets")
+    a("--train_deterministic", default=False, action="store_true",
+      help="weight gradients of the training step as per-chunk partial tiles summed in a fixed order (train_ops.set_deterministic) "
+           "instead of fp32 atomics: with the rest of the step already free of atomics, one process on one GPU with one build repeats "
+           "a seed bit for bit, eagerly and with --train_graph 1, with either --train_optimizer.  Needs --train_layout ndhwc and "
+           "--train_conv x3; across ranks the all-reduce's order is the backend's and nothing is promised.  Default off: the atomic "
+           "path, unchanged (not in the reference)")
     a("--slomo_ckpt", default="ckpt/SuperSloMo.ckpt", type=str,
       help="SuperSloMo checkpoint (validate.py:183 hard-codes this path); 'random' = seeded weights; missing file = cuts")
     a("-long", "--long", dest="long", default=False, action="store_true", help="unused in the reference")
@@ -198,10 +204,20 @@ def main(args, video_name, itr=0):
         from . import train_ops
 
         model = train_ops.training_layout(model)
+        train_ops.set_deterministic(False)  # (a process-wide switch: this run's flag decides, not an earlier run's)
         mode = train_ops.set_conv_mode(getattr(args, "train_conv", "x3"))
         if rank == 0:
             print("training convolutions: %s" % ("split-plane MFMA (x3: fp16 planes forward 2^-22, bf16 planes gradients 2^-16, "
                                                   "fp32 accumulation)" if mode == "x3" else "MIOpen fp32"))
+        if getattr(args, "train_deterministic", False):
+            train_ops.set_deterministic(True)  # (raises with --train_conv fp32)
+            if rank == 0:
+                print("training step: deterministic weight gradients (fixed-order reduction): bit-reproducible within one process on "
+                      "one GPU with this build%s" % ("; across ranks the all-reduce's order is the backend's" if world > 1 else ""))
+    elif not args.evaluate and getattr(args, "train_deterministic", False):
+        from ._lib import AvtError
+
+        raise AvtError("--train_deterministic needs --train_layout ndhwc (the hand-written training kernels)")
     if world > 1 and not args.evaluate:  # weights resident per rank, gradients all-reduced over RCCL
         if getattr(args, "train_graph", 0):
             # every rank replays its step as a HIP graph and the gradients cross the ranks in one flat buffer outside it (train.train):

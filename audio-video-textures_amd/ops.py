@@ -698,6 +698,62 @@ def conv3d_wgrad_x3_sub_f32(dy, x, dw, dims, cin, cout, kernel, stride, pad, out
                                   *[int(v) for v in out_dims], int(ldx), int(ldy), int(ldw), int(bool(zero_dw)), _stream())
 
 
+# ---- the deterministic weight gradients (include/avt_ext.h): partial tiles to a workspace, summed in a fixed order ----
+WGRAD_DET_WS_PEAK = [0]  # bytes of the largest workspace a deterministic weight gradient has taken in this process (tools report it)
+
+
+def _det_workspace(need, device, ws, who):
+    """The call's workspace: `ws` if the caller brings one (tests fill it with NaN: nothing is read that the call did not write), else
+    torch.empty — per call, from the caching allocator, which is stream-aware and capture-safe; one shared buffer would not be: the
+    query encoder and the pathways run their backward on side streams, so two weight gradients are in flight at once."""
+    if need <= 0:
+        raise _lib.AvtError("%s: the library refuses this geometry: %s" % (who, (_lib.lib().avt_last_error() or b"?").decode()))
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=device)
+    else:
+        _dev(ws, "ws")
+    WGRAD_DET_WS_PEAK[0] = max(WGRAD_DET_WS_PEAK[0], int(need))
+    return ws
+
+
+def conv3d_wgrad_x3_det_ws_bytes(dims, cin, cout, kernel, stride, pad, out_dims, ldx, ldy, ldw):
+    """Bytes of workspace conv3d_wgrad_x3_det_sub_f32 needs for this geometry; 0 for a geometry the entry refuses."""
+    b, t, h, w = dims
+    return int(_lib.lib().avt_conv3d_wgrad_x3_det_ws_bytes(int(b), int(t), int(h), int(w), int(cin), int(cout), *[int(k) for k in kernel],
+                                                            *[int(v) for v in stride], *[int(v) for v in pad],
+                                                            *[int(v) for v in out_dims], int(ldx), int(ldy), int(ldw)))
+
+
+def conv3d_wgrad_x3_det_sub_f32(dy, x, dw, dims, cin, cout, kernel, stride, pad, out_dims, ldx, ldy, ldw, ws=None):
+    """conv3d_wgrad_x3_sub_f32 with a fixed summation order: dw's taps * cin columns of each row are WRITTEN (no zeroing; columns beyond
+    them are left alone).  ws: a device byte buffer of at least conv3d_wgrad_x3_det_ws_bytes(...) (default: torch.empty per call)."""
+    b, t, h, w = dims
+    _dev(dy, "dy", torch.float32)
+    _dev(x, "x", torch.float32)
+    need = conv3d_wgrad_x3_det_ws_bytes(dims, cin, cout, kernel, stride, pad, out_dims, ldx, ldy, ldw)
+    ws = _det_workspace(need, dy.device, ws, "conv3d_wgrad_x3_det_sub_f32")
+    K.avt_conv3d_wgrad_x3_det_sub_f32(_p(dy), _p(x), C.c_void_p(dw.data_ptr()), int(b), int(t), int(h), int(w), int(cin), int(cout),
+                                      *[int(k) for k in kernel], *[int(v) for v in stride], *[int(v) for v in pad],
+                                      *[int(v) for v in out_dims], int(ldx), int(ldy), int(ldw), _p(ws), int(ws.numel() * ws.element_size()),
+                                      _stream())
+
+
+def stem_wgrad_x3_det_ws_bytes(batch, t, h, pw, cout, kt, pt):
+    return int(_lib.lib().avt_stem_wgrad_x3_det_ws_bytes(int(batch), int(t), int(h), int(pw), int(cout), int(kt), int(pt)))
+
+
+def stem_wgrad_x3_det(x_hi, x_lo, dy, batch, t, h, pw, cout, kt, pt, ws=None, dw=None):
+    """stem_wgrad_x3 with a fixed summation order -> dw [cout, kt, 7, 4, 8] fp32, written (not accumulated) by the call."""
+    _dev(dy, "dy", torch.float32, contiguous=False)
+    need = stem_wgrad_x3_det_ws_bytes(batch, t, h, pw, cout, kt, pt)
+    ws = _det_workspace(need, dy.device, ws, "stem_wgrad_x3_det")
+    if dw is None:
+        dw = torch.empty((cout, kt, 7, 4, 8), dtype=torch.float32, device=dy.device)
+    K.avt_stem_wgrad_x3_det(_p(x_hi), _p(x_lo), _p(dy), _p(dw), int(batch), int(t), int(h), int(pw), int(cout), int(kt), int(pt), _p(ws),
+                            int(ws.numel() * ws.element_size()), _stream())
+    return dw
+
+
 def stem_conv_x3(x_ptrs, wt_hi, wt_lo, bias, wscale, out_ptrs, batch, t, h, pw, cout, kt, st, pt, plane_dtype, relu=True,
                  frames_per_tile=0, frame_idx=None, table_frames=0):
     """stem_conv on plane pairs (contract-grade mode); wt_hi / wt_lo = fused_slowfast.stem_lds_image of each weight plane

@@ -53,12 +53,39 @@ def set_conv_mode(mode):
     global _CONV_X3, _WGRAD_X3
     if mode not in ("x3", "fp32"):
         raise ValueError("train_conv must be 'x3' or 'fp32', got %r" % (mode,))
+    if mode == "fp32" and _DETERMINISTIC:
+        raise _no_miopen_in_deterministic_mode()
     _CONV_X3 = _WGRAD_X3 = 1 if mode == "x3" else 0
     return mode
 
 
 def conv_mode():
     return "x3" if _CONV_X3 else "fp32"
+
+
+_DETERMINISTIC = 0  # weight gradients through the workspace + fixed-order reduction entries (include/avt_ext.h); set_deterministic
+
+
+def _no_miopen_in_deterministic_mode():
+    return _lib.AvtError("deterministic training needs the hand-written convolutions (--train_conv x3): MIOpen's fp32 weight gradients "
+                         "(--train_conv fp32) sum in an order that changes from run to run")
+
+
+def set_deterministic(flag):
+    """True: every weight gradient of the training step (_conv_wgrad in all its branches, the patch-resident stems, conv2d) is written as
+    per-chunk partial tiles and summed by a second launch in a fixed order, so that — with the rest of the step free of atomics already —
+    one process on one GPU with one build repeats a seed bit for bit.  The default (False) is the atomic path, unchanged.  -> the
+    previous setting.  Raises AvtError with --train_conv fp32 in force (MIOpen's order is not ours to fix)."""
+    global _DETERMINISTIC
+    was = bool(_DETERMINISTIC)
+    if flag and not (_CONV_X3 and _WGRAD_X3):
+        raise _no_miopen_in_deterministic_mode()
+    _DETERMINISTIC = 1 if flag else 0
+    return was
+
+
+def deterministic():
+    return bool(_DETERMINISTIC)
 
 
 def invalidate_weight_cache(drop=False):
@@ -88,7 +115,8 @@ except ImportError:  # (torch < 2.0: callers invalidate by hand, as train() alwa
 # per-process launch counters of the hand-written training kernels (tests assert that the default path really runs them)
 CALLS = {"conv_fwd_x3": 0, "dgrad_x3": 0, "dgrad_strided_x3": 0, "wgrad_x3": 0, "wgrad_stem_x3": 0, "bn_fwd": 0, "bn_bwd": 0,
          "miopen_dgrad": 0, "miopen_wgrad": 0, "stem_fwd_patch": 0, "wgrad_stem_patch": 0, "maxpool_hip": 0, "pw_f32": 0,
-         "bn_fwd_pre": 0, "bn_bwd_pre": 0, "dgrad_bwdstats": 0, "planes_multi": 0, "maxpool3d_hip": 0, "sgd_multi": 0, "grad_pack_multi": 0}
+         "bn_fwd_pre": 0, "bn_bwd_pre": 0, "dgrad_bwdstats": 0, "planes_multi": 0, "maxpool3d_hip": 0, "sgd_multi": 0, "grad_pack_multi": 0,
+         "wgrad_det": 0}  # (wgrad_det: launches of the deterministic weight-gradient entries, counted next to the rows above)
 
 
 def _rows(x):
@@ -1337,15 +1365,24 @@ def _conv_wgrad(ctx, dy, x, weight, stride, padding, kernel, cin, cout):
             #  gradients whose strides equal the parameters' — a permuted view differs in the stride of a one-tap dimension, and a
             #  foreach SGD then ran one launch per tensor: +4.8 ms on a 47 ms step, profiles/r06/train_one_item_arena_sgd_ab.log)
             dw = torch.as_strided(flat, tuple(weight.shape), tuple(weight.stride()))
-            ops.conv3d_wgrad_x3_sub_f32(dyr, xr, flat, dims, cin, cout, kernel, stride, padding, (0, 0, 0), cin, cout, taps * cin, False)
+            if _DETERMINISTIC:
+                _wgrad_det(dyr, xr, flat, dims, cin, cout, kernel, stride, padding, (0, 0, 0), cin, cout, taps * cin)
+            else:
+                ops.conv3d_wgrad_x3_sub_f32(dyr, xr, flat, dims, cin, cout, kernel, stride, padding, (0, 0, 0), cin, cout, taps * cin, False)
         else:
             dw = torch.empty_like(weight)  # channels-last strides: memory [cout][kt][kh][kw][cin], the kernel's order
-            ops.conv3d_wgrad_x3_f32(dyr, xr, dw.permute(0, 2, 3, 4, 1), dims, cin, cout, kernel, stride, padding, cin, cout)
+            if _DETERMINISTIC:
+                _wgrad_det(dyr, xr, dw, dims, cin, cout, kernel, stride, padding, (0, 0, 0), cin, cout, taps * cin)
+            else:
+                ops.conv3d_wgrad_x3_f32(dyr, xr, dw.permute(0, 2, 3, 4, 1), dims, cin, cout, kernel, stride, padding, cin, cout)
     elif (_WGRAD_X3 and cin % 8 and cin != 3 and x.shape[1] == 8 and taps <= 28 and max(x.numel(), dy.numel()) < (1 << 31) - 64):
         # a few-channel first layer (VGGish: 1 mel channel) on its zero-padded 8-channel copy; the padded taps' gradient is dropped
         CALLS["wgrad_x3"] += 1
         dw8 = torch.empty((cout, 8) + tuple(kernel), dtype=torch.float32, device=dy.device, memory_format=torch.channels_last_3d)
-        ops.conv3d_wgrad_x3_f32(dyr, xr, dw8.permute(0, 2, 3, 4, 1), dims, 8, cout, kernel, stride, padding, 8, cout)
+        if _DETERMINISTIC:
+            _wgrad_det(dyr, xr, dw8, dims, 8, cout, kernel, stride, padding, (0, 0, 0), 8, cout, taps * 8)
+        else:
+            ops.conv3d_wgrad_x3_f32(dyr, xr, dw8.permute(0, 2, 3, 4, 1), dims, 8, cout, kernel, stride, padding, 8, cout)
         dw = torch.empty_like(weight)
         dw.copy_(dw8[:, :cin])
     elif (_WGRAD_X3 and _STEM_WGRAD_X3 and cin == 3 and x.shape[1] == 8 and kernel[1] * kernel[2] <= 49 and
@@ -1353,20 +1390,34 @@ def _conv_wgrad(ctx, dy, x, weight, stride, padding, kernel, cin, cout):
         # the stems: 3 input channels travel as 4 of the forward's 8-channel padded clip; a [kt,7,7] filter is kt slices of
         # 49 taps, each a weight-gradient problem of its own with the temporal padding shifted by its frame tap
         kt, kh, kw = kernel
-        acc = torch.zeros((cout, kt, kh * kw, 4), dtype=torch.float32, device=dy.device)
+        # (deterministic: every slice WRITES its kh * kw * 4 columns of each row, and the kt slices cover the rows: no zeroing)
+        acc = (torch.empty if _DETERMINISTIC else torch.zeros)((cout, kt, kh * kw, 4), dtype=torch.float32, device=dy.device)
         for dt in range(kt):
+            if _DETERMINISTIC:
+                _wgrad_det(dyr, xr, acc[:, dt], dims, 4, cout, (1, kh, kw), stride, (padding[0] - dt, padding[1], padding[2]),
+                           (dy.shape[2], dy.shape[3], dy.shape[4]), 8, cout, kt * kh * kw * 4)
+                continue
             ops.conv3d_wgrad_x3_sub_f32(dyr, xr, acc[:, dt], dims, 4, cout, (1, kh, kw), stride, (padding[0] - dt, padding[1], padding[2]),
                                         (dy.shape[2], dy.shape[3], dy.shape[4]), 8, cout, kt * kh * kw * 4, False)
         CALLS["wgrad_stem_x3"] += 1
         dw = torch.empty_like(weight)
         dw.copy_(acc.view(cout, kt, kh, kw, 4)[..., :3].permute(0, 4, 1, 2, 3))
     else:  # (stems when AVT_TRAIN_STEM_WGRAD_X3=0, filters of more than 28 taps): MIOpen
+        if _DETERMINISTIC:
+            raise _lib.AvtError("deterministic training: the weight gradient of a %s -> %s convolution with kernel %s has no hand-written "
+                                "kernel and would run on MIOpen, whose summation order is not fixed" % (cin, cout, tuple(kernel)))
         if x.shape[1] != weight.shape[1]:  # the padded copy was saved: MIOpen wants the 3-channel clip
             x = x[:, : weight.shape[1]].contiguous(memory_format=torch.channels_last_3d)
         CALLS["miopen_wgrad"] += 1
         dw = torch.ops.aten.convolution_backward(dy, x, weight, None, stride, padding, (1, 1, 1), False, (0, 0, 0), 1,
                                                  [False, True, False])[1]
     return dw
+
+
+def _wgrad_det(dyr, xr, dw, dims, cin, cout, kernel, stride, padding, out_dims, ldx, ldy, ldw):
+    """One deterministic weight-gradient launch pair (tile + fixed-order reduction); dw is written, not accumulated."""
+    CALLS["wgrad_det"] += 1
+    ops.conv3d_wgrad_x3_det_sub_f32(dyr, xr, dw, dims, cin, cout, kernel, stride, padding, out_dims, ldx, ldy, ldw)
 
 
 def _conv_dgrad(ctx, dy, dalias, x, weight, stride, padding, kernel, cin, cout):
@@ -1594,7 +1645,11 @@ class _StemX3(torch.autograd.Function):
         dy = dy.contiguous(memory_format=torch.channels_last_3d)
         xh, xl = ops.clip_planes_f32(x, ops.X3_BF16)
         CALLS["wgrad_stem_patch"] += 1
-        dwp = ops.stem_wgrad_x3(xh, xl, dy, b, t, h, w // 2, c, kt, kt // 2)  # [c, kt, 7, 4 pair taps, 2 pixels x 4 channels]
+        if _DETERMINISTIC:
+            CALLS["wgrad_det"] += 1
+            dwp = ops.stem_wgrad_x3_det(xh, xl, dy, b, t, h, w // 2, c, kt, kt // 2)
+        else:
+            dwp = ops.stem_wgrad_x3(xh, xl, dy, b, t, h, w // 2, c, kt, kt // 2)  # [c, kt, 7, 4 pair taps, 2 pixels x 4 channels]
         dw = torch.empty_like(weight)
         dw.copy_(dwp.view(c, kt, 7, 8, 4)[:, :, :, 1:, :3].permute(0, 4, 1, 2, 3))  # column tap k = 2 * pair + pixel - 1
         return None, dw
