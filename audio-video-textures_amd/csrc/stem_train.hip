@@ -28,6 +28,7 @@
 #include "launch.h"
 #include "mfma.h"
 #include "split_planes.h"
+#include "wgrad_reduce.h"
 
 namespace {
 
@@ -621,10 +622,6 @@ extern "C" int avt_stem_wgrad_x3(const void* x_hi, const void* x_lo, const float
 }
 
 // ---- the deterministic form (include/avt_ext.h): ordered LDS rounds, one workspace slot per workgroup, wgrad_reduce.hip's sum ----
-namespace avt {
-int wgrad_reduce(const char* who, const float* ws, float* dw, int nchunk, int cout, int E, int ldw, hipStream_t st);  // wgrad_reduce.hip
-}
-
 // kt = 5 with 16-channel slices would stage 5 x 4 dY rows of 16 channels: 214 KB with the patch, more than a CU's LDS
 static int stem_det_fits(int cout, int kt) {
   AVT_REQUIRE(kt != 5 || cout == 8, "avt_stem_wgrad_x3_det: kt = 5 with cout = %d needs %d bytes of LDS (a CU has %d): cout must be 8", cout,

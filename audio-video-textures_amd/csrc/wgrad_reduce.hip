@@ -9,6 +9,7 @@
 // has just been written by the launch in front of this one on the same stream.
 #include "avt_common.h"
 #include "../../include/avt_ext.h"
+#include "wgrad_reduce.h"
 
 namespace {
 
@@ -56,8 +57,6 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(RdArgs a) {
 
 namespace avt {
 
-// ws [nchunk][cout][E] -> dw [cout][ldw] (first E columns), chunks in ascending order.  The caller has checked the pointers
-// (ws 16-byte aligned and large enough, dw 16-byte aligned) and E % 4 == 0, ldw >= E.
 int wgrad_reduce(const char* who, const float* ws, float* dw, int nchunk, int cout, int E, int ldw, hipStream_t st) {
   AVT_REQUIRE(ws && dw && nchunk >= 1 && cout >= 1 && E >= 4 && E % 4 == 0 && ldw >= E, "%s: bad reduction geometry", who);
   RdArgs a;

@@ -32,6 +32,7 @@
 #include "launch.h"
 #include "conv_args.h"
 #include "mfma.h"
+#include "wgrad_reduce.h"
 
 // phase-skip diagnostic (tools/probe_wgrad_phases.py against a library built with -DAVT_WGRAD_DBG_CONST=n: 1 skip the LDS
 // stage, 2 the MFMAs, 4 the global loads): compile-time, the shipped library carries no switch
@@ -68,29 +69,167 @@ struct WgArgs {
 };
 
 constexpr int kPlane = 64 * 256;  // one plane of one operand: [64 positions][128 channels x 2 B]
-// BUF forms (tensors below 4 GB): the position tables hold BYTE offsets of rows, kRowOob for "no row"; a thread adds its channel's
-// bytes and loads through a buffer resource, whose bounds check returns zeros — see the pipelined tile below
+// "no row" in a position table of BYTE offsets (RowEntry below)
 constexpr unsigned kRowOob = 0xFFF00000u;  // (+ a channel offset of < 1 MB stays beyond every buffer and does not wrap)
 
 // byte offset of 16-byte chunk `ch` (8 channels) of position row `row`: 256-byte rows, chunks XOR-swizzled so that the row
 // writes and the transposed reads are both conflict-free (cdna_hip_programming.md T10, image (b))
 __device__ __forceinline__ int swz(int row, int ch) { return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
 
-// four consecutive channels of one position -> 8 bytes of the hi plane + 8 bytes of the lo plane
-__device__ __forceinline__ void put4(char* lds, int hi_base, int off, float4 v) {
+// four consecutive channels of one position -> 8 bytes of the hi plane (at base + off) + 8 bytes of the lo plane, PITCH bytes further
+template <int PITCH>
+__device__ __forceinline__ void put4(char* base, int off, float4 v) {
   const uint32_t h01 = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){v.x, v.y}, bf16x2));
   const uint32_t h23 = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){v.z, v.w}, bf16x2));
   const float r0 = v.x - __builtin_bit_cast(float, h01 << 16), r1 = v.y - __builtin_bit_cast(float, h01 & 0xFFFF0000u);
   const float r2 = v.z - __builtin_bit_cast(float, h23 << 16), r3 = v.w - __builtin_bit_cast(float, h23 & 0xFFFF0000u);
   const uint32_t l01 = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){r0, r1}, bf16x2));
   const uint32_t l23 = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){r2, r3}, bf16x2));
-  *reinterpret_cast<uint2*>(lds + hi_base + off) = make_uint2(h01, h23);
-  *reinterpret_cast<uint2*>(lds + hi_base + kPlane + off) = make_uint2(l01, l23);
+  *reinterpret_cast<uint2*>(base + off) = make_uint2(h01, h23);
+  *reinterpret_cast<uint2*>(base + PITCH + off) = make_uint2(l01, l23);
+}
+
+// the tap table [taps]: dt | dh << 8 | dw << 16, once per workgroup (two divisions per tap and slab otherwise: the tiles are bound by
+// their vector instructions)
+__device__ __forceinline__ void fill_ttab(const WgArgs& a, int* ttab, int tid) {
+  if (tid < a.taps) {  // (a thread per tap: both tiles have more threads than kMaxTapsBig)
+    const int t1 = (int)fastdiv((uint32_t)tid, a.dKW), dw_ = tid - t1 * a.KW;
+    const int dt = (int)fastdiv((uint32_t)t1, a.dKH), dh = t1 - dt * a.KH;
+    ttab[tid] = dt | (dh << 8) | (dw_ << 16);
+  }
+}
+
+// A position-table entry says where a row starts: as an ELEMENT offset, -1 = no row — or, for the buffer loads (BYTES; tensors below
+// 4 GB), as a BYTE offset, kRowOob = no row: a thread adds its channel's bytes and the buffer resource's bounds check returns zeros
+template <bool BYTES>
+struct RowEntry {
+  static constexpr int none = BYTES ? (int)kRowOob : -1;
+  static __device__ __forceinline__ int at(int elem) { return BYTES ? (int)(4u * (unsigned)elem) : elem; }
+};
+
+// Decodes the P output positions of `step` (P = 64: a slab; 32: a pipelined step) into table slot `slot`: ytab [slot][P] = the
+// position's dy row, xtab [slot][P][tapcap] = its x row under every tap (padding = no row).  Thread -> position tid % P, taps tid / P,
+// + TAP_STEP (= threads / P), ...  `live` = false: the step is not this workgroup's, all of it decodes to "no row".
+template <int P, int TAP_STEP, bool BYTES>
+__device__ __forceinline__ void decode_positions(const WgArgs& a, int* ytab, int* xtab, const int* ttab, int tid, int step, int slot, bool live) {
+  static_assert(P == 64 || P == 32, "positions per step");
+  using Row = RowEntry<BYTES>;
+  const int p = tid & (P - 1), m = step * P + p;
+  const bool ok = m < a.M && live;
+  if (BYTES && a.pointwise) {  // 1x1x1, stride 1, no padding: output position m reads input row m (half of the step's launches)
+    if (tid < P) {
+      ytab[slot * P + p] = ok ? Row::at(m * a.ldy) : Row::none;
+      xtab[(slot * P + p) * a.tapcap] = ok ? Row::at(m * a.ldx) : Row::none;
+    }
+    return;
+  }
+  const int q1 = (int)fastdiv((uint32_t)(ok ? m : 0), a.dWo), wo = (ok ? m : 0) - q1 * a.Wo;
+  const int q2 = (int)fastdiv((uint32_t)q1, a.dHo), ho = q1 - q2 * a.Ho;
+  const int bb = (int)fastdiv((uint32_t)q2, a.dTo), to = q2 - bb * a.To;
+  if (tid < P) ytab[slot * P + p] = ok ? Row::at(m * a.ldy) : Row::none;
+  for (int tap = tid >> (P == 64 ? 6 : 5); tap < a.taps; tap += TAP_STEP) {
+    const int pk = ttab[tap], dt = pk & 255, dh = (pk >> 8) & 255, dw_ = pk >> 16;
+    const int ti = to * a.st - a.pt + dt, hi = ho * a.sh - a.ph + dh, wi = wo * a.sw - a.pw + dw_;
+    const bool in = ok && (unsigned)ti < (unsigned)a.T && (unsigned)hi < (unsigned)a.H && (unsigned)wi < (unsigned)a.W;
+    xtab[(slot * P + p) * a.tapcap + tap] = in ? Row::at((((bb * a.T + ti) * a.H + hi) * a.W + wi) * a.ldx) : Row::none;
+  }
+}
+
+// Transposed-read address, inside one operand's hi plane and at k-slice 0, of a lane's half h2 of the 32-channel block that starts at
+// channel c0 (T10: lane 4q + p of a 16-lane group supplies row q, channels 4p .. 4p + 3 of the block; groups 0 / 1 = channels 0-15 /
+// 16-31 of the 32-row operand block, groups 2 / 3 the same for positions + 8).  A k-slice is 16 positions = 4096 bytes further:
+// + 16 rows leaves the swizzle's (row & 3) and (row >> 2) & 3 alone.
+__device__ __forceinline__ int frag_addr(int lane, int c0, int h2) {
+  const int g = lane >> 4, tq = (lane & 15) >> 2, tp = lane & 3;
+  return swz(8 * (g >> 1) + 4 * h2 + tq, (c0 + 16 * (g & 1)) / 8 + (tp >> 1)) + 8 * (tp & 1);
+}
+
+// the hi / lo fragments of one k-slice (16 positions): NJ 32-channel blocks of the R operand, NI of the S operand
+template <int NI, int NJ>
+struct Frags {
+  i32x4 rh[NJ], rl[NJ], sh[NI], sl[NI];
+};
+
+// PITCH = bytes from an operand's hi plane to its lo plane; raddr / saddr = frag_addr of each block (+ the operand's base)
+template <int PITCH, int NI, int NJ>
+__device__ __forceinline__ void load_frags(Frags<NI, NJ>& f, const char* lds, const int (&raddr)[NJ][2], const int (&saddr)[NI][2], int ks) {
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    f.rh[j] = lds_tr_frag(lds, raddr[j][0] + 4096 * ks, raddr[j][1] + 4096 * ks);
+    f.rl[j] = lds_tr_frag(lds, raddr[j][0] + PITCH + 4096 * ks, raddr[j][1] + PITCH + 4096 * ks);
+  }
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    f.sh[i] = lds_tr_frag(lds, saddr[i][0] + 4096 * ks, saddr[i][1] + 4096 * ks);
+    f.sl[i] = lds_tr_frag(lds, saddr[i][0] + PITCH + 4096 * ks, saddr[i][1] + PITCH + 4096 * ks);
+  }
+}
+
+// acc += s * r on the split planes: sl * rh + sh * rl + sh * rh into one fp32 accumulator
+template <int NI, int NJ>
+__device__ __forceinline__ void mfma3(f32x16 (&acc)[NI][NJ], const Frags<NI, NJ>& f) {
+#pragma unroll
+  for (int i = 0; i < NI; ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      acc[i][j] = mfma32<false>(f.sl[i], f.rh[j], acc[i][j]);  // small terms first
+      acc[i][j] = mfma32<false>(f.sh[i], f.rl[j], acc[i][j]);
+      acc[i][j] = mfma32<false>(f.sh[i], f.rh[j], acc[i][j]);
+    }
+}
+
+// One value of a partial tile leaves the workgroup: added into dW with a hardware fp32 atomic, or — DET (include/avt_ext.h) — STORED
+// to slot `chunk` of a workspace [nchunk][Cout][E] (a.dw, a.ldw = E), whose slots wgrad_reduce.hip sums in ascending order
+template <bool DET>
+__device__ __forceinline__ void sink(const WgArgs& a, int chunk, int co, int e, float v) {
+  if (!(e < a.E && co < a.Cout)) return;
+  if constexpr (DET) a.dw[((int64_t)chunk * a.Cout + co) * a.ldw + e] = v;
+  else unsafeAtomicAdd(a.dw + e + (int64_t)co * a.ldw, v);  // (dw + e first: a lane's 16 values of a block share it)
+}
+
+// The epilogue of both tiles.  A wave's accumulators are 32 x 32 blocks, NJ along the R axis from the workgroup's column wr, NI along
+// the S axis from ws.  D layout: column (lane & 31) = index on the R axis, rows (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) = index on the
+// S axis.  dW is [co][e]: consecutive lanes must walk e for the atomics (or the stores) to coalesce.  Not swapped (R = e), they do.
+// Swapped, lanes would walk co (rows 4 E bytes apart): the tile goes through the LDS first, 128 of the R axis' RT columns at a time,
+// over the operand planes — rows of SW + 1 floats, padded: a wave's 32 co rows hit 32 banks.
+template <bool SWAP, bool DET, int RT, int SW, int THREADS, int NI, int NJ>
+__device__ __forceinline__ void epilogue(const WgArgs& a, char* lds, const f32x16 (&acc)[NI][NJ], int tid, int chunk, int r0, int s0, int wr, int ws) {
+  const int lr = tid & 31, lh = (tid & 63) >> 5;
+  if constexpr (!SWAP) {
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const int e = r0 + wr + j * 32 + lr;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sink<DET>(a, chunk, s0 + ws + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh, e, acc[i][j][r]);
+      }
+  } else {
+    constexpr int ES = SW + 1;
+    float* const stage = reinterpret_cast<float*>(lds);
+    for (int part = 0; part < RT / 128; ++part) {
+      __syncthreads();  // the last fragments (the previous part's staged values) have been read
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const int col = wr + j * 32 - 128 * part + lr;
+        if (RT == 128 || (wr + j * 32) >> 7 == part) {
+#pragma unroll
+          for (int i = 0; i < NI; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) stage[col * ES + ws + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh] = acc[i][j][r];
+        }
+      }
+      __syncthreads();
+      for (int idx = tid; idx < 128 * SW; idx += THREADS) {
+        const int col = idx / SW, el = idx % SW;
+        sink<DET>(a, chunk, r0 + 128 * part + col, s0 + el, stage[col * ES + el]);
+      }
+    }
+  }
 }
 
 // SWAP = false: the 128-wide axis is x's (tap, ci), the BN-wide one dy's co; true: the other way round (Cout > taps * Cin).
-// DET (include/avt_ext.h): the epilogue STORES the partial tile to slot `chunk` of a workspace [nchunk][Cout][E] (a.dw, a.ldw = E)
-// instead of adding it into dW; wgrad_reduce.hip sums the slots in ascending order.  A compile-time flag: the atomic form is unchanged.
+// BUF: buffer loads and byte-offset tables (RowEntry).  DET: the storing epilogue (sink) — a compile-time flag, the atomic form is unchanged.
 template <int BN, bool SWAP, bool BUF, bool DET = false>
 __global__ __launch_bounds__(256, 2) void wgrad_x3_kernel(WgArgs a) {
   constexpr int BM = 128;
@@ -103,14 +242,12 @@ __global__ __launch_bounds__(256, 2) void wgrad_x3_kernel(WgArgs a) {
   constexpr int R_HI = 0, S_HI = 2 * kPlane, YTAB = 4 * kPlane, XTAB = YTAB + 2 * 64 * 4;
   static_assert(NT >= 1 && MT >= 1, "tile");
   extern __shared__ __attribute__((aligned(16))) char lds[];
-  int* const ytab = reinterpret_cast<int*>(lds + YTAB);  // [2][64]: element offset of a position's dy row, -1 = none
-  int* const xtab = reinterpret_cast<int*>(lds + XTAB);  // [2][64][tapcap]: ... of its x row under every tap, -1 = padding
-  int* const ttab = xtab + 2 * 64 * a.tapcap;            // [taps]: dt | dh << 8 | dw << 16, once per workgroup (two divisions per tap and
-                                                         // slab otherwise: the tile is bound by its vector instructions)
+  int* const ytab = reinterpret_cast<int*>(lds + YTAB);  // [2][64]: a position's dy row (RowEntry<BUF>)
+  int* const xtab = reinterpret_cast<int*>(lds + XTAB);  // [2][64][tapcap]: ... its x row under every tap
+  int* const ttab = xtab + 2 * 64 * a.tapcap;            // [taps] (fill_ttab)
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid / WAVES_N, wn = wid % WAVES_N;
-  const int lr = lane & 31, lh = lane >> 5;
 
   // work item: s-tile fastest (neighbours share the 128-wide operand's slabs), then r-tile, chunk — and neighbours in this
   // list run on ONE XCD (blocks are dealt round-robin over the 8 XCDs, each with its own L2): all tiles of a chunk then
@@ -123,7 +260,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_x3_kernel(WgArgs a) {
   const int r0 = tr * BM, s0 = ts * BN;
   const int slab0 = chunk * a.slabs_per_chunk;
   const int slab1 = min(a.nslab, slab0 + a.slabs_per_chunk);
-  const int x0 = SWAP ? s0 : r0, y0 = SWAP ? r0 : s0;  // first (tap, ci) index / first co of this tile
+  const int x0 = SWAP ? s0 : r0;  // first (tap, ci) index of this tile
 
   // the x operand's loads: thread-constant (tap, ci) of each float4
   int xtap[XQ], xci[XQ];
@@ -142,30 +279,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_x3_kernel(WgArgs a) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
 
-  // table entries: element offsets, -1 = none; BUF: byte offsets, kRowOob = none
-  const int none = BUF ? (int)kRowOob : -1;
-  auto enc = [](int elem) { return BUF ? (int)(4u * (unsigned)elem) : elem; };
-  auto decode = [&](int slab, int buf) {  // thread -> position tid & 63, taps (tid >> 6), + 4, + 8, ...
-    const int p = tid & 63, m = slab * 64 + p;
-    const bool ok = m < a.M;
-    if (BUF && a.pointwise) {  // 1x1x1, stride 1, no padding: output position m reads input row m
-      if (tid < 64) {
-        ytab[buf * 64 + p] = ok ? enc(m * a.ldy) : none;
-        xtab[(buf * 64 + p) * a.tapcap] = ok ? enc(m * a.ldx) : none;
-      }
-      return;
-    }
-    const int q1 = (int)fastdiv((uint32_t)(ok ? m : 0), a.dWo), wo = (ok ? m : 0) - q1 * a.Wo;
-    const int q2 = (int)fastdiv((uint32_t)q1, a.dHo), ho = q1 - q2 * a.Ho;
-    const int bb = (int)fastdiv((uint32_t)q2, a.dTo), to = q2 - bb * a.To;
-    if (tid < 64) ytab[buf * 64 + p] = ok ? enc(m * a.ldy) : none;
-    for (int tap = tid >> 6; tap < a.taps; tap += 4) {
-      const int pk = ttab[tap], dt = pk & 255, dh = (pk >> 8) & 255, dw_ = pk >> 16;
-      const int ti = to * a.st - a.pt + dt, hi = ho * a.sh - a.ph + dh, wi = wo * a.sw - a.pw + dw_;
-      const bool in = ok && (unsigned)ti < (unsigned)a.T && (unsigned)hi < (unsigned)a.H && (unsigned)wi < (unsigned)a.W;
-      xtab[(buf * 64 + p) * a.tapcap + tap] = in ? enc((((bb * a.T + ti) * a.H + hi) * a.W + wi) * a.ldx) : none;
-    }
-  };
+  auto decode = [&](int slab) { decode_positions<64, 4, BUF>(a, ytab, xtab, ttab, tid, slab, slab & 1, true); };
   const __amdgpu_buffer_rsrc_t rsx = avt::buffer_rsrc(a.x, a.x_bytes);
   const __amdgpu_buffer_rsrc_t rsy = avt::buffer_rsrc(a.dy, a.dy_bytes);
   float4 rq[RQ], sq[SQ];
@@ -243,67 +357,40 @@ __global__ __launch_bounds__(256, 2) void wgrad_x3_kernel(WgArgs a) {
 #pragma unroll
     for (int q = 0; q < RQ; ++q) {
       const int idx = q * 256 + tid, p = idx >> 5, cq = idx & 31;
-      put4(lds, R_HI, swz(p, cq >> 1) + 8 * (cq & 1), (BUF || ((rmask >> q) & 1u)) ? rq[q] : make_float4(0.f, 0.f, 0.f, 0.f));
+      put4<kPlane>(lds + R_HI, swz(p, cq >> 1) + 8 * (cq & 1), (BUF || ((rmask >> q) & 1u)) ? rq[q] : make_float4(0.f, 0.f, 0.f, 0.f));
     }
 #pragma unroll
     for (int q = 0; q < SQ; ++q) {
       const int idx = q * 256 + tid, p = idx / (BN / 4), cq = idx % (BN / 4);
-      put4(lds, S_HI, swz(p, cq >> 1) + 8 * (cq & 1), (BUF || ((smask >> q) & 1u)) ? sq[q] : make_float4(0.f, 0.f, 0.f, 0.f));
+      put4<kPlane>(lds + S_HI, swz(p, cq >> 1) + 8 * (cq & 1), (BUF || ((smask >> q) & 1u)) ? sq[q] : make_float4(0.f, 0.f, 0.f, 0.f));
     }
   };
-  // transposed-read addresses at k-slice 0 (T10: lane 4q + p of a 16-lane group supplies row q, channels 4p .. 4p + 3 of
-  // the block; groups 0 / 1 = channels 0-15 / 16-31 of the 32-row operand block, groups 2 / 3 the same for positions + 8).
-  // A k-slice is 16 positions = 4096 bytes further: + 16 rows leaves the swizzle's (row & 3) and (row >> 2) & 3 alone.
-  const int g = lane >> 4, tq = (lane & 15) >> 2, tp = lane & 3;
-  int raddr[MT][2], saddr[NT][2];
+  int raddr[MT][2], saddr[NT][2];  // transposed-read addresses at k-slice 0
 #pragma unroll
-  for (int j = 0; j < MT; ++j)
+  for (int h2 = 0; h2 < 2; ++h2) {
 #pragma unroll
-    for (int h2 = 0; h2 < 2; ++h2)
-      raddr[j][h2] = R_HI + swz(8 * (g >> 1) + 4 * h2 + tq, (wm * WTM + j * 32 + 16 * (g & 1)) / 8 + (tp >> 1)) + 8 * (tp & 1);
+    for (int j = 0; j < MT; ++j) raddr[j][h2] = R_HI + frag_addr(lane, wm * WTM + j * 32, h2);
 #pragma unroll
-  for (int i = 0; i < NT; ++i)
-#pragma unroll
-    for (int h2 = 0; h2 < 2; ++h2)
-      saddr[i][h2] = S_HI + swz(8 * (g >> 1) + 4 * h2 + tq, (wn * WN + i * 32 + 16 * (g & 1)) / 8 + (tp >> 1)) + 8 * (tp & 1);
+    for (int i = 0; i < NT; ++i) saddr[i][h2] = S_HI + frag_addr(lane, wn * WN + i * 32, h2);
+  }
   auto compute = [&]() {
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      i32x4 rh[MT], rl[MT], sh_[NT], sl[NT];
-#pragma unroll
-      for (int j = 0; j < MT; ++j) {
-        rh[j] = lds_tr_frag(lds, raddr[j][0] + 4096 * ks, raddr[j][1] + 4096 * ks);
-        rl[j] = lds_tr_frag(lds, raddr[j][0] + kPlane + 4096 * ks, raddr[j][1] + kPlane + 4096 * ks);
-      }
-#pragma unroll
-      for (int i = 0; i < NT; ++i) {
-        sh_[i] = lds_tr_frag(lds, saddr[i][0] + 4096 * ks, saddr[i][1] + 4096 * ks);
-        sl[i] = lds_tr_frag(lds, saddr[i][0] + kPlane + 4096 * ks, saddr[i][1] + kPlane + 4096 * ks);
-      }
-#pragma unroll
-      for (int i = 0; i < NT; ++i)
-#pragma unroll
-        for (int j = 0; j < MT; ++j) {
-          acc[i][j] = mfma32<false>(sl[i], rh[j], acc[i][j]);  // small terms first
-          acc[i][j] = mfma32<false>(sh_[i], rl[j], acc[i][j]);
-          acc[i][j] = mfma32<false>(sh_[i], rh[j], acc[i][j]);
-        }
+      Frags<NT, MT> f;
+      load_frags<kPlane>(f, lds, raddr, saddr, ks);
+      mfma3(acc, f);
     }
   };
 
-  for (int tap = tid; tap < a.taps; tap += 256) {
-    const int t1 = (int)fastdiv((uint32_t)tap, a.dKW), dw_ = tap - t1 * a.KW;
-    const int dt = (int)fastdiv((uint32_t)t1, a.dKH), dh = t1 - dt * a.KH;
-    ttab[tap] = dt | (dh << 8) | (dw_ << 16);
-  }
+  fill_ttab(a, ttab, tid);
   __syncthreads();
   if (slab0 < slab1) {
-    decode(slab0, slab0 & 1);
+    decode(slab0);
     __syncthreads();
     gload(slab0 & 1);
   }
   for (int s = slab0; s < slab1; ++s) {
-    if (s + 1 < slab1) decode(s + 1, (s + 1) & 1);
+    if (s + 1 < slab1) decode(s + 1);
     __syncthreads();  // the previous slab's fragments have been read; the next slab's table is written
     if (!WG_SKIP(1)) lstore();
     __syncthreads();
@@ -311,126 +398,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_x3_kernel(WgArgs a) {
     if (!WG_SKIP(2)) compute();
   }
 
-  // D layout: column (lane & 31) = index on the 128-wide axis, rows (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) = index on the other.
-  // dW is [co][e]: consecutive lanes must walk e for the atomics to coalesce.  Not swapped, they do.  Swapped, lanes walk co
-  // (rows 4 E bytes apart): the tile goes through the LDS first.
-  // DET: a.dw is the workspace [nchunk][Cout][E] (a.ldw = E) and this workgroup's slot is `chunk`
-  if constexpr (!SWAP) {
-#pragma unroll
-    for (int i = 0; i < NT; ++i)
-#pragma unroll
-      for (int j = 0; j < MT; ++j) {
-        const int e = r0 + wm * WTM + j * 32 + lr;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int co = s0 + wn * WN + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          if constexpr (DET) {
-            if (e < a.E && co < a.Cout) a.dw[((int64_t)chunk * a.Cout + co) * a.ldw + e] = acc[i][j][r];
-          } else {
-            if (e < a.E && co < a.Cout) unsafeAtomicAdd(a.dw + (int64_t)co * a.ldw + e, acc[i][j][r]);
-          }
-        }
-      }
-  } else {
-    constexpr int ES = BN + 1;  // floats per staged row (co), padded: a wave's 32 co rows hit 32 banks
-    float* const stage = reinterpret_cast<float*>(lds);
-    __syncthreads();  // the last slab's fragments have been read
-#pragma unroll
-    for (int i = 0; i < NT; ++i)
-#pragma unroll
-      for (int j = 0; j < MT; ++j) {
-        const int col = wm * WTM + j * 32 + lr;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) stage[col * ES + wn * WN + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh] = acc[i][j][r];
-      }
-    __syncthreads();
-    for (int idx = tid; idx < BM * BN; idx += 256) {
-      const int col = idx / BN, el = idx % BN;
-      const int co = r0 + col, e = s0 + el;
-      if constexpr (DET) {
-        if (e < a.E && co < a.Cout) a.dw[((int64_t)chunk * a.Cout + co) * a.ldw + e] = stage[col * ES + el];
-      } else {
-        if (e < a.E && co < a.Cout) unsafeAtomicAdd(a.dw + (int64_t)co * a.ldw + e, stage[col * ES + el]);
-      }
-    }
-  }
-  (void)y0;
-}
-
-
-extern int g_wgrad_buf;
-template <int BN, bool SWAP, bool BUF, bool DET>
-int launch_b(WgArgs& a, int s_count, hipStream_t st);
-
-// The split over positions.  Every workgroup of a launch walks the same number of slabs and `slots` of them run at a time (two per CU
-// for the phase-serial tile, one for the pipelined one), so the launch lasts ceil(grid / slots) rounds of slabs_per_chunk slabs.  Rounds
-// 3-5 took "enough chunks to fill the chip twice" = ceil(2 * slots / tiles) — which makes the grid tiles * chunks >= 2 * slots, and
-// usually a few workgroups MORE: 1025, 1026, 1044 workgroups on 512 slots, 528 and 576 on 256 (res2 b, res3 b, res4 b, res4 a, res5 a
-// at 8 items of config 5) are THREE rounds, the third all but empty — a third of those launches' time (round 6, found on paper:
-// profiles/r06/wgrad_grid_rounds_model.txt).  Here: the chunk count at or below that figure with the least rounds * slabs; ties keep
-// the MORE chunks (two rounds of half the length suffer half as much from a CU that another stream's kernel holds).
-int g_wgrad_rounds = 1;  // (avt_wgrad_x3_set_xl(7) / (8): the round-aware choice off / on — A/Bs)
-static int pick_chunks(int tiles, int nslab, int slots, int min_slabs, bool even) {
-  int chunks = (2 * slots + tiles - 1) / tiles;
-  const int most = nslab / min_slabs > 1 ? nslab / min_slabs : 1;
-  if (chunks > most) chunks = most;
-  if (chunks < 1) chunks = 1;
-  if (!g_wgrad_rounds) return chunks;
-  long best_cost = -1;
-  int best = chunks;
-  for (int c = chunks; c >= 1; --c) {
-    int spc = (nslab + c - 1) / c;
-    if (even) spc += spc & 1;
-    const int nc = (nslab + spc - 1) / spc;
-    const long grid = (long)tiles * nc;
-    const long cost = ((grid + slots - 1) / slots) * spc;
-    if (best_cost < 0 || cost < best_cost) {
-      best_cost = cost;
-      best = c;
-    }
-    if (grid <= slots) break;  // (one round already: fewer chunks only lengthen it)
-  }
-  return best;
-}
-
-template <int BN, bool SWAP, bool DET = false>
-int launch(WgArgs& a, int s_count, hipStream_t st) {
-  const bool fits32 = g_wgrad_buf && a.x_bytes != 0u && a.dy_bytes != 0u && a.ldx < (1 << 17) && a.ldy < (1 << 17);
-  return fits32 ? launch_b<BN, SWAP, true, DET>(a, s_count, st) : launch_b<BN, SWAP, false, DET>(a, s_count, st);
-}
-
-// the phase-serial tile's split (r_tiles set by the caller): s_tiles, slabs_per_chunk, nchunk — from the shapes alone, which is
-// what lets the deterministic entry size its workspace before the launch
-// min_slabs: 16 for the atomic epilogue (below); 2 for the deterministic one, a coalesced store of the tile that no other workgroup
-// contends for — the few-position layers (res5: 49 slabs at 8 items) then split over the chip instead of running as one or two chunks,
-// at the price of their partial tiles' traffic through the workspace (at most ~2 x 512 slots x one 64 KB tile per launch)
-static void plan_chunks(WgArgs& a, int bn, int s_count, int min_slabs = 16) {
-  a.s_tiles = (s_count + bn - 1) / bn;
-  const int tiles = a.r_tiles * a.s_tiles;
-  // split over positions: enough workgroups to fill the chip (256 CUs x 2), but at least 16 slabs each — a workgroup's
-  // epilogue is 128 x BN atomics, and with 3 slabs apiece the pointwise layers spent their time there
-  // (profiles/r02/probe_wgrad_v2.log: 16 TFLOP/s on 256 -> 1024 channels)
-  const int chunks = pick_chunks(tiles, a.nslab, 512, min_slabs, false);
-  a.slabs_per_chunk = (a.nslab + chunks - 1) / chunks;
-  a.nchunk = (a.nslab + a.slabs_per_chunk - 1) / a.slabs_per_chunk;
-}
-
-int64_t g_det_launches[3][2][2];  // [BN 32 / 64 / 128][SWAP][BUF]: avt_conv3d_wgrad_x3_det_launches
-
-template <int BN, bool SWAP, bool BUF, bool DET>
-int launch_b(WgArgs& a, int s_count, hipStream_t st) {
-  if constexpr (!DET) plan_chunks(a, BN, s_count);  // (DET: planned once by det_plan, which sized the workspace from it)
-  const int tiles = a.r_tiles * a.s_tiles;
-  constexpr int lds_small = 4 * kPlane + 2 * 64 * 4 + 2 * 64 * kMaxTaps * 4 + 64 * 4;  // (+ the tap table)
-  constexpr int lds_big = 4 * kPlane + 2 * 64 * 4 + 2 * 64 * kMaxTapsBig * 4 + 64 * 4;
-  static_assert(128 * (BN + 1) * 4 <= lds_small, "the swapped epilogue stages its tile over the operand planes (and tables)");
-  static_assert(lds_small <= 80 * 1024, "two workgroups per CU");
-  const int lds_bytes = a.tapcap > kMaxTaps ? lds_big : lds_small;
-  const int64_t grid = (int64_t)tiles * a.nchunk;
-  AVT_REQUIRE(grid < (1ll << 31), "avt_conv3d_wgrad_x3_f32: grid too large");
-  if constexpr (DET) __atomic_fetch_add(&g_det_launches[BN == 32 ? 0 : (BN == 64 ? 1 : 2)][SWAP][BUF], 1, __ATOMIC_RELAXED);
-  return avt::launch<wgrad_x3_kernel<BN, SWAP, BUF, DET>>(DET ? "avt_conv3d_wgrad_x3_det_sub_f32" : "avt_conv3d_wgrad_x3_f32", dim3((unsigned)grid),
-                                                          dim3(256), lds_big, lds_bytes, st, a);
+  epilogue<SWAP, DET, BM, BN, 256>(a, lds, acc, tid, chunk, r0, s0, wm * WTM, wn * WN);
 }
 
 
@@ -452,17 +420,6 @@ constexpr int XPL = XP * 256;          // one 128-channel plane of a stage: [32 
 constexpr int XSTAGE = 6 * XPL;        // R0 hi | R0 lo | R1 hi | R1 lo | S hi | S lo
 constexpr int XTABS = 2 * XSTAGE;      // ytab [4][32], then xtab [4][32][kMaxTaps]
 
-__device__ __forceinline__ void put4x(char* base, int off, float4 v) {  // put4 with this tile's plane pitch
-  const uint32_t h01 = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){v.x, v.y}, bf16x2));
-  const uint32_t h23 = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){v.z, v.w}, bf16x2));
-  const float r0 = v.x - __builtin_bit_cast(float, h01 << 16), r1 = v.y - __builtin_bit_cast(float, h01 & 0xFFFF0000u);
-  const float r2 = v.z - __builtin_bit_cast(float, h23 << 16), r3 = v.w - __builtin_bit_cast(float, h23 & 0xFFFF0000u);
-  const uint32_t l01 = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){r0, r1}, bf16x2));
-  const uint32_t l23 = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){r2, r3}, bf16x2));
-  *reinterpret_cast<uint2*>(base + off) = make_uint2(h01, h23);
-  *reinterpret_cast<uint2*>(base + XPL + off) = make_uint2(l01, l23);
-}
-
 // SW = width of the S axis' tile: 128 (waves as 4 (R) x 2 (S), 64 x 64 outputs each), 64 (4 x 2, 64 x 32) or 32 (8 x 1, 32 x 32).  The narrow
 // forms are for the layers the 128-wide tile ran LATENCY-bound (64 -> 64 [1,3,3]: 4 us per 64-position slab of which 0.3 us are MFMAs;
 // the 8- to 32-channel fast-pathway layers at 0.9 TB/s): the same pipeline, the S planes of a stage only partly used.
@@ -476,15 +433,14 @@ __global__ __launch_bounds__(512, 1) void wgrad_x3_xl_kernel(WgArgs a) {
   constexpr int RWV = 256 / WR, SWV = SW / WS;            // a wave's outputs: 64 x 64, 64 x 32, 32 x 32
   constexpr int NI = SWV / 32, NJ = RWV / 32;             // 32 x 32 blocks of a wave along S / R
   extern __shared__ __attribute__((aligned(16))) char lds[];
-  unsigned* const ytab = reinterpret_cast<unsigned*>(lds + XTABS);   // [4][32] byte offsets of dy rows
-  unsigned* const xtab = ytab + 4 * XP;                              // [4][32][tapcap] ... of x rows under every tap
-  int* const ttab = reinterpret_cast<int*>(xtab + 4 * XP * kMaxTaps); // [taps]: dt | dh << 8 | dw << 16 (see the 128-wide tile)
+  int* const ytab = reinterpret_cast<int*>(lds + XTABS);  // [4][32] byte offsets of dy rows (RowEntry<true>)
+  int* const xtab = ytab + 4 * XP;                         // [4][32][tapcap] ... of x rows under every tap
+  int* const ttab = xtab + 4 * XP * kMaxTaps;              // [taps] (fill_ttab)
   const __amdgpu_buffer_rsrc_t rsx = avt::buffer_rsrc(a.x, a.x_bytes);
   const __amdgpu_buffer_rsrc_t rsy = avt::buffer_rsrc(a.dy, a.dy_bytes);
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid / WS, wn = wid % WS;
-  const int lr = lane & 31, lh = lane >> 5;
 
   int b_ = avt::xcd_contiguous(blockIdx.x, gridDim.x);
   const int ts = b_ % a.s_tiles; b_ /= a.s_tiles;
@@ -515,27 +471,8 @@ __global__ __launch_bounds__(512, 1) void wgrad_x3_xl_kernel(WgArgs a) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
 
-  auto decode = [&](int step) {  // thread -> position tid & 31, taps (tid >> 5), + 16
-    const int slot = step & 3, p = tid & 31, m = step * XP + p;
-    const bool ok = m < a.M && step < st1;  // (a step past the chunk's end belongs to the next chunk's workgroup: zeros here)
-    if (a.pointwise) {  // 1x1x1, stride 1, no padding: output position m reads input row m (half of the step's launches)
-      if (tid < XP) {
-        ytab[slot * XP + p] = ok ? 4u * (unsigned)(m * a.ldy) : kRowOob;
-        xtab[(slot * XP + p) * a.tapcap] = ok ? 4u * (unsigned)(m * a.ldx) : kRowOob;
-      }
-      return;
-    }
-    const int q1 = (int)fastdiv((uint32_t)(ok ? m : 0), a.dWo), wo = (ok ? m : 0) - q1 * a.Wo;
-    const int q2 = (int)fastdiv((uint32_t)q1, a.dHo), ho = q1 - q2 * a.Ho;
-    const int bb = (int)fastdiv((uint32_t)q2, a.dTo), to = q2 - bb * a.To;
-    if (tid < XP) ytab[slot * XP + p] = ok ? 4u * (unsigned)(m * a.ldy) : kRowOob;
-    for (int tap = tid >> 5; tap < a.taps; tap += 16) {
-      const int pk = ttab[tap], dt = pk & 255, dh = (pk >> 8) & 255, dw_ = pk >> 16;
-      const int ti = to * a.st - a.pt + dt, hi = ho * a.sh - a.ph + dh, wi = wo * a.sw - a.pw + dw_;
-      const bool in = ok && (unsigned)ti < (unsigned)a.T && (unsigned)hi < (unsigned)a.H && (unsigned)wi < (unsigned)a.W;
-      xtab[(slot * XP + p) * a.tapcap + tap] = in ? 4u * (unsigned)((((bb * a.T + ti) * a.H + hi) * a.W + wi) * a.ldx) : kRowOob;
-    }
-  };
+  // (a step past the chunk's end belongs to the next chunk's workgroup: zeros here)
+  auto decode = [&](int step) { decode_positions<XP, 16, true>(a, ytab, xtab, ttab, tid, step, step & 3, step < st1); };
 
   i32x4 rq[2][RQ], sq[2][SQ];
   auto gload = [&](auto set_, int step) {  // all table reads first, then the loads, unconditional (see the 128-wide tile)
@@ -545,12 +482,12 @@ __global__ __launch_bounds__(512, 1) void wgrad_x3_xl_kernel(WgArgs a) {
 #pragma unroll
     for (int q = 0; q < RQ; ++q) {
       const int p = q * 8 + (tid >> 6);
-      rrow[q] = SWAP ? ytab[slot * XP + p] : xtab[(slot * XP + p) * a.tapcap + (xtap < 0 ? 0 : xtap)];
+      rrow[q] = (unsigned)(SWAP ? ytab[slot * XP + p] : xtab[(slot * XP + p) * a.tapcap + (xtap < 0 ? 0 : xtap)]);
     }
 #pragma unroll
     for (int q = 0; q < SQ; ++q) {
       const int p = (q * SPP + sp0) & (XP - 1);
-      srow[q] = SWAP ? xtab[(slot * XP + p) * a.tapcap + (xtap < 0 ? 0 : xtap)] : ytab[slot * XP + p];
+      srow[q] = (unsigned)(SWAP ? xtab[(slot * XP + p) * a.tapcap + (xtap < 0 ? 0 : xtap)] : ytab[slot * XP + p]);
     }
 #pragma unroll
     for (int q = 0; q < RQ; ++q)
@@ -565,76 +502,49 @@ __global__ __launch_bounds__(512, 1) void wgrad_x3_xl_kernel(WgArgs a) {
 #pragma unroll
     for (int q = 0; q < RQ; ++q) {
       const int p = q * 8 + (tid >> 6);
-      put4x(stg + rsub, swz(p, rc >> 1) + 8 * (rc & 1), __builtin_bit_cast(float4, rq[SET][q]));
+      put4<XPL>(stg + rsub, swz(p, rc >> 1) + 8 * (rc & 1), __builtin_bit_cast(float4, rq[SET][q]));
     }
 #pragma unroll
     for (int q = 0; q < SQ; ++q) {
       const int p = q * SPP + sp0;
-      if (SPP <= XP || p < XP) put4x(stg + 4 * XPL, swz(p, scq >> 1) + 8 * (scq & 1), __builtin_bit_cast(float4, sq[SET][q]));
+      if (SPP <= XP || p < XP) put4<XPL>(stg + 4 * XPL, swz(p, scq >> 1) + 8 * (scq & 1), __builtin_bit_cast(float4, sq[SET][q]));
     }
   };
-  // transposed-read addresses inside a stage (k-slice 0; + 4096 per 16 positions): see the 128-wide tile
-  const int g = lane >> 4, tq = (lane & 15) >> 2, tp = lane & 3;
+  // transposed-read addresses inside a stage, k-slice 0 (frag_addr)
   int raddr0_[NJ][2], saddr0_[NI][2];
 #pragma unroll
-  for (int j = 0; j < NJ; ++j)
+  for (int h2 = 0; h2 < 2; ++h2) {
 #pragma unroll
-    for (int h2 = 0; h2 < 2; ++h2) {
+    for (int j = 0; j < NJ; ++j) {
       const int rofs = wm * RWV + j * 32;  // first R channel of the block: plane pair rofs >> 7, channel rofs & 127 inside it
-      raddr0_[j][h2] = (rofs >> 7) * 2 * XPL + swz(8 * (g >> 1) + 4 * h2 + tq, ((rofs & 127) + 16 * (g & 1)) / 8 + (tp >> 1)) + 8 * (tp & 1);
+      raddr0_[j][h2] = (rofs >> 7) * 2 * XPL + frag_addr(lane, rofs & 127, h2);
     }
 #pragma unroll
-  for (int i = 0; i < NI; ++i)
-#pragma unroll
-    for (int h2 = 0; h2 < 2; ++h2)
-      saddr0_[i][h2] = 4 * XPL + swz(8 * (g >> 1) + 4 * h2 + tq, (wn * SWV + i * 32 + 16 * (g & 1)) / 8 + (tp >> 1)) + 8 * (tp & 1);
-  struct Frags {
-    i32x4 rh[NJ], rl[NJ], sh[NI], sl[NI];
-  };
+    for (int i = 0; i < NI; ++i) saddr0_[i][h2] = 4 * XPL + frag_addr(lane, wn * SWV + i * 32, h2);
+  }
   // (the second stage's addresses in registers of their own: stage base + plane + k-slice exceeds the 16-bit offset field of a
   //  ds_read, and the compiler spent one v_add per transposing read — 32 per step — on them)
   int raddr1[NJ][2], saddr1[NI][2];
 #pragma unroll
-  for (int j = 0; j < NJ; ++j)
+  for (int h2 = 0; h2 < 2; ++h2) {
 #pragma unroll
-    for (int h2 = 0; h2 < 2; ++h2) raddr1[j][h2] = raddr0_[j][h2] + XSTAGE;
+    for (int j = 0; j < NJ; ++j) raddr1[j][h2] = raddr0_[j][h2] + XSTAGE;
 #pragma unroll
-  for (int i = 0; i < NI; ++i)
-#pragma unroll
-    for (int h2 = 0; h2 < 2; ++h2) saddr1[i][h2] = saddr0_[i][h2] + XSTAGE;
-  auto fload = [&](Frags& f, auto par_, int ks) {
+    for (int i = 0; i < NI; ++i) saddr1[i][h2] = saddr0_[i][h2] + XSTAGE;
+  }
+  using Fr = Frags<NI, NJ>;
+  auto fload = [&](Fr& f, auto par_, int ks) {
     constexpr int P = decltype(par_)::value;
-    const char* const stg = lds;
-    auto& raddr = *(P ? &raddr1 : &raddr0_);
-    auto& saddr = *(P ? &saddr1 : &saddr0_);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      f.rh[j] = lds_tr_frag(stg, raddr[j][0] + 4096 * ks, raddr[j][1] + 4096 * ks);
-      f.rl[j] = lds_tr_frag(stg, raddr[j][0] + XPL + 4096 * ks, raddr[j][1] + XPL + 4096 * ks);
-    }
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      f.sh[i] = lds_tr_frag(stg, saddr[i][0] + 4096 * ks, saddr[i][1] + 4096 * ks);
-      f.sl[i] = lds_tr_frag(stg, saddr[i][0] + XPL + 4096 * ks, saddr[i][1] + XPL + 4096 * ks);
-    }
+    load_frags<XPL>(f, lds, *(P ? &raddr1 : &raddr0_), *(P ? &saddr1 : &saddr0_), ks);
   };
-  auto fmul = [&](const Frags& f) {
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        acc[i][j] = mfma32<false>(f.sl[i], f.rh[j], acc[i][j]);  // small terms first
-        acc[i][j] = mfma32<false>(f.sh[i], f.rl[j], acc[i][j]);
-        acc[i][j] = mfma32<false>(f.sh[i], f.rh[j], acc[i][j]);
-      }
-  };
+  auto fmul = [&](const Fr& f) { mfma3(acc, f); };
   typedef std::integral_constant<int, 0> S0;
   typedef std::integral_constant<int, 1> S1;
   auto step = [&](auto par_, int s) {  // par = (s - st0) & 1: stage and register set of step s
     constexpr int P = decltype(par_)::value;
     char* nxt = lds + (P ^ 1) * XSTAGE;
     __syncthreads();  // stage P is complete; the other stage's readers (step s - 1) are done; the table of step s + 2 is decoded
-    Frags f0, f1;
+    Fr f0, f1;
     fload(f0, par_, 0);
     fload(f1, par_, 1);
     __builtin_amdgcn_sched_barrier(0);
@@ -650,11 +560,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_x3_xl_kernel(WgArgs a) {
     lstore(std::integral_constant<int, P ^ 1>{}, nxt);  // step s + 1's data, requested during step s - 1
   };
 
-  if (tid < a.taps) {
-    const int t1 = (int)fastdiv((uint32_t)tid, a.dKW), dw_ = tid - t1 * a.KW;
-    const int dt = (int)fastdiv((uint32_t)t1, a.dKH), dh = t1 - dt * a.KH;
-    ttab[tid] = dt | (dh << 8) | (dw_ << 16);
-  }
+  fill_ttab(a, ttab, tid);
   __syncthreads();
   decode(st0);
   decode(st0 + 1);
@@ -668,67 +574,47 @@ __global__ __launch_bounds__(512, 1) void wgrad_x3_xl_kernel(WgArgs a) {
     step(S1{}, s + 1);
   }
 
-  // D layout: column (lane & 31) = index on the R axis, rows (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) = index on the S axis
-  if constexpr (!SWAP) {
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const int e = r0 + wm * RWV + j * 32 + lr;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int co = s0 + wn * SWV + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          if (e < a.E && co < a.Cout) unsafeAtomicAdd(a.dw + (int64_t)co * a.ldw + e, acc[i][j][r]);
-        }
-      }
-  } else {  // lanes would walk co (rows 4 E bytes apart): through the LDS, one half of the R axis (128 co) at a time
-    constexpr int ES = SW + 1;
-    float* const stage = reinterpret_cast<float*>(lds);
-    for (int half = 0; half < 2; ++half) {
-      __syncthreads();
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const int rofs = wm * RWV + j * 32;
-        if ((rofs >> 7) == half) {
-          const int col = (rofs & 127) + lr;
-#pragma unroll
-          for (int i = 0; i < NI; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) stage[col * ES + wn * SWV + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh] = acc[i][j][r];
-        }
-      }
-      __syncthreads();
-      for (int idx = tid; idx < 128 * SW; idx += 512) {
-        const int col = idx / SW, el = idx % SW;
-        const int co = r0 + half * 128 + col, e = s0 + el;
-        if (e < a.E && co < a.Cout) unsafeAtomicAdd(a.dw + (int64_t)co * a.ldw + e, stage[col * ES + el]);
-      }
-    }
-  }
+  epilogue<SWAP, false, 256, SW, 512>(a, lds, acc, tid, chunk, r0, s0, wm * RWV, wn * SWV);
 }
 
-template <bool SWAP, int SW>
-int launch_xl(WgArgs& a, int r_count, int s_count, hipStream_t st) {
-  a.r_tiles = (r_count + 255) / 256;
-  a.s_tiles = (s_count + SW - 1) / SW;
-  const int tiles = a.r_tiles * a.s_tiles;
-  a.nslab = (a.M + XP - 1) / XP;  // steps of 32 positions
-  // one workgroup per CU; at least 32 steps each (the epilogue is 256 x 128 atomics)
-  const int chunks = pick_chunks(tiles, a.nslab, 256, 32, true);
-  a.slabs_per_chunk = (a.nslab + chunks - 1) / chunks;
-  a.slabs_per_chunk += a.slabs_per_chunk & 1;  // (the kernel walks its steps in pairs)
-  a.nchunk = (a.nslab + a.slabs_per_chunk - 1) / a.slabs_per_chunk;
-  constexpr int lds_bytes = XTABS + 4 * XP * 4 + 4 * XP * kMaxTaps * 4 + 64 * 4;  // (+ the tap table)
-  static_assert(128 * 129 * 4 <= XTABS && lds_bytes <= 160 * 1024, "the swapped epilogue's staging and the whole layout fit");
-  const int64_t grid = (int64_t)tiles * a.nchunk;
-  AVT_REQUIRE(grid < (1ll << 31), "avt_conv3d_wgrad_x3_f32: grid too large");
-  return avt::launch<wgrad_x3_xl_kernel<SWAP, SW>>("avt_conv3d_wgrad_x3_f32", dim3((unsigned)grid), dim3(512), lds_bytes, lds_bytes, st, a);
-}
-
-// which tile avt_conv3d_wgrad_x3_f32 launches for (longer axis, shorter axis, taps, positions): 1 = the 256 x 128 tile
-int g_wgrad_xl = 1;  // (avt_wgrad_x3_set_xl: A/B switch for tools and tests; the shipped default is on)
+// ---- the host side: which tile, how many chunks --------------------------------------------------------------------------------------
+int g_wgrad_xl = 1;      // (avt_wgrad_x3_set_xl: A/B switch for tools and tests; the shipped default is on)
 int g_wgrad_buf = 1;     // (avt_wgrad_x3_set_xl(5) / (6): the phase-serial tile's buffer-load form off / on — off is what tensors of 4 GB and more get)
 int g_wgrad_narrow = 1;  // (avt_wgrad_x3_set_xl(3) / (4): the 64- and 32-wide pipelined forms on / off under mode 1)
+int g_wgrad_rounds = 1;  // (avt_wgrad_x3_set_xl(7) / (8): the round-aware choice of pick_chunks off / on — A/Bs)
+int64_t g_det_launches[3][2][2];  // [BN 32 / 64 / 128][SWAP][BUF]: avt_conv3d_wgrad_x3_det_launches
+
+// The split over positions.  Every workgroup of a launch walks the same number of slabs and `slots` of them run at a time (two per CU
+// for the phase-serial tile, one for the pipelined one), so the launch lasts ceil(grid / slots) rounds of slabs_per_chunk slabs.  Rounds
+// 3-5 took "enough chunks to fill the chip twice" = ceil(2 * slots / tiles) — which makes the grid tiles * chunks >= 2 * slots, and
+// usually a few workgroups MORE: 1025, 1026, 1044 workgroups on 512 slots, 528 and 576 on 256 (res2 b, res3 b, res4 b, res4 a, res5 a
+// at 8 items of config 5) are THREE rounds, the third all but empty — a third of those launches' time (round 6, found on paper:
+// profiles/r06/wgrad_grid_rounds_model.txt).  Here: the chunk count at or below that figure with the least rounds * slabs; ties keep
+// the MORE chunks (two rounds of half the length suffer half as much from a CU that another stream's kernel holds).
+static int pick_chunks(int tiles, int nslab, int slots, int min_slabs, bool even) {
+  int chunks = (2 * slots + tiles - 1) / tiles;
+  const int most = nslab / min_slabs > 1 ? nslab / min_slabs : 1;
+  if (chunks > most) chunks = most;
+  if (chunks < 1) chunks = 1;
+  if (!g_wgrad_rounds) return chunks;
+  long best_cost = -1;
+  int best = chunks;
+  for (int c = chunks; c >= 1; --c) {
+    int spc = (nslab + c - 1) / c;
+    if (even) spc += spc & 1;
+    const int nc = (nslab + spc - 1) / spc;
+    const long grid = (long)tiles * nc;
+    const long cost = ((grid + slots - 1) / slots) * spc;
+    if (best_cost < 0 || cost < best_cost) {
+      best_cost = cost;
+      best = c;
+    }
+    if (grid <= slots) break;  // (one round already: fewer chunks only lengthen it)
+  }
+  return best;
+}
+
+// which tile avt_conv3d_wgrad_x3_f32 launches for (longer axis, shorter axis, taps, positions)
 // g_wgrad_xl: 1 = where it measured faster; 2 = every layer, at the S width that fits (tests, probes); 0 = never
 // -> the S width of the pipelined tile to launch (128 / 64 / 32), or 0 for the 128-wide phase-serial tile
 static int wgrad_xl_picked(bool swap, int r_count, int s_count, int taps, int spatial_taps, int m, bool fits32) {
@@ -743,32 +629,91 @@ static int wgrad_xl_picked(bool swap, int r_count, int s_count, int taps, int sp
   return (g_wgrad_narrow && sw == 64 && r_count >= 224) ? 64 : 0;
 }
 
-template <bool SWAP>
-int dispatch(WgArgs& a, int r_count, int s_count, hipStream_t s) {
-  const int xl = wgrad_xl_picked(SWAP, r_count, s_count, a.taps, a.KH * a.KW, a.M, a.x_bytes != 0u && a.dy_bytes != 0u && a.ldx < (1 << 17) && a.ldy < (1 << 17));
-  if (xl == 128) return launch_xl<SWAP, 128>(a, r_count, s_count, s);
-  if (xl == 64) return launch_xl<SWAP, 64>(a, r_count, s_count, s);
-  if (xl == 32) return launch_xl<SWAP, 32>(a, r_count, s_count, s);
-  a.r_tiles = (r_count + 127) / 128;
-  if (s_count <= 32) return launch<32, SWAP>(a, s_count, s);
-  if (s_count <= 64) return launch<64, SWAP>(a, s_count, s);
-  return launch<128, SWAP>(a, s_count, s);
+// both tensors and a row of either fit 32-bit byte offsets (x_bytes / dy_bytes are 0 from kRowOob bytes on): what buffer loads need
+static bool fits32(const WgArgs& a) { return a.x_bytes != 0u && a.dy_bytes != 0u && a.ldx < (1 << 17) && a.ldy < (1 << 17); }
+
+struct WgPlan {
+  bool pipelined;  // the 256-wide pipelined tile, else the 128-wide phase-serial one
+  int width;       // of the S axis' tile: 128 / 64 / 32
+  bool swap;       // the R axis is dy's co (Cout > taps * Cin), else x's (tap, ci): the longer axis takes the wider side of the tile
+  bool buf;        // buffer loads (the pipelined tile has no other form)
+  bool det;        // the storing epilogue
+};
+
+// The one decision: tile family, width, orientation, load form — and the split over positions, written to a (r_tiles, s_tiles, nslab,
+// slabs_per_chunk, nchunk).  From the shapes and the switches alone, which is what lets the deterministic entry size its workspace
+// before the launch.  det: always the phase-serial tile (see avt_conv3d_wgrad_x3_det_sub_f32 below).
+static WgPlan plan(WgArgs& a, bool det) {
+  WgPlan p;
+  p.det = det;
+  p.swap = a.Cout > a.E;
+  const int r_count = p.swap ? a.Cout : a.E, s_count = p.swap ? a.E : a.Cout;
+  const int xl = det ? 0 : wgrad_xl_picked(p.swap, r_count, s_count, a.taps, a.KH * a.KW, a.M, fits32(a));
+  p.pipelined = xl != 0;
+  p.width = xl ? xl : (s_count <= 32 ? 32 : (s_count <= 64 ? 64 : 128));
+  p.buf = p.pipelined || (g_wgrad_buf && fits32(a));
+  const int rt = p.pipelined ? 256 : 128, pos = p.pipelined ? XP : 64;
+  a.r_tiles = (r_count + rt - 1) / rt;
+  a.s_tiles = (s_count + p.width - 1) / p.width;
+  a.nslab = (a.M + pos - 1) / pos;  // slabs of 64 positions / steps of 32
+  // Enough workgroups to fill the chip, but a floor under the slabs of each.  Phase-serial (256 CUs x 2 workgroups): 16 slabs — a
+  // workgroup's epilogue is 128 x BN atomics, and with 3 slabs apiece the pointwise layers spent their time there
+  // (profiles/r02/probe_wgrad_v2.log: 16 TFLOP/s on 256 -> 1024 channels); 2 for the deterministic epilogue, a coalesced store of the
+  // tile that no other workgroup contends for — the few-position layers (res5: 49 slabs at 8 items) then split over the chip instead of
+  // running as one or two chunks, at the price of their partial tiles' traffic through the workspace (at most ~2 x 512 slots x one
+  // 64 KB tile per launch).  Pipelined (one workgroup per CU): 32 steps each (the epilogue is 256 x 128 atomics).
+  const int tiles = a.r_tiles * a.s_tiles;
+  const int chunks = p.pipelined ? pick_chunks(tiles, a.nslab, 256, 32, true) : pick_chunks(tiles, a.nslab, 512, det ? 2 : 16, false);
+  a.slabs_per_chunk = (a.nslab + chunks - 1) / chunks;
+  if (p.pipelined) a.slabs_per_chunk += a.slabs_per_chunk & 1;  // (the kernel walks its steps in pairs)
+  a.nchunk = (a.nslab + a.slabs_per_chunk - 1) / a.slabs_per_chunk;
+  return p;
 }
 
-// The deterministic entry always takes the phase-serial tile (see avt_conv3d_wgrad_x3_det_sub_f32 below).
-// plan_only: fill r_tiles / s_tiles / nchunk and launch nothing (the workspace query and the entry's own size check).
-template <bool SWAP>
-int dispatch_det(WgArgs& a, int r_count, int s_count, bool plan_only, hipStream_t s) {
-  a.r_tiles = (r_count + 127) / 128;
-  const int bn = s_count <= 32 ? 32 : (s_count <= 64 ? 64 : 128);
-  if (plan_only) {
-    plan_chunks(a, bn, s_count, 2);
-    return AVT_OK;
-  }
-  if (bn == 32) return launch<32, SWAP, true>(a, s_count, s);
-  if (bn == 64) return launch<64, SWAP, true>(a, s_count, s);
-  return launch<128, SWAP, true>(a, s_count, s);
+template <int BN, bool SWAP, bool BUF, bool DET>
+int launch_serial(const WgArgs& a, unsigned grid, hipStream_t st) {
+  constexpr int lds_small = 4 * kPlane + 2 * 64 * 4 + 2 * 64 * kMaxTaps * 4 + 64 * 4;  // (+ the tap table)
+  constexpr int lds_big = 4 * kPlane + 2 * 64 * 4 + 2 * 64 * kMaxTapsBig * 4 + 64 * 4;
+  static_assert(128 * (BN + 1) * 4 <= lds_small, "the swapped epilogue stages its tile over the operand planes (and tables)");
+  static_assert(lds_small <= 80 * 1024, "two workgroups per CU");
+  const int lds_bytes = a.tapcap > kMaxTaps ? lds_big : lds_small;
+  if constexpr (DET) __atomic_fetch_add(&g_det_launches[BN == 32 ? 0 : (BN == 64 ? 1 : 2)][SWAP][BUF], 1, __ATOMIC_RELAXED);
+  return avt::launch<wgrad_x3_kernel<BN, SWAP, BUF, DET>>(DET ? "avt_conv3d_wgrad_x3_det_sub_f32" : "avt_conv3d_wgrad_x3_f32", dim3(grid),
+                                                          dim3(256), lds_big, lds_bytes, st, a);
 }
+
+template <bool SWAP, int SW>
+int launch_pipelined(const WgArgs& a, unsigned grid, hipStream_t st) {
+  constexpr int lds_bytes = XTABS + 4 * XP * 4 + 4 * XP * kMaxTaps * 4 + 64 * 4;  // (+ the tap table)
+  static_assert(128 * 129 * 4 <= XTABS && lds_bytes <= 160 * 1024, "the swapped epilogue's staging and the whole layout fit");
+  return avt::launch<wgrad_x3_xl_kernel<SWAP, SW>>("avt_conv3d_wgrad_x3_f32", dim3(grid), dim3(512), lds_bytes, lds_bytes, st, a);
+}
+
+template <class F>
+int with_bool(bool b, F f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+
+// the planned launch: the one place that turns a WgPlan into a kernel instantiation
+int launch(const WgArgs& a, const WgPlan& p, hipStream_t st) {
+  const int64_t grid64 = (int64_t)a.r_tiles * a.s_tiles * a.nchunk;
+  AVT_REQUIRE(grid64 < (1ll << 31), "avt_conv3d_wgrad_x3_f32: grid too large");
+  const unsigned grid = (unsigned)grid64;
+  auto of_width = [&](auto w) {
+    constexpr int W = decltype(w)::value;
+    return with_bool(p.swap, [&](auto swap) {
+      constexpr bool SWAP = decltype(swap)::value;
+      if (p.pipelined) return launch_pipelined<SWAP, W>(a, grid, st);
+      return with_bool(p.buf, [&](auto buf) {
+        return with_bool(p.det, [&](auto det) { return launch_serial<W, SWAP, decltype(buf)::value, decltype(det)::value>(a, grid, st); });
+      });
+    });
+  };
+  switch (p.width) {
+    case 32: return of_width(std::integral_constant<int, 32>{});
+    case 64: return of_width(std::integral_constant<int, 64>{});
+    default: return of_width(std::integral_constant<int, 128>{});
+  }
+}
+
 
 // the checks and derived fields that the atomic and the deterministic entries share, in the atomic entry's order.  ptrs = false: the
 // workspace query, which has the geometry only
@@ -803,17 +748,12 @@ int fill_args(WgArgs& a, bool ptrs, const float* dy, const float* x, float* dw, 
     a.x_bytes = xb < (int64_t)kRowOob ? (unsigned)xb : 0u;  // (0: too large for the pipelined tile's 32-bit byte offsets)
     a.dy_bytes = yb < (int64_t)kRowOob ? (unsigned)yb : 0u;
   }
-  a.nslab = (int)((M + 63) / 64);
   a.dWo = make_fastdiv((uint32_t)a.Wo); a.dHo = make_fastdiv((uint32_t)a.Ho); a.dTo = make_fastdiv((uint32_t)a.To);
   a.dKW = make_fastdiv((uint32_t)kw); a.dKH = make_fastdiv((uint32_t)kh);
   return AVT_OK;
 }
 
 }  // namespace
-
-namespace avt {
-int wgrad_reduce(const char* who, const float* ws, float* dw, int nchunk, int cout, int E, int ldw, hipStream_t st);  // wgrad_reduce.hip
-}
 
 // The general entry: explicit output extent (to, ho, wo; 0 = the symmetric-padding formula), any pt / ph / pw (a slice of a
 // longer filter is the same convolution with a shifted padding), dW rows ldw elements apart, zeroed here or by the caller.
@@ -830,9 +770,7 @@ extern "C" int avt_conv3d_wgrad_x3_sub_f32(const float* dy, const float* x, floa
       return AVT_ERR_LAUNCH;
     }
   }
-  // the longer axis — x's (tap, ci) or dy's co — takes the 128-wide side of the tile
-  if (cout > a.E) return dispatch<true>(a, cout, a.E, s);
-  return dispatch<false>(a, a.E, cout, s);
+  return launch(a, plan(a, false), s);
 }
 
 // ---- the deterministic form (include/avt_ext.h) -----------------------------------------------------------------------------------
@@ -840,11 +778,7 @@ extern "C" int avt_conv3d_wgrad_x3_sub_f32(const float* dy, const float* x, floa
 // ascending-order sum of wgrad_reduce.hip.  The pipelined 256 x 128 tile is NOT used here: its value is the overlap of its phases on
 // the large pointwise layers, where the deterministic mode's cost is the workspace traffic anyway, and one tile family means one
 // epilogue to keep bit-stable and one chunk rule for the workspace query.
-static int64_t det_plan(WgArgs& a) {  // -> workspace bytes; a.nchunk / tiles are set
-  if (a.Cout > a.E) dispatch_det<true>(a, a.Cout, a.E, true, nullptr);
-  else dispatch_det<false>(a, a.E, a.Cout, true, nullptr);
-  return (int64_t)a.nchunk * a.Cout * a.E * 4;
-}
+static int64_t det_ws_bytes(const WgArgs& a) { return (int64_t)a.nchunk * a.Cout * a.E * 4; }  // (a planned)
 
 extern "C" int64_t avt_conv3d_wgrad_x3_det_ws_bytes(int batch, int t, int h, int w, int cin, int cout, int kt, int kh, int kw, int st,
                                                     int sh, int sw, int pt, int ph, int pw, int to, int ho, int wo, int ldx, int ldy,
@@ -852,7 +786,8 @@ extern "C" int64_t avt_conv3d_wgrad_x3_det_ws_bytes(int batch, int t, int h, int
   WgArgs a;
   if (fill_args(a, false, nullptr, nullptr, nullptr, batch, t, h, w, cin, cout, kt, kh, kw, st, sh, sw, pt, ph, pw, to, ho, wo, ldx, ldy, ldw))
     return 0;
-  return det_plan(a);
+  plan(a, true);
+  return det_ws_bytes(a);
 }
 
 extern "C" int64_t avt_conv3d_wgrad_x3_det_launches(int bn, int swap, int buf) {
@@ -865,7 +800,8 @@ extern "C" int avt_conv3d_wgrad_x3_det_sub_f32(const float* dy, const float* x, 
                                                int ho, int wo, int ldx, int ldy, int ldw, void* ws, int64_t ws_bytes, void* stream) {
   WgArgs a;
   if (int rc = fill_args(a, true, dy, x, dw, batch, t, h, w, cin, cout, kt, kh, kw, st, sh, sw, pt, ph, pw, to, ho, wo, ldx, ldy, ldw)) return rc;
-  const int64_t need = det_plan(a);
+  const WgPlan p = plan(a, true);
+  const int64_t need = det_ws_bytes(a);
   AVT_REQUIRE(ws && avt::aligned16(ws), "avt_conv3d_wgrad_x3_det_sub_f32: the workspace must be a 16-byte aligned device pointer");
   AVT_REQUIRE(ws_bytes >= need, "avt_conv3d_wgrad_x3_det_sub_f32: workspace of %lld bytes, %lld needed (avt_conv3d_wgrad_x3_det_ws_bytes)",
               (long long)ws_bytes, (long long)need);
@@ -873,8 +809,7 @@ extern "C" int avt_conv3d_wgrad_x3_det_sub_f32(const float* dy, const float* x, 
   const int ldw_out = a.ldw;
   a.dw = static_cast<float*>(ws);  // the tiles store [chunk][co][e]
   a.ldw = a.E;
-  const int rc = cout > a.E ? dispatch_det<true>(a, cout, a.E, false, s) : dispatch_det<false>(a, a.E, cout, false, s);
-  if (rc != AVT_OK) return rc;
+  if (int rc = launch(a, p, s)) return rc;
   return avt::wgrad_reduce("avt_conv3d_wgrad_x3_det_sub_f32", static_cast<const float*>(ws), dw, a.nchunk, cout, a.E, ldw_out, s);
 }
 

@@ -460,8 +460,8 @@ def conv3d_igemm_x3(x_ptrs, wt_hi, wt_lo, bias, res_ptrs, out_ptrs, ktab, dims, 
 
 
 def _geom(dims, cin, cout, *triples):
-    """The integer run every avt_conv3d_igemm_x3_f32* entry takes after its pointers: b, t, h, w, cin, cout, then the (t, h, w) triples
-    in the entry's own order (kernel, stride, pad, output extent).  (One list and map(int): cheaper on the host than a conversion and a
+    """The integer run every avt_conv3d_igemm_x3_f32* and avt_conv3d_wgrad_x3* entry takes after its pointers: b, t, h, w, cin, cout,
+    then the (t, h, w) triples in the entry's own order (kernel, stride, pad, output extent).  (One list and map(int): cheaper on the host than a conversion and a
     list per field — these wrappers are called ~600 times in a launch-bound training step.)"""
     run = [*dims, cin, cout]
     for tr in triples:
@@ -679,23 +679,19 @@ def weight_planes_t_f32(w3d, sel):
 
 def conv3d_wgrad_x3_f32(dy, x, dw, dims, cin, cout, kernel, stride, pad, ldx, ldy):
     """dw [cout, taps, cin] fp32 = weight gradient of the convolution (csrc/wgrad_x3.hip); dy / x fp32 NDHWC rows; dims = x's (B,T,H,W)."""
-    b, t, h, w = dims
     _dev(dy, "dy", torch.float32)
     _dev(x, "x", torch.float32)
     _dev(dw, "dw", torch.float32)
-    K.avt_conv3d_wgrad_x3_f32(_p(dy), _p(x), _p(dw), int(b), int(t), int(h), int(w), int(cin), int(cout), *[int(k) for k in kernel],
-                              *[int(v) for v in stride], *[int(v) for v in pad], int(ldx), int(ldy), _stream())
+    K.avt_conv3d_wgrad_x3_f32(_p(dy), _p(x), _p(dw), *_geom(dims, cin, cout, kernel, stride, pad), int(ldx), int(ldy), _stream())
 
 
 def conv3d_wgrad_x3_sub_f32(dy, x, dw, dims, cin, cout, kernel, stride, pad, out_dims, ldx, ldy, ldw, zero_dw):
     """The general weight-gradient entry (4-channel inputs, up to 49 taps, explicit output extent, any padding offset, dW a
     column slice of a longer filter): the SlowFast stems; see include/avt.h.  dy / x / dw are device tensors (dw may be a view)."""
-    b, t, h, w = dims
     _dev(dy, "dy", torch.float32)
     _dev(x, "x", torch.float32)
-    K.avt_conv3d_wgrad_x3_sub_f32(_p(dy), _p(x), C.c_void_p(dw.data_ptr()), int(b), int(t), int(h), int(w), int(cin), int(cout),
-                                  *[int(k) for k in kernel], *[int(v) for v in stride], *[int(v) for v in pad],
-                                  *[int(v) for v in out_dims], int(ldx), int(ldy), int(ldw), int(bool(zero_dw)), _stream())
+    K.avt_conv3d_wgrad_x3_sub_f32(_p(dy), _p(x), C.c_void_p(dw.data_ptr()), *_geom(dims, cin, cout, kernel, stride, pad, out_dims),
+                                  int(ldx), int(ldy), int(ldw), int(bool(zero_dw)), _stream())
 
 
 # ---- the deterministic weight gradients (include/avt_ext.h): partial tiles to a workspace, summed in a fixed order ----
@@ -718,24 +714,19 @@ def _det_workspace(need, device, ws, who):
 
 def conv3d_wgrad_x3_det_ws_bytes(dims, cin, cout, kernel, stride, pad, out_dims, ldx, ldy, ldw):
     """Bytes of workspace conv3d_wgrad_x3_det_sub_f32 needs for this geometry; 0 for a geometry the entry refuses."""
-    b, t, h, w = dims
-    return int(_lib.lib().avt_conv3d_wgrad_x3_det_ws_bytes(int(b), int(t), int(h), int(w), int(cin), int(cout), *[int(k) for k in kernel],
-                                                            *[int(v) for v in stride], *[int(v) for v in pad],
-                                                            *[int(v) for v in out_dims], int(ldx), int(ldy), int(ldw)))
+    return int(_lib.lib().avt_conv3d_wgrad_x3_det_ws_bytes(*_geom(dims, cin, cout, kernel, stride, pad, out_dims), int(ldx), int(ldy),
+                                                            int(ldw)))
 
 
 def conv3d_wgrad_x3_det_sub_f32(dy, x, dw, dims, cin, cout, kernel, stride, pad, out_dims, ldx, ldy, ldw, ws=None):
     """conv3d_wgrad_x3_sub_f32 with a fixed summation order: dw's taps * cin columns of each row are WRITTEN (no zeroing; columns beyond
     them are left alone).  ws: a device byte buffer of at least conv3d_wgrad_x3_det_ws_bytes(...) (default: torch.empty per call)."""
-    b, t, h, w = dims
     _dev(dy, "dy", torch.float32)
     _dev(x, "x", torch.float32)
     need = conv3d_wgrad_x3_det_ws_bytes(dims, cin, cout, kernel, stride, pad, out_dims, ldx, ldy, ldw)
     ws = _det_workspace(need, dy.device, ws, "conv3d_wgrad_x3_det_sub_f32")
-    K.avt_conv3d_wgrad_x3_det_sub_f32(_p(dy), _p(x), C.c_void_p(dw.data_ptr()), int(b), int(t), int(h), int(w), int(cin), int(cout),
-                                      *[int(k) for k in kernel], *[int(v) for v in stride], *[int(v) for v in pad],
-                                      *[int(v) for v in out_dims], int(ldx), int(ldy), int(ldw), _p(ws), int(ws.numel() * ws.element_size()),
-                                      _stream())
+    K.avt_conv3d_wgrad_x3_det_sub_f32(_p(dy), _p(x), C.c_void_p(dw.data_ptr()), *_geom(dims, cin, cout, kernel, stride, pad, out_dims),
+                                      int(ldx), int(ldy), int(ldw), _p(ws), int(ws.numel() * ws.element_size()), _stream())
 
 
 def stem_wgrad_x3_det_ws_bytes(batch, t, h, pw, cout, kt, pt):

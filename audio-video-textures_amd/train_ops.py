@@ -1365,24 +1365,15 @@ def _conv_wgrad(ctx, dy, x, weight, stride, padding, kernel, cin, cout):
             #  gradients whose strides equal the parameters' — a permuted view differs in the stride of a one-tap dimension, and a
             #  foreach SGD then ran one launch per tensor: +4.8 ms on a 47 ms step, profiles/r06/train_one_item_arena_sgd_ab.log)
             dw = torch.as_strided(flat, tuple(weight.shape), tuple(weight.stride()))
-            if _DETERMINISTIC:
-                _wgrad_det(dyr, xr, flat, dims, cin, cout, kernel, stride, padding, (0, 0, 0), cin, cout, taps * cin)
-            else:
-                ops.conv3d_wgrad_x3_sub_f32(dyr, xr, flat, dims, cin, cout, kernel, stride, padding, (0, 0, 0), cin, cout, taps * cin, False)
+            _wgrad_x3(dyr, xr, flat, dims, cin, cout, kernel, stride, padding, (0, 0, 0), cin, cout, taps * cin, False)
         else:
             dw = torch.empty_like(weight)  # channels-last strides: memory [cout][kt][kh][kw][cin], the kernel's order
-            if _DETERMINISTIC:
-                _wgrad_det(dyr, xr, dw, dims, cin, cout, kernel, stride, padding, (0, 0, 0), cin, cout, taps * cin)
-            else:
-                ops.conv3d_wgrad_x3_f32(dyr, xr, dw.permute(0, 2, 3, 4, 1), dims, cin, cout, kernel, stride, padding, cin, cout)
+            _wgrad_x3(dyr, xr, dw, dims, cin, cout, kernel, stride, padding, (0, 0, 0), cin, cout, taps * cin, True)
     elif (_WGRAD_X3 and cin % 8 and cin != 3 and x.shape[1] == 8 and taps <= 28 and max(x.numel(), dy.numel()) < (1 << 31) - 64):
         # a few-channel first layer (VGGish: 1 mel channel) on its zero-padded 8-channel copy; the padded taps' gradient is dropped
         CALLS["wgrad_x3"] += 1
         dw8 = torch.empty((cout, 8) + tuple(kernel), dtype=torch.float32, device=dy.device, memory_format=torch.channels_last_3d)
-        if _DETERMINISTIC:
-            _wgrad_det(dyr, xr, dw8, dims, 8, cout, kernel, stride, padding, (0, 0, 0), 8, cout, taps * 8)
-        else:
-            ops.conv3d_wgrad_x3_f32(dyr, xr, dw8.permute(0, 2, 3, 4, 1), dims, 8, cout, kernel, stride, padding, 8, cout)
+        _wgrad_x3(dyr, xr, dw8, dims, 8, cout, kernel, stride, padding, (0, 0, 0), 8, cout, taps * 8, True)
         dw = torch.empty_like(weight)
         dw.copy_(dw8[:, :cin])
     elif (_WGRAD_X3 and _STEM_WGRAD_X3 and cin == 3 and x.shape[1] == 8 and kernel[1] * kernel[2] <= 49 and
@@ -1393,12 +1384,8 @@ def _conv_wgrad(ctx, dy, x, weight, stride, padding, kernel, cin, cout):
         # (deterministic: every slice WRITES its kh * kw * 4 columns of each row, and the kt slices cover the rows: no zeroing)
         acc = (torch.empty if _DETERMINISTIC else torch.zeros)((cout, kt, kh * kw, 4), dtype=torch.float32, device=dy.device)
         for dt in range(kt):
-            if _DETERMINISTIC:
-                _wgrad_det(dyr, xr, acc[:, dt], dims, 4, cout, (1, kh, kw), stride, (padding[0] - dt, padding[1], padding[2]),
-                           (dy.shape[2], dy.shape[3], dy.shape[4]), 8, cout, kt * kh * kw * 4)
-                continue
-            ops.conv3d_wgrad_x3_sub_f32(dyr, xr, acc[:, dt], dims, 4, cout, (1, kh, kw), stride, (padding[0] - dt, padding[1], padding[2]),
-                                        (dy.shape[2], dy.shape[3], dy.shape[4]), 8, cout, kt * kh * kw * 4, False)
+            _wgrad_x3(dyr, xr, acc[:, dt], dims, 4, cout, (1, kh, kw), stride, (padding[0] - dt, padding[1], padding[2]),
+                      (dy.shape[2], dy.shape[3], dy.shape[4]), 8, cout, kt * kh * kw * 4, False)
         CALLS["wgrad_stem_x3"] += 1
         dw = torch.empty_like(weight)
         dw.copy_(acc.view(cout, kt, kh, kw, 4)[..., :3].permute(0, 4, 1, 2, 3))
@@ -1414,10 +1401,17 @@ def _conv_wgrad(ctx, dy, x, weight, stride, padding, kernel, cin, cout):
     return dw
 
 
-def _wgrad_det(dyr, xr, dw, dims, cin, cout, kernel, stride, padding, out_dims, ldx, ldy, ldw):
-    """One deterministic weight-gradient launch pair (tile + fixed-order reduction); dw is written, not accumulated."""
-    CALLS["wgrad_det"] += 1
-    ops.conv3d_wgrad_x3_det_sub_f32(dyr, xr, dw, dims, cin, cout, kernel, stride, padding, out_dims, ldx, ldy, ldw)
+def _wgrad_x3(dyr, xr, dw, dims, cin, cout, kernel, stride, padding, out_dims, ldx, ldy, ldw, fresh):
+    """The one launch of the general weight-gradient kernel (csrc/wgrad_x3.hip).  fresh: dw is a tensor of the filter's own in the kernel's
+    order, [cout][taps][cin], which the plain entry zeroes; else a zeroed accumulator or a column slice of one (the general entry, nothing
+    zeroed).  Deterministic mode: one launch pair (tile + fixed-order reduction) that WRITES dw's taps * cin columns in either case."""
+    if _DETERMINISTIC:
+        CALLS["wgrad_det"] += 1
+        ops.conv3d_wgrad_x3_det_sub_f32(dyr, xr, dw, dims, cin, cout, kernel, stride, padding, out_dims, ldx, ldy, ldw)
+    elif fresh:
+        ops.conv3d_wgrad_x3_f32(dyr, xr, dw.permute(0, 2, 3, 4, 1), dims, cin, cout, kernel, stride, padding, ldx, ldy)
+    else:
+        ops.conv3d_wgrad_x3_sub_f32(dyr, xr, dw, dims, cin, cout, kernel, stride, padding, out_dims, ldx, ldy, ldw, False)
 
 
 def _conv_dgrad(ctx, dy, dalias, x, weight, stride, padding, kernel, cin, cout):
@@ -1645,11 +1639,9 @@ class _StemX3(torch.autograd.Function):
         dy = dy.contiguous(memory_format=torch.channels_last_3d)
         xh, xl = ops.clip_planes_f32(x, ops.X3_BF16)
         CALLS["wgrad_stem_patch"] += 1
-        if _DETERMINISTIC:
-            CALLS["wgrad_det"] += 1
-            dwp = ops.stem_wgrad_x3_det(xh, xl, dy, b, t, h, w // 2, c, kt, kt // 2)
-        else:
-            dwp = ops.stem_wgrad_x3(xh, xl, dy, b, t, h, w // 2, c, kt, kt // 2)  # [c, kt, 7, 4 pair taps, 2 pixels x 4 channels]
+        CALLS["wgrad_det"] += _DETERMINISTIC
+        stem_wgrad = ops.stem_wgrad_x3_det if _DETERMINISTIC else ops.stem_wgrad_x3
+        dwp = stem_wgrad(xh, xl, dy, b, t, h, w // 2, c, kt, kt // 2)  # [c, kt, 7, 4 pair taps, 2 pixels x 4 channels]
         dw = torch.empty_like(weight)
         dw.copy_(dwp.view(c, kt, 7, 8, 4)[:, :, :, 1:, :3].permute(0, 4, 1, 2, 3))  # column tap k = 2 * pair + pixel - 1
         return None, dw
