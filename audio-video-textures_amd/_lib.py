@@ -1,9 +1,10 @@
-"""ctypes loader of the gfx950 C-ABI library (include/avt.h, and the extension entries of include/avt_ext.h).
+"""ctypes loader of the gfx950 C-ABI library (include/avt.h, and the extension entries of include/avt_ext.h and include/avt_ext2.h).
 
 The ABI is written down once, in the header: every csrc/*.hip includes it, so the compiler holds the definitions to it, and the
 ctypes table here is parsed from it (parse_header) — a declaration the parser cannot read is an error, never a default conversion.
 include/avt.h is the pinned table (SIGNATURES, ABI_VERSION); entries added since live in include/avt_ext.h, in the same grammar and
-read by the same parser (EXT_SIGNATURES, EXT_VERSION); lib() and `checked` bind and serve both.
+read by the same parser (EXT_SIGNATURES, EXT_VERSION), and — that table being pinned at its seven names too — in include/avt_ext2.h
+(EXT2_SIGNATURES, EXT2_VERSION: the one-launch state copy); lib() and `checked` bind and serve all three.
 
 There is no CPU fallback: if libavt_hip.so is missing or a call fails, the
 product path raises.  Build it with `python -c "import __graft_entry__ as g; g.build()"`
@@ -18,6 +19,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AVT_HIP_LIB") or os.path.join(_HERE, "libavt_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "avt.h")
 EXT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "avt_ext.h")
+EXT2_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "avt_ext2.h")
 
 
 class AvtError(RuntimeError):
@@ -64,7 +66,14 @@ if set(_EXT_ABI) & set(_ABI):
     raise AvtError("include/avt_ext.h declares again what include/avt.h declares: %s" % ", ".join(sorted(set(_EXT_ABI) & set(_ABI))))
 EXT_SIGNATURES = {name: argtypes for name, (_, argtypes) in _EXT_ABI.items()}  # name -> argtypes, the extension header's entries
 EXT_VERSION = 1  # include/avt_ext.h AVT_EXT_VERSION
-_ALL = dict(_ABI, **_EXT_ABI)
+with open(EXT2_HEADER_PATH) as _f:
+    _EXT2_ABI = parse_header(_f.read())
+if set(_EXT2_ABI) & (set(_ABI) | set(_EXT_ABI)):
+    raise AvtError("include/avt_ext2.h declares again what include/avt.h or include/avt_ext.h declares: %s"
+                   % ", ".join(sorted(set(_EXT2_ABI) & (set(_ABI) | set(_EXT_ABI)))))
+EXT2_SIGNATURES = {name: argtypes for name, (_, argtypes) in _EXT2_ABI.items()}  # name -> argtypes, the second extension header's entries
+EXT2_VERSION = 1  # include/avt_ext2.h AVT_EXT2_VERSION
+_ALL = dict(_ABI, **_EXT_ABI, **_EXT2_ABI)
 
 _lib = None
 
@@ -96,6 +105,14 @@ def lib():
         if handle.avt_ext_version() != EXT_VERSION:
             raise AvtError("libavt_hip.so extension version %d, expected %d: rebuild with `make -C %s`"
                            % (handle.avt_ext_version(), EXT_VERSION, os.path.join(_HERE, "csrc")))
+        for name in _EXT2_ABI:
+            if not hasattr(handle, name):
+                raise AvtError("libavt_hip.so does not export %s (include/avt_ext2.h): rebuild with `make -C %s`"
+                               % (name, os.path.join(_HERE, "csrc")))
+            _bind(getattr(handle, name))
+        if handle.avt_ext2_version() != EXT2_VERSION:
+            raise AvtError("libavt_hip.so second extension version %d, expected %d: rebuild with `make -C %s`"
+                           % (handle.avt_ext2_version(), EXT2_VERSION, os.path.join(_HERE, "csrc")))
         if os.environ.get("AVT_SMALL_TILE", "") == "0":  # (A/Bs: the training convolutions' 64-row tile at small batches off)
             handle.avt_conv_x3_set_small_tile(0)
         if os.environ.get("AVT_WGRAD_ROUNDS", "") == "0":  # (A/Bs: the weight gradient's round-aware split over positions off)

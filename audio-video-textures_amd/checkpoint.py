@@ -16,9 +16,15 @@ Blob grammar of SLOWFAST_8x8_R50 (no non-local blocks):
     t_res<S>_<I>_branch2c_bn_subsample_w / _bn_*  lateral fusion after stage S (2..4)    -> s<S>_fuse
     pred_w, pred_b                                classifier (the reference replaces the head's projection by Identity: dropped)
     *_momentum, lr, model_iter, ...               solver state: dropped
+
+Also here: `AsyncCheckpointWriter`, the background thread that writes the TRAINING checkpoints of main.py --ckpt_async.
 """
+import os
 import pickle
+import queue
 import re
+import shutil
+import threading
 
 import numpy as np
 import torch
@@ -97,3 +103,96 @@ def load_kinetics_slowfast(model, path, strict=True):
             path, len(missing), ", ".join(missing[:3]), len(extra), ", ".join(extra[:3])))
     model.load_state_dict({k: v for k, v in sd.items() if k in own}, strict=False)
     return dropped
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Writing the training checkpoints off the training loop (main.py --ckpt_async).
+def write_atomically(state, path):
+    """torch.save(state) into a temporary file beside `path`, then os.replace: a reader of `path` sees the old file or the new one,
+    never a part of either."""
+    tmp = "%s.tmp.%d" % (path, os.getpid())
+    try:
+        torch.save(state, tmp)
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+
+
+class AsyncCheckpointWriter:
+    """One background thread that turns snapshots into main.save_checkpoint's files:
+
+        w = AsyncCheckpointWriter()
+        w.submit(source, make_state, is_best, filename)   # returns at once
+        w.close()                                         # every file complete, or the thread's exception raised
+
+    source: an object with wait() -> {name: CPU tensor} (train_ops.SnapshotHandle: views into one pinned buffer; its release(), if it
+    has one, is called once the tensors are cloned) or such a dict itself.  The thread CLONES every tensor — torch.save of a view
+    serialises the whole buffer behind it — and calls make_state(clones) -> the checkpoint dict, which it writes to
+    filename + "_latest.pth.tar" through a temporary file and os.replace, then copies to "_best.pth.tar" the same way when is_best: the
+    files, keys and tensors of the synchronous path.  Jobs are written in the order submitted.  An exception in the thread is raised
+    again by the next submit() or by close(); jobs after a failed one are dropped (their sources released)."""
+
+    def __init__(self):
+        self._queue, self._error, self._closed = queue.Queue(), None, False
+        self._thread = threading.Thread(target=self._run, name="avt-checkpoint-writer", daemon=True)
+        self._thread.start()
+
+    def _raise_pending(self):
+        if self._error is not None:
+            err, self._error = self._error, None
+            raise err
+
+    def submit(self, source, make_state, is_best, filename):
+        if self._closed:
+            raise RuntimeError("AsyncCheckpointWriter.submit() after close()")
+        self._raise_pending()
+        self._queue.put((source, make_state, bool(is_best), filename))
+
+    def pending(self):
+        """Jobs submitted and not yet written (or dropped)."""
+        return self._queue.unfinished_tasks
+
+    def drain(self):
+        """Waits until every job submitted so far is written (or has failed: the next submit() or close() tells); the writer stays open."""
+        self._queue.join()
+
+    def close(self):
+        """Waits for every submitted job; raises what the thread raised.  Safe to call twice."""
+        if not self._closed:
+            self._closed = True
+            self._queue.put(None)
+            self._thread.join()
+        self._raise_pending()
+
+    def _run(self):
+        while True:
+            job = self._queue.get()
+            try:
+                if job is None:
+                    return
+                source, make_state, is_best, filename = job
+                release = getattr(source, "release", None)
+                try:
+                    if self._error is not None:
+                        continue  # (a write has failed: nothing after it is written; close() reports)
+                    tensors = source.wait() if hasattr(source, "wait") else source
+                    owned = {k: v.clone() for k, v in tensors.items()}
+                finally:
+                    if release is not None:
+                        release()
+                latest = filename + "_latest.pth.tar"
+                write_atomically(make_state(owned), latest)
+                if is_best:
+                    best, tmp = filename + "_best.pth.tar", "%s_best.pth.tar.tmp.%d" % (filename, os.getpid())
+                    try:
+                        shutil.copyfile(latest, tmp)
+                        os.replace(tmp, best)
+                    finally:
+                        if os.path.exists(tmp):
+                            os.remove(tmp)
+            except BaseException as e:  # noqa: BLE001 (kept for the training thread, which raises it)
+                if self._error is None:
+                    self._error = e
+            finally:
+                self._queue.task_done()

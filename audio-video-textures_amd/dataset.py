@@ -209,6 +209,21 @@ class DeviceSegmentBatcher:
         words = self.state.cpu().numpy().view(np.uint32)
         np.random.set_state(("MT19937", words[:624].copy(), int(words[624]), self._gauss[0], self._gauss[1]))
 
+    def state_dict(self):
+        """What the next batch's negatives depend on: the 625 words of the device MT19937 stream (None before the first upload: the
+        stream then starts from np.random's state) and the host stream's cached gaussian (one D2H of 2.5 KB)."""
+        return {"state": None if self.state is None else self.state.cpu().clone(), "gauss": (int(self._gauss[0]), float(self._gauss[1]))}
+
+    def load_state_dict(self, sd):
+        words = sd["state"]
+        if words is not None:
+            words = torch.as_tensor(words)
+            if words.dtype != torch.int32 or words.numel() != 625:
+                raise ValueError("DeviceSegmentBatcher.load_state_dict: the stream is 625 int32 words, got %s x %d" % (words.dtype, words.numel()))
+            words = words.reshape(625).to(self.dev)
+        self.state = words
+        self._gauss = (int(sd["gauss"][0]), float(sd["gauss"][1]))
+
     def share(self, idx):
         """The rank's items of a global batch: ids [world * per] -> ids [rank * per : (rank + 1) * per] (DataParallel's contiguous
         scatter)."""
@@ -302,6 +317,16 @@ class _DeviceLoader:
 
     def set_epoch(self, epoch):
         self.epoch = int(epoch)
+
+    def state_dict(self):
+        """The loader's seed and epoch (what order() draws from, next to torch's global generator when there is no seed) and the
+        batcher's stream: with the host generators' states, everything the next epoch's batches depend on."""
+        return {"seed": self.seed, "epoch": self.epoch, "batcher": self.bat.state_dict()}
+
+    def load_state_dict(self, sd):
+        self.seed = None if sd["seed"] is None else int(sd["seed"])
+        self.epoch = int(sd["epoch"])
+        self.bat.load_state_dict(sd["batcher"])
 
     def __len__(self):
         n = len(self.bat.ds)

@@ -3,7 +3,9 @@ reference parser with the same names, defaults and types; `main(args, video_name
 loop with the fps -> window/stride override (main.py:511-516) and default checkpoint name (:520-534).
 
 Additions (all optional): --stitch_mode {compat,aligned}, --ref_num_gpus, --enc_dtype {fp32,bf16},
---enc_batch, --train_input {loader,device}, --vcam (the flag validate.py:299 reads but the reference never defines [quirk Q2]).
+--enc_batch, --train_input {loader,device}, --vcam (the flag validate.py:299 reads but the reference never defines [quirk Q2]),
+--ckpt_async (the epoch-end save off the loop: train_ops.StateSnapshot + checkpoint.AsyncCheckpointWriter) and --ckpt_train_state
+(optimizer, scheduler, generators and loader in the checkpoint; --resume then repeats the uninterrupted run).
 Multi-GPU: one process per GPU under torch.distributed.run instead of torch.nn.DataParallel (main.py:420).  --train_input device works
 there too, with or without --train_graph 1: every rank assembles its share of each global batch in its own HBM
 (dataset.DeviceSegmentBatcher(rank, world)), item for item the batch DataParallel would scatter from one NumPy stream.
@@ -90,6 +92,17 @@ def build_parser():
            "a seed bit for bit, eagerly and with --train_graph 1, with either --train_optimizer.  Needs --train_layout ndhwc and "
            "--train_conv x3; across ranks the all-reduce's order is the backend's and nothing is promised.  Default off: the atomic "
            "path, unchanged (not in the reference)")
+    a("--ckpt_async", default=False, action="store_true",
+      help="write the epoch-end checkpoints off the training loop: the state leaves the device in one launch and one copy into pinned "
+           "memory (train_ops.StateSnapshot), a background thread writes *_latest.pth.tar and *_best.pth.tar through temporary files "
+           "and os.replace (checkpoint.AsyncCheckpointWriter); the same files and keys as the default; every file is complete when "
+           "main() returns.  Default off: torch.save on rank 0 inside the loop, as in the reference")
+    a("--ckpt_train_state", default=False, action="store_true",
+      help="checkpoints also carry `train_state` (one more key, which other loaders ignore): the optimizer's and the scheduler's state, "
+           "the torch CPU / device and np.random generator states, the device loader's stream, seed and epoch, the world size and the "
+           "--train_deterministic setting; with --resume all of it is restored (a checkpoint without the key is refused), and with "
+           "--train_deterministic --train_input device (or -j 0) in one process on one GPU a run interrupted after any epoch and resumed "
+           "equals the uninterrupted one bit for bit.  Default off: --resume restores the weights, the epoch and best_loss")
     a("--slomo_ckpt", default="ckpt/SuperSloMo.ckpt", type=str,
       help="SuperSloMo checkpoint (validate.py:183 hard-codes this path); 'random' = seeded weights; missing file = cuts")
     a("-long", "--long", dest="long", default=False, action="store_true", help="unused in the reference")
@@ -148,6 +161,7 @@ parser = build_parser()
 
 def main(args, video_name, itr=0):
     best_loss = 1000000
+    resume_state = None  # the checkpoint's train_state, with --ckpt_train_state --resume
     rank, world, local = avt_dist.init_from_env(backend=getattr(args, "dist_backend", None))
     device = torch.device("cuda", local)
     if world > 1 and torch.distributed.get_backend() == "gloo":  # (gloo ranks may share one GPU; RCCL ranks have one each)
@@ -178,6 +192,17 @@ def main(args, video_name, itr=0):
         best_loss = checkpoint["best_loss"]
         model.load_state_dict(checkpoint["state_dict"])
         print("=> loaded checkpoint '{}' (epoch {})".format(args.resume, checkpoint["epoch"]))
+        if getattr(args, "ckpt_train_state", False) and not args.evaluate and not args.visualize_evaluate:
+            if "train_state" not in checkpoint:
+                from ._lib import AvtError
+
+                raise AvtError("--ckpt_train_state with --resume: '%s' holds no train_state (it was written without the flag); resume "
+                               "it without the flag: weights, epoch and best_loss only" % args.resume)
+            resume_state = checkpoint["train_state"]
+        elif "train_state" in checkpoint:
+            print("=> checkpoint holds a train_state (optimizer, scheduler, generators, loader) that is not used: give "
+                  "--ckpt_train_state to resume the run exactly")
+        del checkpoint
     os.makedirs("./ckpt", exist_ok=True)
     tag = "{}_model_{}_vd_{}_vn_{}_bs_{}_".format(args.logname, args.model_type, os.path.split(args.vdata)[-1],
                                                   video_name, args.batch_size)
@@ -246,21 +271,43 @@ def main(args, video_name, itr=0):
         optimizer = torch.optim.SGD(params=model.parameters(), lr=args.lr, momentum=args.momentum,
                                     weight_decay=args.weight_decay)
     scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=args.lr_steps)
-    print("Training for {} epochs.".format(args.epochs - args.start_epoch))
-    for epoch in range(args.start_epoch, args.epochs):
-        if world > 1:
-            train_loader.sampler.set_epoch(epoch)
-        loss = train(train_loader, model, optimizer, args, epoch, tb_logger)
-        is_best = loss < best_loss
-        best_loss = min(loss, best_loss)
+    with_state = bool(getattr(args, "ckpt_train_state", False))
+    if resume_state is not None:
+        load_train_state(resume_state, optimizer, scheduler, train_loader, device, world, args)
         if rank == 0:
-            net = model.module if hasattr(model, "module") else model
-            save_checkpoint({"epoch": epoch + 1, "arch": args.enc_arch, "state_dict": net.state_dict(),
-                             "best_loss": best_loss}, is_best, os.path.join(args.ckpt, logname))
-        scheduler.step()
-        if loss < 0.07:
-            print("Loss {}. Stopping at epoch {}.".format(loss, epoch))
-            break
+            print("=> restored the training state: optimizer, scheduler (learning rate %s), generators and loader"
+                  % ", ".join("%g" % g["lr"] for g in optimizer.param_groups))
+    writer = None
+    if getattr(args, "ckpt_async", False) and rank == 0:
+        from .checkpoint import AsyncCheckpointWriter
+
+        writer, snapshot = AsyncCheckpointWriter(), None
+    print("Training for {} epochs.".format(args.epochs - args.start_epoch))
+    try:
+        for epoch in range(args.start_epoch, args.epochs):
+            if world > 1:
+                train_loader.sampler.set_epoch(epoch)
+            loss = train(train_loader, model, optimizer, args, epoch, tb_logger)
+            is_best = loss < best_loss
+            best_loss = min(loss, best_loss)
+            if rank == 0:
+                net = model.module if hasattr(model, "module") else model
+                extra = train_state(optimizer, scheduler, train_loader, device, world, args) if with_state else None
+                if writer is None:
+                    state = {"epoch": epoch + 1, "arch": args.enc_arch, "state_dict": net.state_dict(), "best_loss": best_loss}
+                    if extra is not None:
+                        state["train_state"] = extra
+                    save_checkpoint(state, is_best, os.path.join(args.ckpt, logname))
+                else:
+                    snapshot = save_checkpoint_async(writer, snapshot, {"epoch": epoch + 1, "arch": args.enc_arch, "best_loss": best_loss},
+                                                     net.state_dict(), extra, is_best, os.path.join(args.ckpt, logname))
+            scheduler.step()
+            if loss < 0.07:
+                print("Loss {}. Stopping at epoch {}.".format(loss, epoch))
+                break
+    finally:
+        if writer is not None:
+            writer.close()  # (every file complete, or the writer's exception, before main() returns — the stop rule's break included)
 
 
 def build_train_loader(args, dataset_train, device, rank, world):
@@ -316,6 +363,89 @@ def save_checkpoint(state, is_best, filename):
     torch.save(state, filename + "_latest.pth.tar")
     if is_best:
         shutil.copyfile(filename + "_latest.pth.tar", filename + "_best.pth.tar")
+
+
+def save_checkpoint_async(writer, snapshot, head, state_dict, extra, is_best, filename):
+    """save_checkpoint off the loop (--ckpt_async): the model's state_dict and, with a train_state, the optimizer's device tensors leave
+    the device through train_ops.StateSnapshot (one launch, one copy; built at the first save and again whenever a tensor has moved),
+    the writer's thread does the rest.  head: epoch, arch, best_loss.  -> the snapshot, for the next call."""
+    from . import train_ops
+
+    named = [("state_dict." + k, v) for k, v in state_dict.items() if v.is_cuda]
+    opt = extra["optimizer"] if extra is not None else None
+    if opt is not None:
+        named += [("optimizer.%s.%s" % (i, k), v) for i, st in opt["state"].items() for k, v in st.items()
+                  if isinstance(v, torch.Tensor) and v.is_cuda]
+    if snapshot is None or snapshot.key != train_ops.StateSnapshot.key_of(named):
+        snapshot = train_ops.StateSnapshot(named)
+    handle = snapshot.take()
+    metadata = getattr(state_dict, "_metadata", None)
+    keys = [(k, None if v.is_cuda else v.clone()) for k, v in state_dict.items()]  # (host tensors of a state_dict: copied now)
+    if opt is not None:  # the optimizer's state_dict with its device tensors taken out: the thread puts the host copies in
+        extra = dict(extra, optimizer={"state": {i: {k: (None if isinstance(v, torch.Tensor) and v.is_cuda else v) for k, v in st.items()}
+                                                 for i, st in opt["state"].items()},
+                                       "param_groups": opt["param_groups"]})
+
+    def make_state(tensors):
+        sd = type(state_dict)((k, tensors["state_dict." + k] if v is None else v) for k, v in keys)
+        if metadata is not None:
+            sd._metadata = metadata
+        state = {"epoch": head["epoch"], "arch": head["arch"], "state_dict": sd, "best_loss": head["best_loss"]}
+        if extra is not None:
+            if opt is not None:
+                for i, st in extra["optimizer"]["state"].items():
+                    for k in st:
+                        if "optimizer.%s.%s" % (i, k) in tensors:
+                            st[k] = tensors["optimizer.%s.%s" % (i, k)]
+            state["train_state"] = extra
+        return state
+
+    writer.submit(handle, make_state, is_best, filename)
+    return snapshot
+
+
+def train_state(optimizer, scheduler, train_loader, device, world, args):
+    """What --ckpt_train_state adds to a checkpoint: everything epoch e + 1 depends on besides the weights.  Taken where main() saves —
+    after epoch e's train(), BEFORE scheduler.step(): load_train_state makes that step."""
+    import numpy as np
+
+    kind, words, pos, has_gauss, gauss = np.random.get_state()
+    # (tensors and Python scalars only: main()'s torch.load of a checkpoint, as the reference's, unpickles nothing else)
+    numpy_rng = {"kind": str(kind), "words": torch.from_numpy(np.asarray(words, np.int64)), "pos": int(pos), "has_gauss": int(has_gauss),
+                 "gauss": float(gauss)}
+    return {"optimizer": optimizer.state_dict(), "scheduler": scheduler.state_dict(),
+            "torch_rng": torch.get_rng_state(), "device_rng": torch.cuda.get_rng_state(device), "numpy_rng": numpy_rng,
+            "loader": train_loader.state_dict() if hasattr(train_loader, "state_dict") else None,
+            "world": int(world), "train_deterministic": bool(getattr(args, "train_deterministic", False))}
+
+
+def load_train_state(state, optimizer, scheduler, train_loader, device, world, args):
+    """The inverse, on every rank, right before the epoch loop: the optimizer (momentum buffers; torch's SGD and train_ops.ArenaSGD read
+    each other's), the scheduler — stepped once, the step the interrupted run made after it saved, so that the resumed epoch trains at
+    the rate the uninterrupted run gives it — the generators, and the device loader's stream, seed and epoch."""
+    import warnings
+
+    import numpy as np
+    from ._lib import AvtError
+
+    if int(state["world"]) != int(world) or bool(state["train_deterministic"]) != bool(getattr(args, "train_deterministic", False)):
+        print("=> the checkpoint's run had world %d, --train_deterministic %s; this one has world %d, %s: the resumed run will not "
+              "repeat it bit for bit" % (state["world"], state["train_deterministic"], world, bool(getattr(args, "train_deterministic", False))))
+    has_loader = hasattr(train_loader, "load_state_dict")
+    if (state["loader"] is not None) != has_loader:
+        raise AvtError("--ckpt_train_state: the checkpoint was written with --train_input %s, this run uses %s"
+                       % ("device" if state["loader"] is not None else "loader", "device" if has_loader else "loader"))
+    optimizer.load_state_dict(state["optimizer"])
+    scheduler.load_state_dict(state["scheduler"])
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")  # (torch warns that no optimizer.step() came before: it did, in the interrupted run)
+        scheduler.step()
+    if has_loader:
+        train_loader.load_state_dict(state["loader"])
+    rng = state["numpy_rng"]
+    np.random.set_state((rng["kind"], rng["words"].numpy().astype(np.uint32), rng["pos"], rng["has_gauss"], rng["gauss"]))
+    torch.cuda.set_rng_state(state["device_rng"].cpu(), device)
+    torch.set_rng_state(state["torch_rng"].cpu())
 
 
 def cli(argv=None):

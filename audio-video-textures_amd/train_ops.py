@@ -116,7 +116,8 @@ except ImportError:  # (torch < 2.0: callers invalidate by hand, as train() alwa
 CALLS = {"conv_fwd_x3": 0, "dgrad_x3": 0, "dgrad_strided_x3": 0, "wgrad_x3": 0, "wgrad_stem_x3": 0, "bn_fwd": 0, "bn_bwd": 0,
          "miopen_dgrad": 0, "miopen_wgrad": 0, "stem_fwd_patch": 0, "wgrad_stem_patch": 0, "maxpool_hip": 0, "pw_f32": 0,
          "bn_fwd_pre": 0, "bn_bwd_pre": 0, "dgrad_bwdstats": 0, "planes_multi": 0, "maxpool3d_hip": 0, "sgd_multi": 0, "grad_pack_multi": 0,
-         "wgrad_det": 0}  # (wgrad_det: launches of the deterministic weight-gradient entries, counted next to the rows above)
+         "wgrad_det": 0,  # (wgrad_det: launches of the deterministic weight-gradient entries, counted next to the rows above)
+         "state_copy_multi": 0}
 
 
 def _rows(x):
@@ -614,6 +615,27 @@ class ArenaSGD(torch.optim.Optimizer):
             buf = self.state[p]["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
         return buf
 
+    @torch.no_grad()
+    def load_state_dict(self, state_dict):
+        """torch's load_state_dict (torch.optim.SGD's state is interchangeable), after which every momentum buffer again has its
+        parameter's layout: a buffer that came back from a checkpoint with other strides (a channels-last weight's went through the host)
+        is copied into one that has them, so that step() finds what it checks for.  The job table is built anew (new addresses)."""
+        super().load_state_dict(state_dict)
+        self._check_groups()
+        for group in self.param_groups:
+            for p in group["params"]:
+                buf = self.state[p].get("momentum_buffer") if p in self.state else None
+                if buf is None:
+                    continue
+                if buf.dtype != torch.float32 or buf.device != p.device or not _same_layout(buf, p):
+                    if tuple(buf.shape) != tuple(p.shape):
+                        raise _lib.AvtError("ArenaSGD.load_state_dict(): a momentum buffer of shape %s for a parameter of shape %s"
+                                            % (tuple(buf.shape), tuple(p.shape)))
+                    new = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    new.copy_(buf)
+                    self.state[p]["momentum_buffer"] = new
+        self._jobs.forget()
+
     def sync_hyper(self):
         """Make the device copy of (lr, momentum, weight_decay, nesterov) per group equal `param_groups`: one small host-to-device copy
         on the current stream when they differ from what was last uploaded (after scheduler.step(), once per epoch), nothing otherwise.
@@ -838,6 +860,206 @@ def prepare_ranks(model, group=None):
         print("prepare_ranks: %d rank(s), %d parameters and %d buffers broadcast from rank 0; gradients through train_ops.GradExchange, "
               "no DistributedDataParallel wrapper" % (world, len(list(model.parameters())), len(list(model.buffers()))))
     return model
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# The training state off the loop's critical path (main.py --ckpt_async, checkpoint.AsyncCheckpointWriter).  An epoch-end checkpoint
+# that calls torch.save on device tensors copies them to the host one by one, synchronously, and serialises them while every rank
+# waits.  Here the state leaves the training stream in ONE launch (csrc/state_copy.hip: every tensor into one flat device buffer) and
+# one device-to-host copy on a stream of its own into pinned memory; a host thread does the rest.
+_STATE_CHUNK = 16384  # bytes per block (csrc/state_copy.hip kChunk)
+_STATE_JOB = "<2Qq2i"  # AvtStateJob (include/avt_ext2.h)
+
+
+def state_layout(nbytes_list):
+    """-> (offsets, total) in bytes: tensor k of `nbytes_list` starts at a multiple of 16 bytes, total = sum of ceil16(nbytes).  A
+    zero-size tensor takes no room (its offset is the next tensor's)."""
+    offsets, total = [], 0
+    for n in nbytes_list:
+        offsets.append(total)
+        total += (int(n) + 15) // 16 * 16
+    return offsets, total
+
+
+def pack_state_jobs(recs):
+    """recs: (src, dst, nbytes) per tensor — addresses as ints, nbytes > 0 -> (AvtStateJob table as bytes, blk2job int32 array, blocks):
+    job n owns ceil(nbytes / 16384) consecutive blocks from its blk0 (include/avt_ext2.h)."""
+    return _pack_jobs(recs, lambda r: (int(r[2]) + _STATE_CHUNK - 1) // _STATE_CHUNK,
+                      lambda r, b0: struct.pack(_STATE_JOB, r[0], r[1], int(r[2]), b0, 0))
+
+
+def _dense_in_storage_order(t):
+    """True when the tensor's elements fill numel * itemsize consecutive bytes from data_ptr(), each once (contiguous in torch's default
+    format, channels-last, or any permutation of one: what ArenaSGD._check_param accepts and more; a strided or expanded view is not)."""
+    expect = 1
+    for size, stride in sorted(((n, s) for n, s in zip(t.shape, t.stride()) if n > 1), key=lambda v: v[1]):
+        if stride != expect:
+            return False
+        expect *= size
+    return True
+
+
+class SnapshotHandle:
+    """One taken snapshot: wait() blocks the calling host thread until the copy into the pinned buffer has finished and -> {name: CPU
+    view into that buffer} (shape, dtype and strides of the device tensor); release() hands the buffer back to the StateSnapshot (the
+    views are dead from then on: clone what must outlive it)."""
+
+    def __init__(self, owner, slot, event):
+        import threading
+        self._owner, self._slot, self._event, self._released = owner, slot, event, threading.Event()
+
+    def wait(self):
+        if self._released.is_set():
+            raise _lib.AvtError("SnapshotHandle.wait() after release(): the buffer belongs to a later snapshot")
+        self._event.synchronize()
+        return self._owner._views(self._owner._host[self._slot])
+
+    def release(self):
+        self._released.set()
+
+
+class StateSnapshot:
+    """A list of named device tensors — parameters, buffers, momentum buffers — as ONE flat device buffer and two pinned host buffers:
+
+        snap = StateSnapshot(named)          # named: [(name, tensor)] or a dict; layout and both job tables built once
+        h = snap.take()                      # one launch + one async D2H copy; returns at once
+        views = h.wait(); ...; h.release()   # on any host thread
+        snap.restore(h)  /  snap.restore({name: CPU tensor})    # the inverse: host -> flat buffer -> one launch
+
+    Tensors must be dense in storage order (contiguous, channels-last, a contiguous view at any offset); a zero-size tensor gets no job.
+    The tensors are addressed by data_ptr(): the snapshot is valid for as long as they stay where they are (`key` tells)."""
+
+    def __init__(self, named):
+        named = list(named.items()) if isinstance(named, dict) else list(named)
+        if not named:
+            raise _lib.AvtError("StateSnapshot: no tensors")
+        for name, t in named:
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.layout != torch.strided:
+                raise _lib.AvtError("StateSnapshot: %s must be a dense device (HIP) tensor" % name)
+            if t.device != named[0][1].device:
+                raise _lib.AvtError("StateSnapshot: %s is on %s, the first tensor on %s" % (name, t.device, named[0][1].device))
+            if not _dense_in_storage_order(t):
+                raise _lib.AvtError("StateSnapshot: %s is not dense in storage order (shape %s strides %s): a strided view cannot be "
+                                    "copied as bytes" % (name, tuple(t.shape), tuple(t.stride())))
+        self.names = [n for n, _ in named]
+        self.tensors = [t.detach() for _, t in named]
+        self.device = self.tensors[0].device
+        self.nbytes = [t.numel() * t.element_size() for t in self.tensors]
+        self.offsets, self.total = state_layout(self.nbytes)
+        self.key = self.key_of(named)
+        self.flat = torch.zeros(max(self.total, 16), dtype=torch.uint8, device=self.device)
+        assert self.flat.data_ptr() % 16 == 0
+        base = self.flat.data_ptr()
+        live = [(t.data_ptr(), base + o, n) for t, o, n in zip(self.tensors, self.offsets, self.nbytes) if n > 0]
+        self._pack_tab = self._upload(pack_state_jobs(live))
+        self._unpack_tab = self._upload(pack_state_jobs([(d, s, n) for s, d, n in live]))
+        self._host = [torch.zeros(max(self.total, 16), dtype=torch.uint8).pin_memory() for _ in range(2)]
+        self._stage = None                       # restore() from loose CPU tensors: a third pinned buffer, made on first use
+        self._handles = [None, None]             # the handle that owns each host buffer
+        self._next = 0
+        self._copy_stream = torch.cuda.Stream(device=self.device)
+        self.flat.record_stream(self._copy_stream)
+        self._flat_read = None                   # event: the last device-to-host copy has read the flat buffer
+        self._stage_read = None                  # event: the last host-to-device copy has read its pinned source
+
+    @staticmethod
+    def key_of(named):
+        named = list(named.items()) if isinstance(named, dict) else list(named)
+        return tuple((n, t.data_ptr(), t.numel() * t.element_size()) for n, t in named)
+
+    def _upload(self, packed):
+        raw, blk, blocks = packed
+        if blocks == 0:
+            return None
+        assert len(raw) % ops.state_job_bytes() == 0 and ops.state_job_bytes() == struct.calcsize(_STATE_JOB), "AvtStateJob layout"
+        dev = torch.from_numpy(np.frombuffer(raw + blk.tobytes(), dtype=np.uint8).copy()).to(self.device)
+        return dev[:len(raw)], dev[len(raw):].view(torch.int32), blocks
+
+    def _views(self, host):
+        """{name: view of a host byte buffer laid out as the flat buffer, with the device tensor's shape, dtype and strides}."""
+        out = {}
+        for name, t, o, n in zip(self.names, self.tensors, self.offsets, self.nbytes):
+            out[name] = torch.as_strided(host[o:o + n].view(t.dtype), tuple(t.shape), tuple(t.stride())) if n else \
+                torch.empty_strided(tuple(t.shape), tuple(t.stride()), dtype=t.dtype)
+        return out
+
+    def _after_every_stream(self, who):
+        """The current stream, once it has waited for every side stream of the training step (the query encoder's BatchNorm buffers are
+        written on one: main._allreduce_after_every_stream's hazard) and for the default stream."""
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.AvtError("StateSnapshot.%s() under stream capture: a snapshot is taken between steps, not inside a graph" % who)
+        from . import models
+        cur = torch.cuda.current_stream(self.device)
+        for s in models.training_side_streams(self.device) + [torch.cuda.default_stream(self.device)]:
+            if s != cur:
+                cur.wait_stream(s)
+        return cur
+
+    def _launch(self, tab):
+        if tab is not None:
+            ops.state_copy_multi(tab[0], tab[1], tab[2])
+            CALLS["state_copy_multi"] += 1
+
+    @torch.no_grad()
+    def take(self):
+        """Every tensor into the flat buffer (one launch on the current stream, after every training stream), the flat buffer into a
+        pinned host buffer (one async copy on the snapshot's copy stream) -> SnapshotHandle.  With both host buffers still owned by
+        earlier handles it first waits, on the host, for the older one's release(): no snapshot is ever dropped or overwritten."""
+        cur = self._after_every_stream("take")
+        slot = self._next
+        old = self._handles[slot]
+        if old is not None:
+            old._released.wait()
+        if self._flat_read is not None:
+            cur.wait_event(self._flat_read)  # (the previous snapshot's copy still reads the flat buffer)
+        with torch.cuda.device(self.device):
+            self._launch(self._pack_tab)
+            packed = torch.cuda.Event()
+            packed.record(cur)
+            self._copy_stream.wait_event(packed)
+            with torch.cuda.stream(self._copy_stream):
+                self._host[slot].copy_(self.flat, non_blocking=True)
+                done = torch.cuda.Event()
+                done.record(self._copy_stream)
+        self._flat_read = done
+        h = self._handles[slot] = SnapshotHandle(self, slot, done)
+        self._next = 1 - slot
+        return h
+
+    @torch.no_grad()
+    def restore(self, source):
+        """The inverse of take(): `source` a SnapshotHandle not yet released (its pinned buffer) or {name: CPU tensor} for every name
+        (shapes and dtypes of the device tensors; copied, strides and all, into a pinned staging buffer) -> one host-to-device copy of the
+        flat buffer and one launch on the current stream, after every training stream.  The weight-plane cache is stale afterwards."""
+        cur = self._after_every_stream("restore")
+        if isinstance(source, SnapshotHandle):
+            if source._owner is not self:
+                raise _lib.AvtError("StateSnapshot.restore(): the handle belongs to another snapshot")
+            source.wait()
+            host = self._host[source._slot]
+        else:
+            missing = [n for n in self.names if n not in source]
+            if missing:
+                raise _lib.AvtError("StateSnapshot.restore(): no tensor for %s" % ", ".join(missing[:5]))
+            if self._stage_read is not None:
+                self._stage_read.synchronize()  # (the previous restore's copy still reads the staging buffer)
+            if self._stage is None:
+                self._stage = torch.zeros(max(self.total, 16), dtype=torch.uint8).pin_memory()
+            host = self._stage
+            for name, t, view in zip(self.names, self.tensors, self._views(host).values()):
+                src = source[name]
+                if src.is_cuda or src.dtype != t.dtype or tuple(src.shape) != tuple(t.shape):
+                    raise _lib.AvtError("StateSnapshot.restore(): %s must be a CPU tensor of %s %s, got %s %s %s"
+                                        % (name, t.dtype, tuple(t.shape), src.device, src.dtype, tuple(src.shape)))
+                view.copy_(src)
+        if self._flat_read is not None:
+            cur.wait_event(self._flat_read)
+        with torch.cuda.device(self.device):
+            self.flat.copy_(host, non_blocking=True)
+            self._stage_read = torch.cuda.Event()
+            self._stage_read.record(cur)
+            self._launch(self._unpack_tab)
+        invalidate_weight_cache()
 
 
 def weight_cache_is_stale():
