@@ -40,7 +40,8 @@ __device__ __forceinline__ Rgb backwarp(const float4* __restrict__ img, int H, i
   const float wx1 = sub(ix, fx), wy1 = sub(iy, fy);            // ix - ix_nw
   const float wx0 = sub(add(fx, 1.0f), ix), wy0 = sub(add(fy, 1.0f), iy);  // ix_se - ix
   const float nw = mul(wx0, wy0), ne = mul(wx1, wy0), sw = mul(wx0, wy1), se = mul(wx1, wy1);
-  // (a NaN / huge flow makes every corner invalid: zeros, as torch's bounds test does)
+  // (a huge flow makes every corner invalid: zeros, as torch's bounds test does; a NaN flow fails every test too, but its
+  //  NaN weights times the zero taps give NaN, as torch's grid_sample does)
   const bool okx0 = fx >= 0.0f && fx <= (float)(W - 1), okx1 = fx + 1.0f >= 0.0f && fx + 1.0f <= (float)(W - 1);
   const bool oky0 = fy >= 0.0f && fy <= (float)(H - 1), oky1 = fy + 1.0f >= 0.0f && fy + 1.0f <= (float)(H - 1);
   const int x0 = okx0 ? (int)fx : 0, x1 = okx1 ? (int)fx + 1 : 0, y0 = oky0 ? (int)fy : 0, y1 = oky1 ? (int)fy + 1 : 0;
