@@ -1,10 +1,8 @@
-"""ctypes loader of the gfx950 C-ABI library (include/avt.h, and the extension entries of include/avt_ext.h and include/avt_ext2.h).
+"""ctypes loader of the gfx950 C-ABI library (include/avt.h).
 
 The ABI is written down once, in the header: every csrc/*.hip includes it, so the compiler holds the definitions to it, and the
-ctypes table here is parsed from it (parse_header) — a declaration the parser cannot read is an error, never a default conversion.
-include/avt.h is the pinned table (SIGNATURES, ABI_VERSION); entries added since live in include/avt_ext.h, in the same grammar and
-read by the same parser (EXT_SIGNATURES, EXT_VERSION), and — that table being pinned at its seven names too — in include/avt_ext2.h
-(EXT2_SIGNATURES, EXT2_VERSION: the one-launch state copy); lib() and `checked` bind and serve all three.
+ctypes table (SIGNATURES) and the version (ABI_VERSION) here are parsed from it (parse_header, abi_version) — a declaration the
+parser cannot read, a name declared twice or a missing version is an error, never a default conversion.
 
 There is no CPU fallback: if libavt_hip.so is missing or a call fails, the
 product path raises.  Build it with `python -c "import __graft_entry__ as g; g.build()"`
@@ -18,8 +16,6 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # AVT_HIP_LIB selects another build of the same ABI (the diagnostic libavt_hip_stamp.so of `make stamp`); default = the product
 LIB_PATH = os.environ.get("AVT_HIP_LIB") or os.path.join(_HERE, "libavt_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "avt.h")
-EXT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "avt_ext.h")
-EXT2_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "avt_ext2.h")
 
 
 class AvtError(RuntimeError):
@@ -43,11 +39,14 @@ def _ctype(decl, name):
 
 def parse_header(text):
     """The text of include/avt.h -> {name: (restype, [argtypes])} for every avt_* function it declares.  Raises AvtError for a
-    parameter type outside the ABI's vocabulary and for any avt_* name followed by `(` that is not a declaration it has read."""
+    parameter type outside the ABI's vocabulary, for a name declared twice, and for any avt_* name followed by `(` that is not a
+    declaration it has read."""
     code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     code = re.sub(r"^[ \t]*#.*$", "", code, flags=re.M)
     table = {}
     for ret, name, params in _DECL.findall(code):
+        if name in table:
+            raise AvtError("include/avt.h: %s is declared twice" % name)
         params = [] if params.strip() in ("", "void") else params.split(",")
         table[name] = (_ctype(ret, name), [_ctype(p, name) for p in params])
     unread = set(re.findall(r"\b(avt_[a-z0-9_]+)\s*\(", code)) - set(table)
@@ -56,30 +55,25 @@ def parse_header(text):
     return table
 
 
+def abi_version(text):
+    """The header's `#define AVT_ABI_VERSION n` -> n; a header without it is an AvtError."""
+    m = re.search(r"^[ \t]*#[ \t]*define[ \t]+AVT_ABI_VERSION[ \t]+(\d+)\b", text, flags=re.M)
+    if not m:
+        raise AvtError("include/avt.h: no #define AVT_ABI_VERSION")
+    return int(m.group(1))
+
+
 with open(HEADER_PATH) as _f:
-    _ABI = parse_header(_f.read())
+    _TEXT = _f.read()
+_ABI = parse_header(_TEXT)
 SIGNATURES = {name: argtypes for name, (_, argtypes) in _ABI.items() if name != "avt_last_error"}  # name -> argtypes
-ABI_VERSION = 8  # include/avt.h AVT_ABI_VERSION
-with open(EXT_HEADER_PATH) as _f:
-    _EXT_ABI = parse_header(_f.read())
-if set(_EXT_ABI) & set(_ABI):
-    raise AvtError("include/avt_ext.h declares again what include/avt.h declares: %s" % ", ".join(sorted(set(_EXT_ABI) & set(_ABI))))
-EXT_SIGNATURES = {name: argtypes for name, (_, argtypes) in _EXT_ABI.items()}  # name -> argtypes, the extension header's entries
-EXT_VERSION = 1  # include/avt_ext.h AVT_EXT_VERSION
-with open(EXT2_HEADER_PATH) as _f:
-    _EXT2_ABI = parse_header(_f.read())
-if set(_EXT2_ABI) & (set(_ABI) | set(_EXT_ABI)):
-    raise AvtError("include/avt_ext2.h declares again what include/avt.h or include/avt_ext.h declares: %s"
-                   % ", ".join(sorted(set(_EXT2_ABI) & (set(_ABI) | set(_EXT_ABI)))))
-EXT2_SIGNATURES = {name: argtypes for name, (_, argtypes) in _EXT2_ABI.items()}  # name -> argtypes, the second extension header's entries
-EXT2_VERSION = 1  # include/avt_ext2.h AVT_EXT2_VERSION
-_ALL = dict(_ABI, **_EXT_ABI, **_EXT2_ABI)
+ABI_VERSION = abi_version(_TEXT)
 
 _lib = None
 
 
 def _bind(fn):
-    fn.restype, fn.argtypes = _ALL[fn.__name__]
+    fn.restype, fn.argtypes = _ABI[fn.__name__]
     return fn
 
 
@@ -93,26 +87,12 @@ def lib():
                 "there is no CPU fallback for the hot path." % (LIB_PATH, os.path.join(_HERE, "csrc")))
         handle = C.CDLL(LIB_PATH)
         for name in _ABI:
+            if not hasattr(handle, name):
+                raise AvtError("libavt_hip.so does not export %s: rebuild with `make -C %s`" % (name, os.path.join(_HERE, "csrc")))
             _bind(getattr(handle, name))
         if handle.avt_abi_version() != ABI_VERSION:
             raise AvtError("libavt_hip.so ABI version %d, expected %d: rebuild with `make -C %s`"
                            % (handle.avt_abi_version(), ABI_VERSION, os.path.join(_HERE, "csrc")))
-        for name in _EXT_ABI:
-            if not hasattr(handle, name):
-                raise AvtError("libavt_hip.so does not export %s (include/avt_ext.h): rebuild with `make -C %s`"
-                               % (name, os.path.join(_HERE, "csrc")))
-            _bind(getattr(handle, name))
-        if handle.avt_ext_version() != EXT_VERSION:
-            raise AvtError("libavt_hip.so extension version %d, expected %d: rebuild with `make -C %s`"
-                           % (handle.avt_ext_version(), EXT_VERSION, os.path.join(_HERE, "csrc")))
-        for name in _EXT2_ABI:
-            if not hasattr(handle, name):
-                raise AvtError("libavt_hip.so does not export %s (include/avt_ext2.h): rebuild with `make -C %s`"
-                               % (name, os.path.join(_HERE, "csrc")))
-            _bind(getattr(handle, name))
-        if handle.avt_ext2_version() != EXT2_VERSION:
-            raise AvtError("libavt_hip.so second extension version %d, expected %d: rebuild with `make -C %s`"
-                           % (handle.avt_ext2_version(), EXT2_VERSION, os.path.join(_HERE, "csrc")))
         if os.environ.get("AVT_SMALL_TILE", "") == "0":  # (A/Bs: the training convolutions' 64-row tile at small batches off)
             handle.avt_conv_x3_set_small_tile(0)
         if os.environ.get("AVT_WGRAD_ROUNDS", "") == "0":  # (A/Bs: the weight gradient's round-aware split over positions off)
@@ -144,7 +124,7 @@ class _Checked:
     go through lib().  Each function is a ctypes object of its own, so lib()'s raw entries keep returning the status."""
 
     def __getattr__(self, name):  # (first use only: the function then sits in the instance's dict)
-        if name not in _ALL:
+        if name not in _ABI:
             raise AttributeError(name)
         fn = _bind(lib()[name])
         fn.errcheck = _errcheck

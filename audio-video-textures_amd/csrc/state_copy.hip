@@ -1,5 +1,5 @@
 // The training state — every parameter, buffer and momentum buffer — copied between its tensors and ONE flat device buffer in ONE launch
-// (include/avt_ext2.h avt_state_copy_multi): what an epoch-end checkpoint costs the training stream (train_ops.StateSnapshot).  Per
+// (include/avt.h avt_state_copy_multi): what an epoch-end checkpoint costs the training stream (train_ops.StateSnapshot).  Per
 // tensor, the same state is ~650 launches of a few microseconds each for config 5, most of them moving less than a kilobyte.
 //
 // The pattern of sgd.hip and grad_pack.hip: a DEVICE table of jobs — one per tensor — and a block-to-job map; block b owns bytes
@@ -11,8 +11,6 @@
 // last chunk goes through dwords and bytes, so nothing outside [dst, dst + nbytes) is ever written.  Vector loads and stores only: no LDS,
 // no atomics.
 #include "avt_common.h"
-
-#include "../../include/avt_ext2.h"
 
 namespace {
 
@@ -32,7 +30,7 @@ struct StateJob {
   int32_t blk0;        // the job's first block
   int32_t pad;
 };
-static_assert(sizeof(StateJob) == sizeof(AvtStateJob) && sizeof(StateJob) == 32, "AvtStateJob layout (include/avt_ext2.h)");
+static_assert(sizeof(StateJob) == sizeof(AvtStateJob) && sizeof(StateJob) == 32, "AvtStateJob layout (include/avt.h)");
 
 // bytes [0, n) with dword accesses where n allows and bytes for the rest: s and d 4-byte aligned
 __device__ __forceinline__ void copy_dwords(gsrc_t __restrict__ s, gdst_t __restrict__ d, int n, int t) {
@@ -83,8 +81,6 @@ __global__ __launch_bounds__(kThreads) void state_copy_multi_kernel(const StateJ
 }
 
 }  // namespace
-
-extern "C" int avt_ext2_version(void) { return AVT_EXT2_VERSION; }
 
 extern "C" int avt_state_job_bytes(void) { return (int)sizeof(StateJob); }
 

@@ -24,7 +24,6 @@
 // is read once per step and used by every (output row r, row tap dh) with 2 r + dh = j.
 // Roofline: MFMA (3 x the bf16 work; the padded columns 112 -> 128 and the sixth frame tap are issued work, not algorithmic).
 #include "avt_common.h"
-#include "../../include/avt_ext.h"
 #include "launch.h"
 #include "mfma.h"
 #include "split_planes.h"
@@ -85,7 +84,7 @@ struct SwArgs {
 
 // KT frame taps; CO = output channels a workgroup owns per position row in the LDS (8: the fast stem; 16: a 16-channel slice
 // of the slow stem's 64, blockIdx.y walks the slices)
-// DET (include/avt_ext.h): the waves meet in red[] in ordered rounds instead of LDS atomics, and the workgroup STORES its partial
+// DET (include/avt.h): the waves meet in red[] in ordered rounds instead of LDS atomics, and the workgroup STORES its partial
 // filter to slot blockIdx.x of a workspace [gridDim.x][Cout][KT * 7 * 32] (a.dw) for wgrad_reduce.hip to sum in ascending order.
 // A compile-time flag: the atomic form is unchanged.
 template <int KT, int CO, bool DET = false>
@@ -621,7 +620,7 @@ extern "C" int avt_stem_wgrad_x3(const void* x_hi, const void* x_lo, const float
   return cout == 8 ? launch_wgrad<1, 8>(a, s) : launch_wgrad<1, 16>(a, s);
 }
 
-// ---- the deterministic form (include/avt_ext.h): ordered LDS rounds, one workspace slot per workgroup, wgrad_reduce.hip's sum ----
+// ---- the deterministic form (include/avt.h): ordered LDS rounds, one workspace slot per workgroup, wgrad_reduce.hip's sum ----
 // kt = 5 with 16-channel slices would stage 5 x 4 dY rows of 16 channels: 214 KB with the patch, more than a CU's LDS
 static int stem_det_fits(int cout, int kt) {
   AVT_REQUIRE(kt != 5 || cout == 8, "avt_stem_wgrad_x3_det: kt = 5 with cout = %d needs %d bytes of LDS (a CU has %d): cout must be 8", cout,

@@ -1,4 +1,4 @@
-// wgrad_reduce — the second pass of the DETERMINISTIC weight gradients (include/avt_ext.h): the weight-gradient tiles of
+// wgrad_reduce — the second pass of the DETERMINISTIC weight gradients (include/avt.h): the weight-gradient tiles of
 // wgrad_x3.hip and stem_train.hip have stored their partial filters to a workspace [nchunk][cout][E] (one slot per chunk of
 // positions / per persistent workgroup, a function of the shapes alone), and
 //     dW[co][e] = partial[0][co][e] + partial[1][co][e] + ... + partial[nchunk - 1][co][e]
@@ -8,7 +8,6 @@
 // multiple of 4 channels, or 32 per stem row), four independent chunk loads in flight per step.  HBM / L2 bound: the workspace
 // has just been written by the launch in front of this one on the same stream.
 #include "avt_common.h"
-#include "../../include/avt_ext.h"
 #include "wgrad_reduce.h"
 
 namespace {
@@ -72,5 +71,3 @@ int wgrad_reduce(const char* who, const float* ws, float* dw, int nchunk, int co
 }
 
 }  // namespace avt
-
-extern "C" int avt_ext_version(void) { return AVT_EXT_VERSION; }

@@ -18,7 +18,7 @@
 // so an 8-channel 3x3 layer fills 72 of a tile's 128 rows and reads dY once, not 8 of 128 nine times over.
 // Work split: one workgroup = (chunk of slabs, 128 of the longer axis, BN of the shorter one); partial tiles are added into
 // dW with hardware fp32 atomics (dW is zeroed first; the order is not deterministic, as MIOpen's is not — the opt-in deterministic
-// form, include/avt_ext.h, stores the partial tiles to a workspace instead and wgrad_reduce.hip sums them in a fixed order).  Strides,
+// form, include/avt.h, stores the partial tiles to a workspace instead and wgrad_reduce.hip sums them in a fixed order).  Strides,
 // padding and ragged edges live in the table; input channels in multiples of 4 (a float4 per tap), output channels of 8; at most
 // 28 taps (3x3x3, 7x1x1) with two workgroups per CU, up to 49 ([1,7,7]: the SlowFast stems, whose 3 input channels travel as
 // 4 — the stems' weight gradient was the last MIOpen kernel of weight in the step, 77 ms of 730) with one; a frame-tap slice
@@ -28,7 +28,6 @@
 #include <type_traits>
 
 #include "avt_common.h"
-#include "../../include/avt_ext.h"
 #include "launch.h"
 #include "conv_args.h"
 #include "mfma.h"
@@ -178,7 +177,7 @@ __device__ __forceinline__ void mfma3(f32x16 (&acc)[NI][NJ], const Frags<NI, NJ>
     }
 }
 
-// One value of a partial tile leaves the workgroup: added into dW with a hardware fp32 atomic, or — DET (include/avt_ext.h) — STORED
+// One value of a partial tile leaves the workgroup: added into dW with a hardware fp32 atomic, or — DET (include/avt.h) — STORED
 // to slot `chunk` of a workspace [nchunk][Cout][E] (a.dw, a.ldw = E), whose slots wgrad_reduce.hip sums in ascending order
 template <bool DET>
 __device__ __forceinline__ void sink(const WgArgs& a, int chunk, int co, int e, float v) {
@@ -773,7 +772,7 @@ extern "C" int avt_conv3d_wgrad_x3_sub_f32(const float* dy, const float* x, floa
   return launch(a, plan(a, false), s);
 }
 
-// ---- the deterministic form (include/avt_ext.h) -----------------------------------------------------------------------------------
+// ---- the deterministic form (include/avt.h) -----------------------------------------------------------------------------------
 // Two stream-ordered launches: the phase-serial tile with its storing epilogue (slot = chunk, a function of the shapes), then the
 // ascending-order sum of wgrad_reduce.hip.  The pipelined 256 x 128 tile is NOT used here: its value is the overlap of its phases on
 // the large pointwise layers, where the deterministic mode's cost is the workspace traffic anyway, and one tile family means one

@@ -699,13 +699,13 @@ def state_job_bytes():
 
 
 def state_copy_multi(jobs, blk2job, nblocks):
-    """dst[0:nbytes] = src[0:nbytes] over every job of a DEVICE table of AvtStateJob (include/avt_ext2.h) in one launch on the current
+    """dst[0:nbytes] = src[0:nbytes] over every job of a DEVICE table of AvtStateJob (include/avt.h) in one launch on the current
     stream (train_ops.StateSnapshot builds the tables: the training state into one flat buffer, and back)."""
     assert jobs.is_cuda and blk2job.is_cuda and blk2job.dtype == torch.int32 and blk2job.numel() == nblocks
     K.avt_state_copy_multi(_p(jobs), _p(blk2job), int(nblocks), _stream())
 
 
-# ---- the deterministic weight gradients (include/avt_ext.h): partial tiles to a workspace, summed in a fixed order ----
+# ---- the deterministic weight gradients (include/avt.h): partial tiles to a workspace, summed in a fixed order ----
 WGRAD_DET_WS_PEAK = [0]  # bytes of the largest workspace a deterministic weight gradient has taken in this process (tools report it)
 
 

@@ -63,7 +63,7 @@ def conv_mode():
     return "x3" if _CONV_X3 else "fp32"
 
 
-_DETERMINISTIC = 0  # weight gradients through the workspace + fixed-order reduction entries (include/avt_ext.h); set_deterministic
+_DETERMINISTIC = 0  # weight gradients through the workspace + fixed-order reduction entries (include/avt.h); set_deterministic
 
 
 def _no_miopen_in_deterministic_mode():
@@ -868,7 +868,7 @@ def prepare_ranks(model, group=None):
 # waits.  Here the state leaves the training stream in ONE launch (csrc/state_copy.hip: every tensor into one flat device buffer) and
 # one device-to-host copy on a stream of its own into pinned memory; a host thread does the rest.
 _STATE_CHUNK = 16384  # bytes per block (csrc/state_copy.hip kChunk)
-_STATE_JOB = "<2Qq2i"  # AvtStateJob (include/avt_ext2.h)
+_STATE_JOB = "<2Qq2i"  # AvtStateJob (include/avt.h)
 
 
 def state_layout(nbytes_list):
@@ -883,7 +883,7 @@ def state_layout(nbytes_list):
 
 def pack_state_jobs(recs):
     """recs: (src, dst, nbytes) per tensor — addresses as ints, nbytes > 0 -> (AvtStateJob table as bytes, blk2job int32 array, blocks):
-    job n owns ceil(nbytes / 16384) consecutive blocks from its blk0 (include/avt_ext2.h)."""
+    job n owns ceil(nbytes / 16384) consecutive blocks from its blk0 (include/avt.h)."""
     return _pack_jobs(recs, lambda r: (int(r[2]) + _STATE_CHUNK - 1) // _STATE_CHUNK,
                       lambda r, b0: struct.pack(_STATE_JOB, r[0], r[1], int(r[2]), b0, 0))
 

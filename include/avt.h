@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define AVT_ABI_VERSION 8  /* 8: avt_res2_x3, avt_weight_planes_gather_f32, avt_weight_planes_multi (round 6); 7: BatchNorm statistics on the producing convolution's epilogue: avt_conv3d_igemm_x3_f32_stats, avt_bn_train_fwd_pre (round 5); 2: avt_bn_train_fwd gained num_batches_tracked (round 2); 3: avt_bn_train_* take groups (+ beta, relu in bwd), avt_stem_conv_x3 takes frames_per_tile (round 3); 4: avt_stem_conv_pool_x3 removed, avt_stem_conv_x3 / avt_maxpool_hw3s2_ndhwc_x3 take a frame index, avt_stem_conv_x3_merged, avt_lateral_x3 (round 4); 5: avt_bn_train_fwd / _bwd and avt_maxpool_train_fwd / _bwd take the leading dimension of y / dy (round 4); 6: avt_pw_x3_f32 (round 4) */
+#define AVT_ABI_VERSION 9  /* 9: the entries of the two former extension headers (the deterministic weight gradients, the one-launch state copy) folded in, their two extension version entries removed; 8: avt_res2_x3, avt_weight_planes_gather_f32, avt_weight_planes_multi (round 6); 7: BatchNorm statistics on the producing convolution's epilogue: avt_conv3d_igemm_x3_f32_stats, avt_bn_train_fwd_pre (round 5); 2: avt_bn_train_fwd gained num_batches_tracked (round 2); 3: avt_bn_train_* take groups (+ beta, relu in bwd), avt_stem_conv_x3 takes frames_per_tile (round 3); 4: avt_stem_conv_pool_x3 removed, avt_stem_conv_x3 / avt_maxpool_hw3s2_ndhwc_x3 take a frame index, avt_stem_conv_x3_merged, avt_lateral_x3 (round 4); 5: avt_bn_train_fwd / _bwd and avt_maxpool_train_fwd / _bwd take the leading dimension of y / dy (round 4); 6: avt_pw_x3_f32 (round 4) */
 
 typedef enum {
   AVT_OK = 0,
@@ -705,6 +705,44 @@ int avt_stem_wgrad_x3_supported(int h, int pw, int cout, int kt);
 int avt_stem_wgrad_x3(const void* x_hi, const void* x_lo, const float* dy, float* dw, int batch, int t, int h, int pw,
                       int cout, int kt, int pt, void* stream);
 
+/* The DETERMINISTIC weight gradients of the training step (csrc/wgrad_x3.hip, csrc/stem_train.hip, csrc/wgrad_reduce.hip).
+ * avt_conv3d_wgrad_x3_sub_f32 and avt_stem_wgrad_x3 above split the reduction over output positions across workgroups and add
+ * the partial tiles into dW with fp32 atomics, so the summation order — and with it the last bits of dW — changes from run to
+ * run.  The entries below compute the same partial tiles with the same arithmetic, but a workgroup STORES its tile into a
+ * workspace slot that depends on its (chunk, tile) indices alone, and a second launch on the same stream sums the chunks in
+ * ascending order in fp32 and WRITES dW (no zeroing, nothing accumulated).  No workgroup waits for another; the split into
+ * chunks is computed on the host from the shapes alone.  Same inputs + same build -> the same bits, on one device. */
+/* HOST.  Bytes of workspace avt_conv3d_wgrad_x3_det_sub_f32 needs for this geometry (the arguments of that entry that
+ * decide it): chunks * cout * taps * cin * 4.  0 for a geometry that entry refuses (avt_last_error says why). */
+int64_t avt_conv3d_wgrad_x3_det_ws_bytes(int batch, int t, int h, int w, int cin, int cout, int kt, int kh, int kw, int st,
+                                         int sh, int sw, int pt, int ph, int pw, int to, int ho, int wo, int ldx, int ldy,
+                                         int ldw);
+/* avt_conv3d_wgrad_x3_sub_f32 with a fixed summation order: the same arguments without zero_dw — dW's E = taps * cin
+ * columns of each of its cout rows (ldw elements apart; 0 = E) are WRITTEN, columns beyond E are left alone, so the frame-tap
+ * slices of a longer filter are independent calls.  Always the phase-serial tile (128 x {128, 64, 32}; buffer loads as
+ * avt_wgrad_x3_set_xl(5 / 6) says).  ws: device memory, 16-byte aligned, at least avt_conv3d_wgrad_x3_det_ws_bytes(...)
+ * bytes, contents arbitrary on entry, owned by the call until the stream has run it; every byte read from it was written
+ * by this call.  AVT_ERR_ARG before any launch for a NULL, misaligned or short workspace and for everything the atomic
+ * entry refuses. */
+int avt_conv3d_wgrad_x3_det_sub_f32(const float* dy, const float* x, float* dw, int batch, int t, int h, int w, int cin,
+                                    int cout, int kt, int kh, int kw, int st, int sh, int sw, int pt, int ph, int pw, int to,
+                                    int ho, int wo, int ldx, int ldy, int ldw, void* ws, int64_t ws_bytes, void* stream);
+/* HOST.  Launches so far, in this process, of the deterministic tile form (bn = 32 / 64 / 128 outputs on the shorter axis; swap: 1 =
+ * cout on the 128-wide axis; buf: 1 = buffer loads): what tests assert their coverage of the forms with.  -1: no such form. */
+int64_t avt_conv3d_wgrad_x3_det_launches(int bn, int swap, int buf);
+/* HOST.  Bytes of workspace avt_stem_wgrad_x3_det needs: workgroups-per-slice * cout * kt * 7 * 32 * 4.  0 for a shape that
+ * entry refuses. */
+int64_t avt_stem_wgrad_x3_det_ws_bytes(int batch, int t, int h, int pw, int cout, int kt, int pt);
+/* avt_stem_wgrad_x3 with a fixed summation order: a workgroup's eight waves meet in the LDS in ordered rounds
+ * (column block 0 stores, barrier, block 1 adds, ...), the workgroups' partial filters go to the workspace and are summed
+ * in ascending workgroup order.  dw[cout][kt][7][4][8] is WRITTEN: the caller does not zero it.  ws as above.  Shapes as
+ * avt_stem_wgrad_x3_supported, less kt = 5 with cout != 8 (that instance's staging area does not fit a CU's LDS: refused here
+ * with AVT_ERR_ARG instead of failing at the launch). */
+int avt_stem_wgrad_x3_det(const void* x_hi, const void* x_lo, const float* dy, float* dw, int batch, int t, int h, int pw,
+                          int cout, int kt, int pt, void* ws, int64_t ws_bytes, void* stream);
+/* HOST.  Launches so far of the deterministic stem instance (kt 1 / 5; co = 8, or 16 for every multiple of 16).  -1: no such instance. */
+int64_t avt_stem_wgrad_x3_det_launches(int kt, int co);
+
 /* The planes conv_x3 reads, from a training convolution's fp32 weight (re-made after every optimizer step; csrc/stem_train.hip).
  * avt_weight_planes_f32: w [cout][k] fp32 (a channels-last Conv3d weight: k = taps * cin) -> hi / lo [cout][k]; fp16 planes
  *   (plane_dtype 1) are scaled per row by a power of two into [2^9, 2^10) and wscale [cout] receives 1 / scale; bf16 planes
@@ -785,6 +823,27 @@ typedef struct AvtPackJob {
 } AvtPackJob;
 int avt_pack_job_bytes(void);
 int avt_grad_pack_multi(const void* jobs, const int32_t* blk2job, int nblocks, const float* scale, void* stream);
+
+/* The training state — parameters, buffers, momentum buffers — copied between its tensors and ONE flat device buffer in one launch
+ * (csrc/state_copy.hip), so that an epoch-end checkpoint costs the training stream one kernel and one device-to-host copy instead of one
+ * copy per tensor.  A byte-granular copy in the job-table pattern of avt_sgd_multi and avt_grad_pack_multi: `jobs` a DEVICE array of
+ * AvtStateJob, `blk2job` a DEVICE int32 [nblocks]; job j owns blocks blk0 .. blk0 + ceil(nbytes / 16384), block b the bytes
+ * [(b - blk0) * 16384, + 16384) of its job (64-bit offsets).  dst[i] = src[i] for 0 <= i < nbytes; nothing outside [dst, dst + nbytes)
+ * is written.  Where src | dst is 16-byte aligned a lane moves 16 bytes per access, where it is 4-byte aligned a dword, otherwise single
+ * bytes; the nbytes % 16 and nbytes % 4 tails take the narrower access.  src and dst of one job must not overlap; the jobs' destinations
+ * must not overlap each other.  The same entry packs (tensors -> flat buffer) and unpacks (flat buffer -> tensors): only the table
+ * differs.  The caller validates the jobs (dense tensors, the flat buffer's slots); avt_state_job_bytes() = sizeof(AvtStateJob) = 32.
+ * AVT_ERR_ARG before any launch for a NULL pointer, nblocks <= 0, a job table that is not 8-byte aligned or a block map that is not
+ * 4-byte aligned. */
+typedef struct AvtStateJob {
+  const void* src;
+  void* dst;
+  int64_t nbytes;
+  int32_t blk0;          /* first block of the job in the launch */
+  int32_t pad;
+} AvtStateJob;
+int avt_state_job_bytes(void);
+int avt_state_copy_multi(const void* jobs, const int32_t* blk2job, int nblocks, void* stream);
 
 /* MaxPool3d((1,3,3),(1,2,2),(0,1,1)) of the stems in the training step on fp32 NDHWC rows [bt, h, w, c] (csrc/stem_train.hip;
  * the reference: the third-party SlowFast stem under autograd, train.py:114-141).  fwd: y [bt, ho, wo, c] and `tap`

@@ -1,5 +1,6 @@
-"""The C-ABI library loads on a box without a GPU and exports every symbol include/avt.h declares; the ctypes
-binding table is parsed from the header and covers it one to one; host-only entry points behave.  No device calls here."""
+"""The C-ABI library loads on a box without a GPU and exports every symbol include/avt.h declares, and no avt_* function besides; the
+ctypes binding table and the ABI version are parsed from the header and cover it one to one; every entry recorded in
+tests/golden/abi_entries.txt keeps its signature; host-only entry points behave.  No device calls here."""
 import ctypes
 import os
 import re
@@ -15,6 +16,30 @@ def _header_functions(path):
     return sorted(set(re.findall(r"\b(avt_[a-z0-9_]+)\s*\(", src)))
 
 
+def _exported_functions(path):
+    """Names of the functions an ELF64 little-endian shared library defines in its dynamic symbol table (.dynsym / .dynstr)."""
+    import struct
+
+    with open(path, "rb") as f:
+        elf = f.read()
+    assert elf[:6] == b"\x7fELF\x02\x01", "not a little-endian ELF64 file"
+    shoff, = struct.unpack_from("<Q", elf, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", elf, 0x3A)
+    # a section header: name u32, type u32, flags u64, addr u64, offset u64, size u64, link u32, info u32, addralign u64, entsize u64
+    sections = [struct.unpack_from("<IIQQQQIIQQ", elf, shoff + n * shentsize) for n in range(shnum)]
+    SHT_DYNSYM, STT_FUNC, SHN_UNDEF = 11, 2, 0
+    names = set()
+    for _, kind, _, _, offset, size, link, _, _, entsize in sections:
+        if kind != SHT_DYNSYM:
+            continue
+        strtab = sections[link][4]  # .dynstr's file offset
+        for at in range(offset, offset + size, entsize):
+            st_name, st_info, _, st_shndx = struct.unpack_from("<IBBH", elf, at)  # (then value u64, size u64)
+            if st_info & 15 == STT_FUNC and st_shndx != SHN_UNDEF:
+                names.add(elf[strtab + st_name:elf.index(b"\0", strtab + st_name)].decode())
+    return names
+
+
 def test_library_exports_every_declared_symbol(avt):
     names = _header_functions(avt._lib.HEADER_PATH)
     assert len(names) >= 14
@@ -22,7 +47,43 @@ def test_library_exports_every_declared_symbol(avt):
     for n in names:
         assert hasattr(handle, n), "libavt_hip.so does not export %s" % n
     assert sorted(list(avt._lib.SIGNATURES) + ["avt_last_error"]) == names
-    assert avt._lib.lib().avt_abi_version() == avt._lib.ABI_VERSION == 8
+    # ... and the converse: every avt_* function the library defines is declared (no entry point outside the header)
+    exported = sorted(n for n in _exported_functions(avt._lib.LIB_PATH) if n.startswith("avt_"))
+    assert exported == names, sorted(set(exported) ^ set(names))
+
+
+def test_header_binding_and_library_carry_one_version(avt):
+    """The header's #define is the only place the number is written: the binding parses it, the library compiles it in.  A stale library
+    (built from another header) is what disagrees in practice."""
+    with open(avt._lib.HEADER_PATH) as f:
+        text = f.read()
+    defined = [int(v) for v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+AVT_ABI_VERSION[ \t]+(\d+)", text, flags=re.M)]
+    assert len(defined) == 1
+    assert defined[0] == avt._lib.abi_version(text) == avt._lib.ABI_VERSION == avt._lib.lib().avt_abi_version()
+    assert defined[0] >= 9
+    with pytest.raises(avt._lib.AvtError, match="AVT_ABI_VERSION"):
+        avt._lib.abi_version("/* #define AVT_ABI_VERSION in words only */\nint avt_abi_version(void);\n")
+
+
+def _type_names(restype, argtypes):
+    """A signature in the names the binding's vocabulary is written in (c_int64.__name__ itself is the platform's c_long)."""
+    C = ctypes
+    names = {getattr(C, n): n for n in ("c_int", "c_int64", "c_float", "c_double", "c_size_t", "c_void_p", "c_char_p")}
+    return [names[t] for t in [restype] + list(argtypes)]
+
+
+def test_every_recorded_entry_keeps_its_signature(avt):
+    """tests/golden/abi_entries.txt holds one line per entry of include/avt.h — `name restype argtypes...` in ctypes type names, sorted by
+    name — written once as `" ".join([name] + _type_names(*sig))` for every (name, sig) of parse_header(include/avt.h); an entry added
+    later adds its line.  Every recorded entry must still be declared with exactly that signature: a removed or changed one fails by name."""
+    with open(avt._lib.HEADER_PATH) as f:
+        table = avt._lib.parse_header(f.read())
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "abi_entries.txt")) as f:
+        recorded = [line.split() for line in f.read().splitlines()]
+    assert len(recorded) >= 130 and len({r[0] for r in recorded}) == len(recorded)
+    for name, *types in recorded:
+        assert name in table, "include/avt.h no longer declares %s" % name
+        assert _type_names(*table[name]) == types, "%s changed its signature" % name
 
 
 def test_parsed_signatures_of_each_declaration_shape(avt):
@@ -31,7 +92,6 @@ def test_parsed_signatures_of_each_declaration_shape(avt):
     i, i64, vp = C.c_int, C.c_int64, C.c_void_p
     with open(avt._lib.HEADER_PATH) as f:
         table = avt._lib.parse_header(f.read())
-    assert len(table) == 122
     assert table["avt_device_check"] == (i, [C.c_char_p, C.c_size_t])
     assert table["avt_logmel_f64"] == (i, [vp, i, i64, vp, i, i, i, vp, i, C.c_double, vp, vp])
     assert table["avt_pw_x3_f32"] == (i, [vp, i, i, vp, vp, vp, vp, i, vp, i, i, i64, i, vp])  # int64_t m: the 12th argument
@@ -40,10 +100,24 @@ def test_parsed_signatures_of_each_declaration_shape(avt):
     assert table["avt_abi_version"] == (i, [])
     assert table["avt_bn_train_ws_bytes_pre"] == (i64, [i, i, i])
     assert table["avt_last_error"] == (C.c_char_p, [])
+    assert table["avt_conv3d_wgrad_x3_det_ws_bytes"] == (i64, [i] * 21)
+    assert table["avt_conv3d_wgrad_x3_det_sub_f32"] == (i, [vp, vp, vp] + [i] * 21 + [vp, i64, vp])
+    assert table["avt_stem_wgrad_x3_det_ws_bytes"] == (i64, [i] * 7)
+    assert table["avt_stem_wgrad_x3_det"] == (i, [vp, vp, vp, vp] + [i] * 7 + [vp, i64, vp])
+    assert table["avt_state_job_bytes"] == (i, []) and table["avt_state_copy_multi"] == (i, [vp, vp, i, vp])
+    # the atomic entries the deterministic ones mirror: the same arguments, less zero_dw, plus (ws, ws_bytes)
+    sub, det = table["avt_conv3d_wgrad_x3_sub_f32"][1], table["avt_conv3d_wgrad_x3_det_sub_f32"][1]
+    assert det == sub[:-2] + [vp, i64] + sub[-1:]
+    stem, sdet = table["avt_stem_wgrad_x3"][1], table["avt_stem_wgrad_x3_det"][1]
+    assert sdet == stem[:-1] + [vp, i64] + stem[-1:]
     assert {n: a for n, (_, a) in table.items() if n != "avt_last_error"} == avt._lib.SIGNATURES
-    fn = avt._lib.lib().avt_pw_x3_f32
-    assert (fn.restype, list(fn.argtypes)) == table["avt_pw_x3_f32"]
-    assert avt._lib.lib().avt_bn_train_ws_bytes_pre.restype is i64 and avt._lib.lib().avt_last_error.restype is C.c_char_p
+    lib, checked = avt._lib.lib(), avt._lib.checked
+    for name in ("avt_pw_x3_f32", "avt_conv3d_wgrad_x3_det_ws_bytes", "avt_state_copy_multi"):  # lib() binds the header's types
+        fn = getattr(lib, name)
+        assert (fn.restype, list(fn.argtypes)) == table[name]
+    assert list(checked.avt_stem_wgrad_x3_det.argtypes) == table["avt_stem_wgrad_x3_det"][1]  # ... and so does `checked`
+    assert list(checked.avt_state_copy_multi.argtypes) == table["avt_state_copy_multi"][1]
+    assert lib.avt_bn_train_ws_bytes_pre.restype is i64 and lib.avt_last_error.restype is C.c_char_p
 
 
 @pytest.mark.parametrize("text", [
@@ -57,6 +131,13 @@ def test_parsed_signatures_of_each_declaration_shape(avt):
 def test_parser_refuses_what_it_cannot_read(avt, text):
     with pytest.raises(avt._lib.AvtError):
         avt._lib.parse_header(text)
+
+
+def test_a_name_declared_twice_is_an_error(avt):
+    """What the dict of declarations would keep silently — the last one — is refused, whether or not the two agree."""
+    for text in ("int avt_a(int n);\nint avt_b(void);\nint avt_a(int n);", "int avt_a(int n);\nint64_t avt_a(const float* x, int n);"):
+        with pytest.raises(avt._lib.AvtError, match="avt_a is declared twice"):
+            avt._lib.parse_header(text)
 
 
 def test_parser_reads_arrays_and_unnamed_parameters(avt):

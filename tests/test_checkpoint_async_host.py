@@ -32,7 +32,7 @@ def test_state_layout_slots_are_aligned_and_disjoint(avt):
 def test_job_table_packer_writes_the_headers_struct(avt):
     from avtex import train_ops
 
-    class AvtStateJob(ctypes.Structure):  # include/avt_ext2.h
+    class AvtStateJob(ctypes.Structure):  # include/avt.h
         _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("nbytes", ctypes.c_int64), ("blk0", ctypes.c_int32),
                     ("pad", ctypes.c_int32)]
 

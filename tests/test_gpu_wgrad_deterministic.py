@@ -1,4 +1,4 @@
-"""The deterministic weight gradients (include/avt_ext.h; csrc/wgrad_x3.hip and csrc/stem_train.hip with the storing epilogue,
+"""The deterministic weight gradients (include/avt.h; csrc/wgrad_x3.hip and csrc/stem_train.hip with the storing epilogue,
 csrc/wgrad_reduce.hip): per layer case, on fp32 NDHWC rows with seeded inputs,
   (a) two calls on the same inputs are bit-equal — the workspace filled with NaN and dW with a sentinel before each call, and dW's
       columns beyond E keep the sentinel where ldw > E;
