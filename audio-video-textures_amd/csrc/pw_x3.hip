@@ -14,9 +14,12 @@
 // are split into channel chunks handled by workgroups that are adjacent in the grid AND on one XCD (block b and b + 8
 // share an XCD), so the chunks' re-reads of the same input rows meet in that XCD's L2.
 // v_mfma_f32_16x16x32_{f16,bf16}: three passes per product, wl*xh + wh*xl + wh*xh, fp32 accumulate.
+#include <limits.h>
 #include <stdlib.h>
 
+#include <iterator>
 #include <type_traits>
+#include <utility>
 
 #include "avt_common.h"
 #include "launch.h"
@@ -62,6 +65,139 @@ constexpr int PX_NW = 8;
 #define PW_IL 2  // accumulators interleaved in the MFMA loop (NT1 is even)
 #endif
 
+// ---- the pieces the kernels share ----------------------------------------------------------------------------------------------------
+
+// A wave's tile of 16 positions, as a lane sees it: does its position exist (`ok`: the stores' guard), the row it loads (`pc`: the
+// last row where the tile is ragged), and its byte offset into a fragment
+struct Tile {
+  bool ok;
+  int lofs;
+  int64_t pc;
+};
+
+__device__ __forceinline__ Tile tile_of(int tile, int lane, int M) {
+  const int p = tile * 16 + (lane & 15);
+  const bool ok = p < M;
+  int lofs = lane * 16;  // opaque per tile: keeps the loop-invariant fragment reads from being hoisted into registers
+  asm volatile("" : "+v"(lofs));
+  return Tile{ok, lofs, ok ? p : M - 1};
+}
+
+// the 8-channel chunk of k-step ks that k-group q reads: past the row's end the weights are zero: any finite value will do
+__device__ __forceinline__ int row_chunk(int ks, int q, int k1c) {
+  const int ch = 4 * ks + q;
+  return ch < k1c ? ch : k1c - 1;
+}
+
+// a lane's part of its operand row — plane pairs: 16 bytes of each plane per k-step
+template <int K1S>
+__device__ __forceinline__ void load_row(const uint16_t* xh, const uint16_t* xl, int64_t pc, int ldx, int k1c, int q, i32x4 (&vh)[K1S],
+                                         i32x4 (&vl)[K1S]) {
+#pragma unroll
+  for (int ks = 0; ks < K1S; ++ks) {
+    const int ch = row_chunk(ks, q, k1c);
+    vh[ks] = *reinterpret_cast<const i32x4*>(xh + pc * ldx + ch * 8);
+    vl[ks] = *reinterpret_cast<const i32x4*>(xl + pc * ldx + ch * 8);
+  }
+}
+
+// ... fp32 rows: the 8 channels as two 16-byte loads
+template <int K1S>
+__device__ __forceinline__ void load_row(const float* x, int64_t pc, int ldx, int k1c, int q, float4 (&xa)[K1S], float4 (&xb)[K1S]) {
+#pragma unroll
+  for (int ks = 0; ks < K1S; ++ks) {
+    const float* px = x + pc * ldx + row_chunk(ks, q, k1c) * 8;
+    xa[ks] = *reinterpret_cast<const float4*>(px);
+    xb[ks] = *reinterpret_cast<const float4*>(px + 4);
+  }
+}
+
+// packed fragments f0 .. f0 + n - 1 of both planes (fused_slowfast.pack_pw_planes: 1 KB each, 16 bytes per lane) -> LDS
+__device__ __forceinline__ void stage_frags(char* dh, char* dl, const i32x4* wh, const i32x4* wl, int f0, int n, int wid, int lane) {
+  for (int f = wid; f < n; f += PX_NW) {
+    *reinterpret_cast<i32x4*>(dh + f * 1024 + lane * 16) = wh[(f0 + f) * 64 + lane];
+    *reinterpret_cast<i32x4*>(dl + f * 1024 + lane * 16) = wl[(f0 + f) * 64 + lane];
+  }
+}
+
+// channels c0 .. c0 + n - 1 of a layer's bias and row scales -> LDS (absent: 0 and 1)
+__device__ __forceinline__ void stage_bias_scale(float* bl, float* sl, const float* bias, const float* wscale, int c0, int n, int tid) {
+  for (int i = tid; i < n; i += PX_NW * 64) {
+    bl[i] = bias ? bias[c0 + i] : 0.0f;
+    sl[i] = wscale ? wscale[c0 + i] : 1.0f;
+  }
+}
+
+// acc[n] += W[n] x for output tiles n = 0 .. NT - 1 over k-steps 0 .. NK - 1; fragment (n, ks) lies at whl / wll + (n * KS + ks) KB.
+// IL accumulators in turn (round 4): every accumulator still sees its own three terms in the order wl*xh, wh*xl, wh*xh
+// (bit-identical results), but no MFMA reads the result of the one issued just before it: -4.5 % on 256 -> 1024 + residual
+// (pw_x3_kernel keeps its own copy, with its phase-skip hook: see profiles/r24)
+template <bool F16, int KS, int NK, int NT, int IL>
+__device__ __forceinline__ void product(const char* whl, const char* wll, int lofs, const i32x4* xh, const i32x4* xl, f32x4* acc) {
+#pragma unroll
+  for (int ks = 0; ks < NK; ++ks) {
+#pragma unroll
+    for (int n = 0; n < NT; n += IL) {
+      i32x4 wh[IL], wl[IL];
+#pragma unroll
+      for (int u = 0; u < IL; ++u) {
+        const int f = (n + u) * KS + ks;
+        wh[u] = *reinterpret_cast<const i32x4*>(whl + f * 1024 + lofs);
+        wl[u] = *reinterpret_cast<const i32x4*>(wll + f * 1024 + lofs);
+      }
+#pragma unroll
+      for (int u = 0; u < IL; ++u) acc[n + u] = mfma16<F16>(wl[u], xh[ks], acc[n + u]);
+#pragma unroll
+      for (int u = 0; u < IL; ++u) acc[n + u] = mfma16<F16>(wh[u], xl[ks], acc[n + u]);
+#pragma unroll
+      for (int u = 0; u < IL; ++u) acc[n + u] = mfma16<F16>(wh[u], xh[ks], acc[n + u]);
+    }
+  }
+}
+
+// A lane's two accumulators of a tile pair -> its 8 consecutive channels cl .. cl + 7 of the plane pair: scale + bias, the residual
+// octet, ReLU, the split; stored at row `row` (of ld elements), column `col` of yh / yl when `store` — the offset is formed inside
+// that branch, where the kernels formed it.  -> the planes as stored: the chained form's next operand.
+// (pw_x3_kernel keeps its own copy, with its phase-skip hook: see profiles/r24)
+struct Octet {
+  uint4 h, l;
+};
+
+template <bool F16>
+__device__ __forceinline__ Octet octet_epilogue(const f32x4& a0, const f32x4& a1, const float* bl, const float* sl, int cl, bool has_res,
+                                                const uint4& rh, const uint4& rl, bool relu, bool store, uint16_t* yh, uint16_t* yl,
+                                                int64_t row, int ld, int col) {
+  const float4 ba = *reinterpret_cast<const float4*>(bl + cl), bb = *reinterpret_cast<const float4*>(bl + cl + 4);
+  const float4 sa = *reinterpret_cast<const float4*>(sl + cl), sb = *reinterpret_cast<const float4*>(sl + cl + 4);
+  float v[8] = {a0[0] * sa.x + ba.x, a0[1] * sa.y + ba.y, a0[2] * sa.z + ba.z, a0[3] * sa.w + ba.w,
+                a1[0] * sb.x + bb.x, a1[1] * sb.y + bb.y, a1[2] * sb.z + bb.z, a1[3] * sb.w + bb.w};
+  if (has_res) {
+    const uint32_t* ph = reinterpret_cast<const uint32_t*>(&rh);
+    const uint32_t* pl = reinterpret_cast<const uint32_t*>(&rl);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const avt::f32x2 r = avt::join2<F16>(ph[e], pl[e]);
+      v[2 * e] += r.x;
+      v[2 * e + 1] += r.y;
+    }
+  }
+  if (relu) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = avt::relu_keep_nan(v[i]);
+  }
+  Octet y;
+  avt::split2<F16>(v[0], v[1], y.h.x, y.l.x);
+  avt::split2<F16>(v[2], v[3], y.h.y, y.l.y);
+  avt::split2<F16>(v[4], v[5], y.h.z, y.l.z);
+  avt::split2<F16>(v[6], v[7], y.h.w, y.l.w);
+  if (store) {
+    const int64_t o = row * ld + col;
+    *reinterpret_cast<uint4*>(yh + o) = y.h;
+    *reinterpret_cast<uint4*>(yl + o) = y.l;
+  }
+  return y;
+}
+
 template <int K1S, int NT1, bool F16>
 __global__ __launch_bounds__(PX_NW * 64) void pw_x3_kernel(PxArgs a) {
   constexpr int NC = NT1 * 16;  // output channels of this workgroup's chunk
@@ -80,25 +216,15 @@ __global__ __launch_bounds__(PX_NW * 64) void pw_x3_kernel(PxArgs a) {
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l15 = lane & 15, q = lane >> 4;
+  const int q = lane >> 4;
   const int f0 = chunk * NT1 * K1S;  // first fragment of the chunk
-  for (int f = wid; f < NT1 * K1S; f += PX_NW) {
-    *reinterpret_cast<i32x4*>(whl + f * 1024 + lane * 16) = a.wh[(f0 + f) * 64 + lane];
-    *reinterpret_cast<i32x4*>(wll + f * 1024 + lane * 16) = a.wl[(f0 + f) * 64 + lane];
-  }
-  for (int i = tid; i < NC; i += PX_NW * 64) {
-    bl[i] = a.bias ? a.bias[c0 + i] : 0.0f;
-    sl[i] = a.wscale ? a.wscale[c0 + i] : 1.0f;
-  }
+  stage_frags(whl, wll, a.wh, a.wl, f0, NT1 * K1S, wid, lane);
+  stage_bias_scale(bl, sl, a.bias, a.wscale, c0, NC, tid);
   __syncthreads();
   const bool has_res = a.rh != nullptr;
 
   for (int tile = rg * PX_NW + wid; tile < a.ntiles; tile += a.n_rg * PX_NW) {
-    const int p = tile * 16 + l15;
-    const bool ok = p < a.M;
-    int lofs = lane * 16;  // opaque per tile: keeps the loop-invariant fragment reads from being hoisted into registers
-    asm volatile("" : "+v"(lofs));
-    const int64_t pc = ok ? p : a.M - 1;
+    const auto [ok, lofs, pc] = tile_of(tile, lane, a.M);
     i32x4 xh[K1S], xl[K1S];
     if (a.taps > 1) {  // uniform: the temporal-tap form
       const int bto = (int)pc / a.HW, pos = (int)pc - bto * a.HW;
@@ -115,13 +241,7 @@ __global__ __launch_bounds__(PX_NW * 64) void pw_x3_kernel(PxArgs a) {
         xl[ks] = valid ? vl : i32x4{0, 0, 0, 0};
       }
     } else {
-#pragma unroll
-    for (int ks = 0; ks < K1S; ++ks) {
-      int ch = 4 * ks + q;  // past the row's end the weights are zero: any finite value will do
-      ch = ch < a.k1c ? ch : a.k1c - 1;
-      xh[ks] = *reinterpret_cast<const i32x4*>(a.xh + pc * a.ldx + ch * 8);
-      xl[ks] = *reinterpret_cast<const i32x4*>(a.xl + pc * a.ldx + ch * 8);
-    }
+      load_row<K1S>(a.xh, a.xl, pc, a.ldx, a.k1c, q, xh, xl);
     }
     uint4 rfh[NT1 / 2], rfl[NT1 / 2];
     if (has_res && !PW_SKIP(4)) {
@@ -234,40 +354,18 @@ __global__ __launch_bounds__(PX_NW * 64) void pw_chain_x3_kernel(PcArgs c) {
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l15 = lane & 15, q = lane >> 4;
-  for (int f = wid; f < NT1 * K1S; f += PX_NW) {
-    *reinterpret_cast<i32x4*>(whl + f * 1024 + lane * 16) = a.wh[f * 64 + lane];
-    *reinterpret_cast<i32x4*>(wll + f * 1024 + lane * 16) = a.wl[f * 64 + lane];
-  }
-  for (int f = wid; f < NT2 * K2S; f += PX_NW) {
-    *reinterpret_cast<i32x4*>(w2hl + f * 1024 + lane * 16) = c.w2h[f * 64 + lane];
-    *reinterpret_cast<i32x4*>(w2ll + f * 1024 + lane * 16) = c.w2l[f * 64 + lane];
-  }
-  for (int i = tid; i < NC; i += PX_NW * 64) {
-    bl[i] = a.bias ? a.bias[i] : 0.0f;
-    sl[i] = a.wscale ? a.wscale[i] : 1.0f;
-  }
-  for (int i = tid; i < NC2; i += PX_NW * 64) {
-    b2l[i] = c.bias2 ? c.bias2[i] : 0.0f;
-    s2l[i] = c.wscale2 ? c.wscale2[i] : 1.0f;
-  }
+  const int q = lane >> 4;
+  stage_frags(whl, wll, a.wh, a.wl, 0, NT1 * K1S, wid, lane);
+  stage_frags(w2hl, w2ll, c.w2h, c.w2l, 0, NT2 * K2S, wid, lane);
+  stage_bias_scale(bl, sl, a.bias, a.wscale, 0, NC, tid);
+  stage_bias_scale(b2l, s2l, c.bias2, c.wscale2, 0, NC2, tid);
   __syncthreads();
   const bool has_res = a.rh != nullptr;
 
   for (int tile = blockIdx.x * PX_NW + wid; tile < a.ntiles; tile += gridDim.x * PX_NW) {
-    const int p = tile * 16 + l15;
-    const bool ok = p < a.M;
-    int lofs = lane * 16;
-    asm volatile("" : "+v"(lofs));
-    const int64_t pc = ok ? p : a.M - 1;
+    const auto [ok, lofs, pc] = tile_of(tile, lane, a.M);
     i32x4 xh[K1S], xl[K1S];
-#pragma unroll
-    for (int ks = 0; ks < K1S; ++ks) {
-      int ch = 4 * ks + q;
-      ch = ch < a.k1c ? ch : a.k1c - 1;
-      xh[ks] = *reinterpret_cast<const i32x4*>(a.xh + pc * a.ldx + ch * 8);
-      xl[ks] = *reinterpret_cast<const i32x4*>(a.xl + pc * a.ldx + ch * 8);
-    }
+    load_row<K1S>(a.xh, a.xl, pc, a.ldx, a.k1c, q, xh, xl);
     uint4 rfh[NT1 / 2], rfl[NT1 / 2];
     if (has_res) {
 #pragma unroll
@@ -296,66 +394,16 @@ __global__ __launch_bounds__(PX_NW * 64) void pw_chain_x3_kernel(PcArgs c) {
         a1 = mfma16<F16>(w1h, xh[ks], a1);
       }
       const int cl = 32 * jj + 8 * q;
-      const float4 ba = *reinterpret_cast<const float4*>(bl + cl), bb = *reinterpret_cast<const float4*>(bl + cl + 4);
-      const float4 sa = *reinterpret_cast<const float4*>(sl + cl), sb = *reinterpret_cast<const float4*>(sl + cl + 4);
-      float v[8] = {a0[0] * sa.x + ba.x, a0[1] * sa.y + ba.y, a0[2] * sa.z + ba.z, a0[3] * sa.w + ba.w,
-                    a1[0] * sb.x + bb.x, a1[1] * sb.y + bb.y, a1[2] * sb.z + bb.z, a1[3] * sb.w + bb.w};
-      if (has_res) {
-        const uint32_t* ph = reinterpret_cast<const uint32_t*>(&rfh[jj]);
-        const uint32_t* pl = reinterpret_cast<const uint32_t*>(&rfl[jj]);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const avt::f32x2 r = avt::join2<F16>(ph[e], pl[e]);
-          v[2 * e] += r.x;
-          v[2 * e + 1] += r.y;
-        }
-      }
-      if (a.relu) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = avt::relu_keep_nan(v[i]);
-      }
-      uint4 oh, ol;
-      avt::split2<F16>(v[0], v[1], oh.x, ol.x);
-      avt::split2<F16>(v[2], v[3], oh.y, ol.y);
-      avt::split2<F16>(v[4], v[5], oh.z, ol.z);
-      avt::split2<F16>(v[6], v[7], oh.w, ol.w);
-      if (ok) {
-        const int64_t o = pc * a.ldy + cl;
-        *reinterpret_cast<uint4*>(a.yh + o) = oh;
-        *reinterpret_cast<uint4*>(a.yl + o) = ol;
-      }
+      const Octet y = octet_epilogue<F16>(a0, a1, bl, sl, cl, has_res, rfh[jj], rfl[jj], a.relu != 0, ok, a.yh, a.yl, pc, a.ldy, cl);
+      const uint4 oh = y.h, ol = y.l;
       // layer 2, k-step jj: the planes just stored are the operand
       const i32x4 yh = __builtin_bit_cast(i32x4, oh), yl = __builtin_bit_cast(i32x4, ol);
-#pragma unroll
-      for (int n = 0; n < NT2; ++n) {
-        const int f = n * K2S + jj;
-        const i32x4 wh = *reinterpret_cast<const i32x4*>(w2hl + f * 1024 + lofs), wl = *reinterpret_cast<const i32x4*>(w2ll + f * 1024 + lofs);
-        acc2[n] = mfma16<F16>(wl, yh, acc2[n]);
-        acc2[n] = mfma16<F16>(wh, yl, acc2[n]);
-        acc2[n] = mfma16<F16>(wh, yh, acc2[n]);
-      }
+      product<F16, K2S, 1, NT2, 1>(w2hl + jj * 1024, w2ll + jj * 1024, lofs, &yh, &yl, acc2);
     }
 #pragma unroll
     for (int jj = 0; jj < NT2 / 2; ++jj) {
       const int cl = 32 * jj + 8 * q;
-      const float4 ba = *reinterpret_cast<const float4*>(b2l + cl), bb = *reinterpret_cast<const float4*>(b2l + cl + 4);
-      const float4 sa = *reinterpret_cast<const float4*>(s2l + cl), sb = *reinterpret_cast<const float4*>(s2l + cl + 4);
-      float v[8] = {acc2[2 * jj][0] * sa.x + ba.x,     acc2[2 * jj][1] * sa.y + ba.y,
-                    acc2[2 * jj][2] * sa.z + ba.z,     acc2[2 * jj][3] * sa.w + ba.w,
-                    acc2[2 * jj + 1][0] * sb.x + bb.x, acc2[2 * jj + 1][1] * sb.y + bb.y,
-                    acc2[2 * jj + 1][2] * sb.z + bb.z, acc2[2 * jj + 1][3] * sb.w + bb.w};
-#pragma unroll
-      for (int i = 0; i < 8; ++i) v[i] = avt::relu_keep_nan(v[i]);
-      uint4 oh, ol;
-      avt::split2<F16>(v[0], v[1], oh.x, ol.x);
-      avt::split2<F16>(v[2], v[3], oh.y, ol.y);
-      avt::split2<F16>(v[4], v[5], oh.z, ol.z);
-      avt::split2<F16>(v[6], v[7], oh.w, ol.w);
-      if (ok) {
-        const int64_t o = pc * c.ldz + cl;
-        *reinterpret_cast<uint4*>(c.zh + o) = oh;
-        *reinterpret_cast<uint4*>(c.zl + o) = ol;
-      }
+      octet_epilogue<F16>(acc2[2 * jj], acc2[2 * jj + 1], b2l, s2l, cl, false, uint4{}, uint4{}, true, ok, c.zh, c.zl, pc, c.ldz, cl);
     }
   }
 }
@@ -469,47 +517,35 @@ __global__ __launch_bounds__(PX_NW * 64) void pw_x3_f32_kernel(PfArgs a) {
   }
 
   for (int tile = rg * PX_NW + wid; tile < a.ntiles; tile += a.n_rg * PX_NW) {
-    const int p = tile * 16 + l15;
-    const bool ok = p < a.M;
-    int lofs = lane * 16;  // opaque per tile: keeps the loop-invariant fragment reads from being hoisted into registers
-    asm volatile("" : "+v"(lofs));
-    int kz = 0;            // ... and the STATS = 2 coefficient reads
+    const Tile t = tile_of(tile, lane, a.M);
+    int kz = 0;  // opaque per tile as lofs is: the same for the STATS = 2 coefficient reads
     asm volatile("" : "+v"(kz));
-    const int64_t pc = ok ? p : a.M - 1;
     float4 xa[K1S], xb[K1S];
-#pragma unroll
-    for (int ks = 0; ks < K1S; ++ks) {
-      int ch = 4 * ks + q;  // past the row's end the weights are zero: any finite value will do
-      ch = ch < a.k1c ? ch : a.k1c - 1;
-      const float* px = a.x + pc * a.ldx + ch * 8;
-      xa[ks] = *reinterpret_cast<const float4*>(px);
-      xb[ks] = *reinterpret_cast<const float4*>(px + 4);
-    }
+    load_row<K1S>(a.x, t.pc, a.ldx, a.k1c, q, xa, xb);
     // the epilogue's operands (`add` rows, STATS = 2: the BatchNorm input's octets + mask nibbles), requested ahead of their use.
-    // STATS = 2 with 16 tiles per wave: in TWO batches — the second after the MFMAs, when the operand registers are free (all at
-    // once, the kernel spilled 40-115 registers)
-    constexpr int HB = (STATS == 2 && NT1 > 8) ? NT1 / 4 : NT1 / 2;
+    // (The three phases are lambdas, each called once: written straight into the tile loop, the uniform choices inside them come out
+    //  as branches instead of selects and the plain instances take up to 6 more registers — profiles/r24)
     float4 ra[NT1 / 2], rb[NT1 / 2];
     float4 bxa[STATS == 2 ? NT1 / 2 : 1], bxb[STATS == 2 ? NT1 / 2 : 1];
     unsigned bbits[STATS == 2 ? NT1 / 2 : 1];
-    auto epi_request = [&](auto j0, auto j1) {  // (compile-time bounds: the arrays stay in registers)
+    auto epi_request = [&] {
 #pragma unroll
-      for (int jj = decltype(j0)::value; jj < decltype(j1)::value; ++jj) {
-        if (has_add) {
-          const float* pr = a.add + pc * a.lda + c0 + 32 * jj + 8 * q;
-          ra[jj] = *reinterpret_cast<const float4*>(pr);
-          rb[jj] = *reinterpret_cast<const float4*>(pr + 4);
-        }
-        if constexpr (STATS == 2) {
-          const int64_t o = pc * a.ldy + c0 + 32 * jj + 8 * q;
-          bxa[jj] = *reinterpret_cast<const float4*>(a.bst_x + o);
-          bxb[jj] = *reinterpret_cast<const float4*>(a.bst_x + o + 4);
-          const unsigned v = a.bst_mask ? *reinterpret_cast<const uint16_t*>(a.bst_mask + (o >> 2)) : 0u;
-          bbits[jj] = (v & 0xFu) | ((v >> 4) & 0xF0u);
-        }
+    for (int jj = 0; jj < NT1 / 2; ++jj) {
+      if (has_add) {
+        const float* pr = a.add + t.pc * a.lda + c0 + 32 * jj + 8 * q;
+        ra[jj] = *reinterpret_cast<const float4*>(pr);
+        rb[jj] = *reinterpret_cast<const float4*>(pr + 4);
       }
+      if constexpr (STATS == 2) {
+        const int64_t o = t.pc * a.ldy + c0 + 32 * jj + 8 * q;
+        bxa[jj] = *reinterpret_cast<const float4*>(a.bst_x + o);
+        bxb[jj] = *reinterpret_cast<const float4*>(a.bst_x + o + 4);
+        const unsigned v = a.bst_mask ? *reinterpret_cast<const uint16_t*>(a.bst_mask + (o >> 2)) : 0u;
+        bbits[jj] = (v & 0xFu) | ((v >> 4) & 0xF0u);
+      }
+    }
     };
-    epi_request(std::integral_constant<int, 0>{}, std::integral_constant<int, HB>{});
+    epi_request();
     i32x4 xh[K1S], xl[K1S];
 #pragma unroll
     for (int ks = 0; ks < K1S; ++ks) {
@@ -520,33 +556,15 @@ __global__ __launch_bounds__(PX_NW * 64) void pw_x3_f32_kernel(PfArgs a) {
       xl[ks] = __builtin_bit_cast(i32x4, l);
     }
     f32x4 acc[NT1];
-    auto mfma_part = [&](auto n0_, auto n1_) {  // output tiles n0 .. n1 - 1: every accumulator sees its own terms in the one order
+    auto mfma_part = [&] {
 #pragma unroll
-      for (int n = decltype(n0_)::value; n < decltype(n1_)::value; ++n) acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < K1S; ++ks) {
-#pragma unroll
-        for (int n = decltype(n0_)::value; n < decltype(n1_)::value; n += PW_IL) {
-          i32x4 wh[PW_IL], wl[PW_IL];
-#pragma unroll
-          for (int u = 0; u < PW_IL; ++u) {
-            const int f = (n + u) * K1S + ks;
-            wh[u] = *reinterpret_cast<const i32x4*>(whl + f * 1024 + lofs);
-            wl[u] = *reinterpret_cast<const i32x4*>(wll + f * 1024 + lofs);
-          }
-#pragma unroll
-          for (int u = 0; u < PW_IL; ++u) acc[n + u] = mfma16<F16>(wl[u], xh[ks], acc[n + u]);
-#pragma unroll
-          for (int u = 0; u < PW_IL; ++u) acc[n + u] = mfma16<F16>(wh[u], xl[ks], acc[n + u]);
-#pragma unroll
-          for (int u = 0; u < PW_IL; ++u) acc[n + u] = mfma16<F16>(wh[u], xh[ks], acc[n + u]);
-        }
-      }
+      for (int n = 0; n < NT1; ++n) acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+      product<F16, K1S, K1S, NT1, PW_IL>(whl, wll, t.lofs, xh, xl, acc);
     };
     f32x4 hv[4];  // (STATS = 2: the second statistic's addends of one pass)
-    auto epilogue = [&](auto j0_, auto j1_) {
+    auto epilogue = [&] {
 #pragma unroll
-    for (int jj = decltype(j0_)::value; jj < decltype(j1_)::value; ++jj) {  // tiles 2jj, 2jj+1 -> channels c0 + 32 jj + 8 q .. + 7
+    for (int jj = 0; jj < NT1 / 2; ++jj) {  // tiles 2jj, 2jj+1 -> channels c0 + 32 jj + 8 q .. + 7
       const int cl = 32 * jj + 8 * q;
       f32x4 o0, o1;
       if constexpr (STATS == 2) {  // (gradients: bf16 planes, no row scales — and no 4 NT1 scale registers held across the tile loop)
@@ -588,8 +606,8 @@ __global__ __launch_bounds__(PX_NW * 64) void pw_x3_f32_kernel(PfArgs a) {
         v0 = f32x4{vv[0], vv[1], vv[2], vv[3]};
         v1 = f32x4{vv[4], vv[5], vv[6], vv[7]};
       }
-      if (ok) {
-        float* po = a.y + pc * a.ldy + c0 + cl;
+      if (t.ok) {
+        float* po = a.y + t.pc * a.ldy + c0 + cl;
         avt::stg4(po, o0);
         avt::stg4(po + 4, o1);
       }
@@ -598,7 +616,7 @@ __global__ __launch_bounds__(PX_NW * 64) void pw_x3_f32_kernel(PfArgs a) {
         // most two octets — until the first block has been read back)
         constexpr int JPP = PS::PW / 32;
         const int jl = jj % JPP;
-        if (!ok) o0 = o1 = v0 = v1 = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (!t.ok) o0 = o1 = v0 = v1 = f32x4{0.f, 0.f, 0.f, 0.f};
         float* pw_ = scr + l15 * PS::RS + 32 * jl + 8 * q;
         *reinterpret_cast<f32x4*>(pw_) = o0;
         *reinterpret_cast<f32x4*>(pw_ + 4) = o1;
@@ -635,7 +653,7 @@ __global__ __launch_bounds__(PX_NW * 64) void pw_x3_f32_kernel(PfArgs a) {
         // order, so a wait on the counter is the only synchronisation; no cross-lane traffic, 8 accumulator registers per pass
         constexpr int JPP = PS::PW / 32;  // jj's per pass
         const int jl = jj % JPP;
-        if (!ok) o0 = o1 = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (!t.ok) o0 = o1 = f32x4{0.f, 0.f, 0.f, 0.f};
         float* pw_ = scr + l15 * PS::RS + 32 * jl + 8 * q;
         *reinterpret_cast<f32x4*>(pw_) = o0;
         *reinterpret_cast<f32x4*>(pw_ + 4) = o1;
@@ -659,24 +677,8 @@ __global__ __launch_bounds__(PX_NW * 64) void pw_x3_f32_kernel(PfArgs a) {
       }
     }
     };
-    typedef std::integral_constant<int, 0> I0;
-    typedef std::integral_constant<int, HB> IH;
-    typedef std::integral_constant<int, NT1 / 2> IE;
-    if constexpr (HB < NT1 / 2) {  // (STATS = 2, 16 tiles) two halves: the second half's epilogue operands are requested under its MFMAs
-      // (sched_barrier: the scheduler otherwise lifts the second batch's loads and MFMAs over the first half's epilogue, and the
-      //  register pressure of the unsplit form is back)
-      mfma_part(I0{}, std::integral_constant<int, 2 * HB>{});
-      __builtin_amdgcn_sched_barrier(0);
-      epilogue(I0{}, IH{});
-      __builtin_amdgcn_sched_barrier(0);
-      epi_request(IH{}, IE{});
-      mfma_part(std::integral_constant<int, 2 * HB>{}, std::integral_constant<int, NT1>{});
-      __builtin_amdgcn_sched_barrier(0);
-      epilogue(IH{}, IE{});
-    } else {
-      mfma_part(I0{}, std::integral_constant<int, NT1>{});
-      epilogue(I0{}, IE{});
-    }
+    mfma_part();
+    epilogue();
   }
   if constexpr (STATS != 0) {  // this wave's row of partials: channel c0 + PW * pass + column
     const int C = a.n_total, q4 = C / 4, nq = q4 < 256 ? q4 : 256, unit = q4 > 256 ? q4 / 256 : 1;
@@ -714,72 +716,113 @@ constexpr int pf_lds_bytes(int stats) {  // 0 none, 1 forward statistics, 2 back
   return 2 * NT1 * K1S * 1024 + NT1 * 16 * 4 + (stats ? PfStat<K1S, NT1>::BYTES : 0) + (stats == 2 ? 3 * NT1 * 16 * 4 : 0);
 }
 
-template <int K1S, int NT1, bool F16, int MODE>
-int launch_pf_stats(PfArgs& a, hipStream_t st, int groups) {  // blockIdx.y = the BatchNorm's replica group, a.M / a.ntiles per group
-  constexpr int lds_bytes = pf_lds_bytes<K1S, NT1>(MODE);
-  static_assert(lds_bytes <= 160 * 1024, "weights + the statistics scratch fit the LDS");
-  a.n_rg = pf_row_groups(lds_bytes, a.n_chunks, a.ntiles, groups);
-  return avt::launch<pw_x3_f32_kernel<K1S, NT1, F16, MODE>>("avt_pw_x3_f32_stats", dim3((unsigned)(a.n_rg * a.n_chunks), (unsigned)groups),
-                                                            dim3(PX_NW * 64), lds_bytes, lds_bytes, st, a);
-}
+// ---- the instances ----------------------------------------------------------------------------------------------------------------
+// A kernel family's instances are its K steps x the tiles per workgroup chunk that fit beside them (`fits`).  The two lists below
+// are the only place that names them: the `*_supported` answers, the LDS-bytes query and the dispatch all walk them, and nothing
+// else is instantiated.
+constexpr int TILES[] = {16, 8, 4, 2};  // widest first
+constexpr bool fits(int k1s, int t) { return 2 * t * k1s <= 128; }  // both planes' fragments within 128 KB of LDS
 
-template <int K1S, int NT1, bool F16>
-int launch_pf(PfArgs& a, hipStream_t st, int groups = 0) {
-  if (groups > 0) {
-    if (a.bst_x) {
-      if constexpr (!F16) return launch_pf_stats<K1S, NT1, false, 2>(a, st, groups);  // (gradients: bf16 planes)
-      avt::set_error("avt_pw_x3_f32_bwdstats: bf16 planes only");
-      return AVT_ERR_UNSUPPORTED;
-    }
-    return launch_pf_stats<K1S, NT1, F16, 1>(a, st, groups);
-  }
-  constexpr int lds_bytes = pf_lds_bytes<K1S, NT1>(0);
-  a.n_rg = pf_row_groups(lds_bytes, a.n_chunks, a.ntiles, 1);
-  return avt::launch<pw_x3_f32_kernel<K1S, NT1, F16>>("avt_pw_x3_f32", dim3((unsigned)(a.n_rg * a.n_chunks)), dim3(PX_NW * 64), lds_bytes,
-                                                      lds_bytes, st, a);
-}
-
-// LDS bytes of the (K1S, NT1) instance, for the row-group query (avt_pw_x3_f32_stat_rows)
-int pf_lds_of(int k1s, int nt1, int stats) {
-#define PF_CASE(K, N) if (k1s == K && nt1 == N) return pf_lds_bytes<K, N>(stats);
-  PF_CASE(1, 16) PF_CASE(1, 8) PF_CASE(1, 4) PF_CASE(1, 2) PF_CASE(2, 16) PF_CASE(2, 8) PF_CASE(2, 4) PF_CASE(2, 2)
-  PF_CASE(4, 16) PF_CASE(4, 8) PF_CASE(4, 4) PF_CASE(4, 2) PF_CASE(8, 8) PF_CASE(8, 4) PF_CASE(8, 2)
-#undef PF_CASE
-  return 0;
-}
-
-template <int K1S, bool F16>
-int dispatch_pf_nt(PfArgs& a, int nt1, hipStream_t st, int groups) {
-  switch (nt1) {
-    case 16: if constexpr (K1S <= 4) return launch_pf<K1S, 16, F16>(a, st, groups); break;
-    case 8: if constexpr (K1S <= 8) return launch_pf<K1S, 8, F16>(a, st, groups); break;
-    case 4: return launch_pf<K1S, 4, F16>(a, st, groups);
-    case 2: return launch_pf<K1S, 2, F16>(a, st, groups);
-  }
-  avt::set_error("avt_pw_x3_f32: no kernel for K steps %d, tiles %d", K1S, nt1);
-  return AVT_ERR_UNSUPPORTED;
-}
-
-template <bool F16>
-int dispatch_pf_k(PfArgs& a, int k1s, int nt1, hipStream_t st, int groups = 0) {
-  switch (k1s) {
-    case 1: return dispatch_pf_nt<1, F16>(a, nt1, st, groups);
-    case 2: return dispatch_pf_nt<2, F16>(a, nt1, st, groups);
-    case 4: return dispatch_pf_nt<4, F16>(a, nt1, st, groups);
-    case 8: return dispatch_pf_nt<8, F16>(a, nt1, st, groups);
-  }
-  avt::set_error("avt_pw_x3_f32: unsupported K (%d steps of 32)", k1s);
-  return AVT_ERR_UNSUPPORTED;
-}
+enum : unsigned { POINTWISE = 1, LATERAL = 2 };  // the entries that may ask for a K step
+struct KStep {
+  int k1s;
+  unsigned users;
+};
+struct PxSteps {  // pw_x3_kernel
+  static constexpr KStep at[] = {{1, POINTWISE}, {2, POINTWISE | LATERAL}, {3, POINTWISE}, {4, POINTWISE},  {5, POINTWISE},
+                                 {7, LATERAL},   {8, POINTWISE},           {10, POINTWISE}, {14, LATERAL}, {16, POINTWISE}};
+};
+struct PfSteps {  // pw_x3_f32_kernel
+  static constexpr KStep at[] = {{1, POINTWISE}, {2, POINTWISE}, {4, POINTWISE}, {8, POINTWISE}};
+};
 
 // tiles per workgroup chunk for (K1S, N): the widest of 16 / 8 / 4 / 2 that divides N/16 and keeps both planes' fragments
 // within 128 KB of LDS; 0 = unsupported
 int pick_nt1(int k1s, int n) {
   if (n % 32) return 0;
   const int nt = n / 16;
-  for (int t : {16, 8, 4, 2})
-    if (nt % t == 0 && 2 * t * k1s <= 128) return t;
+  for (int t : TILES)
+    if (nt % t == 0 && fits(k1s, t)) return t;
   return 0;
+}
+
+// a layer of n outputs over k inputs that `user` may run on the family
+template <class Steps>
+int layer_supported(int k, int n, unsigned user) {
+  const int k1s = (k + 31) / 32;
+  bool listed = false;
+  for (const KStep& s : Steps::at) listed |= s.k1s == k1s && (s.users & user) != 0;
+  if (k % 8 || !listed) return 0;
+  const int nt1 = pick_nt1(k1s, n);
+  return (nt1 && n / (16 * nt1) <= 8) ? 1 : 0;  // more than 8 channel chunks re-read the input too often: the general tile is better
+}
+
+constexpr int NO_INSTANCE = INT_MIN;
+
+template <int K1S, int NT1, class F>
+bool try_instance(int k1s, int nt1, int& rc, F& f) {
+  if constexpr (fits(K1S, NT1)) {
+    if (k1s == K1S && nt1 == NT1) {
+      rc = f(std::integral_constant<int, K1S>{}, std::integral_constant<int, NT1>{});
+      return true;
+    }
+  }
+  return false;
+}
+
+template <class Steps, class F, size_t... I>
+int with_instance(int k1s, int nt1, F& f, std::index_sequence<I...>) {
+  int rc = NO_INSTANCE;
+  (void)(try_instance<Steps::at[I / std::size(TILES)].k1s, TILES[I % std::size(TILES)]>(k1s, nt1, rc, f) || ...);
+  return rc;
+}
+
+// f(K1S, NT1), the two as integral constants, of the family's instance (k1s, nt1); NO_INSTANCE if it has none
+template <class Steps, class F>
+int with_instance(int k1s, int nt1, F f) {
+  return with_instance<Steps>(k1s, nt1, f, std::make_index_sequence<std::size(Steps::at) * std::size(TILES)>{});
+}
+
+int no_instance(const char* who, int k1s, int nt1) {
+  avt::set_error("%s: no kernel for K steps %d, tiles %d", who, k1s, nt1);
+  return AVT_ERR_UNSUPPORTED;
+}
+
+// LDS bytes of the (K1S, NT1) instance, for the row-group queries (avt_pw_x3_f32_stat_rows, avt_pw_x3_f32_bwdstats_rows)
+int pf_lds_of(int k1s, int nt1, int stats) {
+  const int bytes = with_instance<PfSteps>(k1s, nt1, [&](auto k, auto t) { return pf_lds_bytes<k(), t()>(stats); });
+  return bytes == NO_INSTANCE ? 0 : bytes;
+}
+
+// STATS != 0: blockIdx.y = the BatchNorm's replica group, a.M / a.ntiles per group
+template <int K1S, int NT1, bool F16, int STATS>
+int launch_pf(PfArgs& a, hipStream_t st, int groups) {
+  constexpr int lds_bytes = pf_lds_bytes<K1S, NT1>(STATS);
+  static_assert(lds_bytes <= 160 * 1024, "weights + the statistics scratch fit the LDS");
+  a.n_rg = pf_row_groups(lds_bytes, a.n_chunks, a.ntiles, groups);
+  return avt::launch<pw_x3_f32_kernel<K1S, NT1, F16, STATS>>(STATS ? "avt_pw_x3_f32_stats" : "avt_pw_x3_f32",
+                                                             dim3((unsigned)(a.n_rg * a.n_chunks), (unsigned)groups), dim3(PX_NW * 64), lds_bytes,
+                                                             lds_bytes, st, a);
+}
+
+// The one place where the run-time choices of the training form become template arguments: the instance, the plane type, and the
+// mode (stats: 0 plain — one group —, 1 forward statistics, 2 backward).  Mode 2 has bf16 planes (gradients) and at most 8 tiles.
+int run_pf(PfArgs& a, int k1s, int nt1, int plane_dtype, int stats, int groups, hipStream_t st) {
+  const bool f16 = plane_dtype == AVT_X3_F16;
+  if (stats == 2 && f16) {
+    avt::set_error("avt_pw_x3_f32_bwdstats: bf16 planes only");
+    return AVT_ERR_UNSUPPORTED;
+  }
+  const int rc = with_instance<PfSteps>(k1s, nt1, [&](auto k, auto t) {
+    constexpr int K1S = k(), NT1 = t();
+    if (stats == 2) {
+      if constexpr (NT1 < 16) return launch_pf<K1S, NT1, false, 2>(a, st, groups);
+      return NO_INSTANCE;
+    }
+    if (stats == 1) return f16 ? launch_pf<K1S, NT1, true, 1>(a, st, groups) : launch_pf<K1S, NT1, false, 1>(a, st, groups);
+    return f16 ? launch_pf<K1S, NT1, true, 0>(a, st, 1) : launch_pf<K1S, NT1, false, 0>(a, st, 1);
+  });
+  return rc == NO_INSTANCE ? no_instance("avt_pw_x3_f32", k1s, nt1) : rc;
 }
 
 template <int K1S, int NT1, bool F16>
@@ -791,34 +834,12 @@ int launch_px(PxArgs& a, hipStream_t st) {
                                                   st, a);
 }
 
-template <int K1S, bool F16>
-int dispatch_nt(PxArgs& a, int nt1, hipStream_t st) {
-  switch (nt1) {
-    case 16: if constexpr (K1S <= 4) return launch_px<K1S, 16, F16>(a, st); break;
-    case 8: if constexpr (K1S <= 8) return launch_px<K1S, 8, F16>(a, st); break;
-    case 4: return launch_px<K1S, 4, F16>(a, st);
-    case 2: return launch_px<K1S, 2, F16>(a, st);
-  }
-  avt::set_error("avt_pw_x3: no kernel for K steps %d, tiles %d", K1S, nt1);
-  return AVT_ERR_UNSUPPORTED;
-}
-
-template <bool F16>
-int dispatch_k(PxArgs& a, int k1s, int nt1, hipStream_t st) {
-  switch (k1s) {
-    case 1: return dispatch_nt<1, F16>(a, nt1, st);
-    case 2: return dispatch_nt<2, F16>(a, nt1, st);
-    case 3: return dispatch_nt<3, F16>(a, nt1, st);
-    case 4: return dispatch_nt<4, F16>(a, nt1, st);
-    case 5: return dispatch_nt<5, F16>(a, nt1, st);
-    case 7: return dispatch_nt<7, F16>(a, nt1, st);
-    case 8: return dispatch_nt<8, F16>(a, nt1, st);
-    case 10: return dispatch_nt<10, F16>(a, nt1, st);
-    case 14: return dispatch_nt<14, F16>(a, nt1, st);
-    case 16: return dispatch_nt<16, F16>(a, nt1, st);
-  }
-  avt::set_error("avt_pw_x3: unsupported K (%d steps of 32)", k1s);
-  return AVT_ERR_UNSUPPORTED;
+// ... and of the plane-pair form
+int run_px(PxArgs& a, int k1s, int nt1, int plane_dtype, hipStream_t st) {
+  const bool f16 = plane_dtype == AVT_X3_F16;
+  const int rc = with_instance<PxSteps>(
+      k1s, nt1, [&](auto k, auto t) { return f16 ? launch_px<k(), t(), true>(a, st) : launch_px<k(), t(), false>(a, st); });
+  return rc == NO_INSTANCE ? no_instance("avt_pw_x3", k1s, nt1) : rc;
 }
 
 // The fields the PxArgs users share: a pointwise layer of n columns (nt1 tiles per chunk) over m rows.  The lateral and the chained
@@ -867,14 +888,7 @@ void pf_fill(PfArgs& a, const float* x, int ldx, int k, const void* w_hi, const 
 
 }  // namespace
 
-extern "C" int avt_pw_x3_supported(int k, int n) {
-  const int k1s = (k + 31) / 32;
-  if (k % 8 || !(k1s == 1 || k1s == 2 || k1s == 3 || k1s == 4 || k1s == 5 || k1s == 8 || k1s == 10 || k1s == 16)) return 0;
-  const int nt1 = pick_nt1(k1s, n);
-  if (!nt1) return 0;
-  if ((nt1 == 16 && k1s > 4) || (nt1 == 8 && k1s > 8)) return 0;
-  return n / (16 * nt1) <= 8 ? 1 : 0;  // more than 8 channel chunks re-read the input too often: the general tile is better
-}
+extern "C" int avt_pw_x3_supported(int k, int n) { return layer_supported<PxSteps>(k, n, POINTWISE); }
 
 extern "C" int avt_pw_x3(const void* x_hi, const void* x_lo, int ldx, int k, const void* w_hi, const void* w_lo, const float* bias,
                          const float* wscale, const void* res_hi, const void* res_lo, int ldr, void* y_hi, void* y_lo, int ldy,
@@ -891,17 +905,14 @@ extern "C" int avt_pw_x3(const void* x_hi, const void* x_lo, int ldx, int k, con
   const int k1s = (k + 31) / 32, nt1 = pick_nt1(k1s, n);
   PxArgs a;
   px_fill(a, x_hi, x_lo, ldx, k, w_hi, w_lo, bias, wscale, res_hi, res_lo, ldr, y_hi, y_lo, ldy, n, nt1, m, relu);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  return plane_dtype == AVT_X3_F16 ? dispatch_k<true>(a, k1s, nt1, st) : dispatch_k<false>(a, k1s, nt1, st);
+  return run_px(a, k1s, nt1, plane_dtype, static_cast<hipStream_t>(stream));
 }
 
 // Conv3d [kt,1,1], temporal stride st, padding pt, on plane pairs: the lateral fast -> slow connections (FuseFastToSlow: [7,1,1]
 // stride 4 + BN + ReLU of the third-party SlowFast model the reference runs per clip window, models/models.py:335, 399)
 extern "C" int avt_lateral_x3_supported(int cin, int cout, int kt) {
-  const int k = kt * cin, k1s = (k + 31) / 32, n = (cout + 31) / 32 * 32;
-  if (cin % 8 || kt < 2 || !(k1s == 2 || k1s == 7 || k1s == 14)) return 0;
-  const int nt1 = pick_nt1(k1s, n);
-  return (nt1 && cout % 16 == 0 && n / (16 * nt1) <= 8) ? 1 : 0;
+  if (cin % 8 || kt < 2 || cout % 16) return 0;
+  return layer_supported<PxSteps>(kt * cin, (cout + 31) / 32 * 32, LATERAL);
 }
 
 extern "C" int avt_lateral_x3(const void* x_hi, const void* x_lo, int ldx, int cin, const void* w_hi, const void* w_lo, const float* bias,
@@ -930,8 +941,7 @@ extern "C" int avt_lateral_x3(const void* x_hi, const void* x_lo, int ldx, int c
   a.tst = st;
   a.tpad = pt;
   a.n_valid = cout;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return plane_dtype == AVT_X3_F16 ? dispatch_k<true>(a, k1s, nt1, s) : dispatch_k<false>(a, k1s, nt1, s);
+  return run_px(a, k1s, nt1, plane_dtype, static_cast<hipStream_t>(stream));
 }
 
 // (k1, n1, n2) of the chained form: the slow res2 pair 64 -> 256 (+ residual) -> 64
@@ -974,14 +984,7 @@ extern "C" int avt_pw_chain_x3(const void* x_hi, const void* x_lo, int ldx, int 
 }
 
 // The training form of avt_pw_x3 (see include/avt.h): fp32 rows in / out, plain [n][k] weight planes
-extern "C" int avt_pw_x3_f32_supported(int k, int n) {
-  const int k1s = (k + 31) / 32;
-  if (k % 8 || n % 32 || !(k1s == 1 || k1s == 2 || k1s == 4 || k1s == 8)) return 0;
-  const int nt1 = pick_nt1(k1s, n);
-  if (!nt1) return 0;
-  if ((nt1 == 16 && k1s > 4) || (nt1 == 8 && k1s > 8)) return 0;
-  return n / (16 * nt1) <= 8 ? 1 : 0;
-}
+extern "C" int avt_pw_x3_f32_supported(int k, int n) { return layer_supported<PfSteps>(k, n, POINTWISE); }
 
 extern "C" int avt_pw_x3_f32(const float* x, int ldx, int k, const void* w_hi, const void* w_lo, const float* wscale, const float* add,
                              int lda, float* y, int ldy, int n, int64_t m, int plane_dtype, void* stream) {
@@ -996,8 +999,7 @@ extern "C" int avt_pw_x3_f32(const float* x, int ldx, int k, const void* w_hi, c
   const int k1s = (k + 31) / 32, nt1 = pick_nt1(k1s, n);
   PfArgs a;
   pf_fill(a, x, ldx, k, w_hi, w_lo, wscale, add, lda, y, ldy, n, nt1, (int)m, nullptr);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  return plane_dtype == AVT_X3_F16 ? dispatch_pf_k<true>(a, k1s, nt1, st) : dispatch_pf_k<false>(a, k1s, nt1, st);
+  return run_pf(a, k1s, nt1, plane_dtype, 0, 1, static_cast<hipStream_t>(stream));
 }
 
 // ... leaving the train-mode BatchNorm statistics of its output behind (include/avt.h; the streaming counterpart of
@@ -1023,8 +1025,7 @@ extern "C" int avt_pw_x3_f32_stats(const float* x, int ldx, int k, const void* w
   const int k1s = (k + 31) / 32, nt1 = pick_nt1(k1s, n);
   PfArgs a;
   pf_fill(a, x, ldx, k, w_hi, w_lo, wscale, nullptr, 0, y, ldy, n, nt1, (int)(m / groups), stat_part);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  return plane_dtype == AVT_X3_F16 ? dispatch_pf_k<true>(a, k1s, nt1, st, groups) : dispatch_pf_k<false>(a, k1s, nt1, st, groups);
+  return run_pf(a, k1s, nt1, plane_dtype, 1, groups, static_cast<hipStream_t>(stream));
 }
 
 // The streaming input gradient whose result is a train-mode BatchNorm's OUTPUT gradient (include/avt.h; the counterpart of
@@ -1053,10 +1054,13 @@ extern "C" int avt_pw_x3_f32_bwdstats(const float* x, int ldx, int k, const void
   int k1s = (k + 31) / 32, nt1 = pick_nt1(k1s, n);
   // (16 tiles per wave spill 13-84 registers in this mode, and a scratch reload's s_waitcnt vmcnt(0) serializes the tile's loads: 8
   //  tiles and twice the chunks — the dy rows read twice, a small operand here — are 10 % (K = 64) to 27 % (K = 128) faster)
+  //  tiles and twice the chunks — the dy rows read twice, a small operand here — are 10 % (K = 64) to 27 % (K = 128) faster.  The
+  //  16 tiles split in two halves, the second half's operands requested under its MFMAs, were tried first: that form is in the
+  //  history, in this file at the parent of the commit that removed it)
   if (nt1 == 16) nt1 = 8;
   PfArgs a;
   pf_fill(a, x, ldx, k, w_hi, w_lo, nullptr, add, lda, y, ldy, n, nt1, (int)(m / groups), stat_part);
   a.bst_x = bn_x; a.bst_mean = bn_mean; a.bst_invstd = bn_invstd; a.bst_gamma = bn_gamma; a.bst_beta = bn_beta;
   a.bst_mask = static_cast<const uint8_t*>(bn_mask); a.bst_relu = relu;
-  return dispatch_pf_k<false>(a, k1s, nt1, static_cast<hipStream_t>(stream), groups);
+  return run_pf(a, k1s, nt1, plane_dtype, 2, groups, static_cast<hipStream_t>(stream));
 }

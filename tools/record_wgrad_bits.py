@@ -1,7 +1,10 @@
-"""Writes tests/golden/wgrad_x3_bits.json: per key of tests/wgrad_bits_cases.py the SHA-256 of dW's bytes on THIS tree.  Run it on the
-MI355X on the commit whose weight-gradient kernels are the reference, and commit the file; tests/test_gpu_wgrad_bits.py then holds
-later trees to it.  Every key is run twice in the process, and no file is written if the two hashes of any key differ.
-python tools/record_wgrad_bits.py <commit the tree is at> [output path]"""
+"""Writes a golden file of output hashes: per key of a cases module under tests/ the SHA-256 its digest(key) gives on THIS tree —
+tests/golden/wgrad_x3_bits.json for wgrad_bits_cases (dW's bytes; the default), tests/golden/pw_x3_bits.json for pw_bits_cases (the
+output buffers of csrc/pw_x3.hip's entries).  Run it on the MI355X on the commit whose kernels are the reference, and commit the file;
+tests/test_gpu_wgrad_bits.py / tests/test_gpu_pw_bits.py then hold later trees to it.  Every key is run twice in the process, and no
+file is written if the two hashes of any key differ.
+python tools/record_wgrad_bits.py <commit the tree is at> [cases module [output path]]"""
+import importlib
 import json
 import os
 import sys
@@ -10,13 +13,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-import wgrad_bits_cases as wb  # noqa: E402
+GOLDEN = {"wgrad_bits_cases": "wgrad_x3_bits.json", "pw_bits_cases": "pw_x3_bits.json"}
 
 
 def main(argv):
     if len(argv) < 2:
         raise SystemExit(__doc__)
-    path = argv[2] if len(argv) > 2 else os.path.join(ROOT, "tests", "golden", "wgrad_x3_bits.json")
+    module = argv[2] if len(argv) > 2 else "wgrad_bits_cases"
+    wb = importlib.import_module(module)
+    path = argv[3] if len(argv) > 3 else os.path.join(ROOT, "tests", "golden", GOLDEN[module])
     first = {key: wb.digest(key) for key in wb.KEYS}
     second = {key: wb.digest(key) for key in wb.KEYS}
     differ = [key for key in wb.KEYS if first[key] != second[key]]
