@@ -9,6 +9,8 @@ Additions (all optional): --stitch_mode {compat,aligned}, --ref_num_gpus, --enc_
 Multi-GPU: one process per GPU under torch.distributed.run instead of torch.nn.DataParallel (main.py:420).  --train_input device works
 there too, with or without --train_graph 1: every rank assembles its share of each global batch in its own HBM
 (dataset.DeviceSegmentBatcher(rank, world)), item for item the batch DataParallel would scatter from one NumPy stream.
+--train_deterministic there also sums the gradients in rank order (train_ops.GradExchange, ordered: one all-gather, one HIP launch),
+with or without --train_graph 1, so that a seed repeats across ranks for one world size.
 """
 import argparse
 import math
@@ -90,8 +92,12 @@ def build_parser():
       help="weight gradients of the training step as per-chunk partial tiles summed in a fixed order (train_ops.set_deterministic) "
            "instead of fp32 atomics: with the rest of the step already free of atomics, one process on one GPU with one build repeats "
            "a seed bit for bit, eagerly and with --train_graph 1, with either --train_optimizer.  Needs --train_layout ndhwc and "
-           "--train_conv x3; across ranks the all-reduce's order is the backend's and nothing is promised.  Default off: the atomic "
-           "path, unchanged (not in the reference)")
+           "--train_conv x3.  Under torch.distributed.run the gradients are also summed in rank order: the model is prepared by "
+           "train_ops.prepare_ranks (no DistributedDataParallel, with or without --train_graph 1), the ranks all-gather their packed "
+           "gradients and one HIP launch adds them in ascending rank order (train_ops.GradExchange, ordered), so a seed repeats bit "
+           "for bit for the same world size, the same build and the same GPU type; the gathered rows cost world x 4 bytes per "
+           "trained parameter of HBM per rank.  Default off: the atomic path and the backend's all-reduce, unchanged (not in the "
+           "reference)")
     a("--ckpt_async", default=False, action="store_true",
       help="write the epoch-end checkpoints off the training loop: the state leaves the device in one launch and one copy into pinned "
            "memory (train_ops.StateSnapshot), a background thread writes *_latest.pth.tar and *_best.pth.tar through temporary files "
@@ -102,7 +108,10 @@ def build_parser():
            "the torch CPU / device and np.random generator states, the device loader's stream, seed and epoch, the world size and the "
            "--train_deterministic setting; with --resume all of it is restored (a checkpoint without the key is refused), and with "
            "--train_deterministic --train_input device (or -j 0) in one process on one GPU a run interrupted after any epoch and resumed "
-           "equals the uninterrupted one bit for bit.  Default off: --resume restores the weights, the epoch and best_loss")
+           "equals the uninterrupted one bit for bit; across ranks, with --train_deterministic --train_input device and the same world "
+           "size, it equals it in rank 0's checkpoint and in every rank's losses (the train_state is rank 0's; the BatchNorm running "
+           "statistics of the other ranks are not saved and come back as rank 0's).  Default off: --resume restores the weights, the "
+           "epoch and best_loss")
     a("--slomo_ckpt", default="ckpt/SuperSloMo.ckpt", type=str,
       help="SuperSloMo checkpoint (validate.py:183 hard-codes this path); 'random' = seeded weights; missing file = cuts")
     a("-long", "--long", dest="long", default=False, action="store_true", help="unused in the reference")
@@ -236,17 +245,22 @@ def main(args, video_name, itr=0):
                                                   "fp32 accumulation)" if mode == "x3" else "MIOpen fp32"))
         if getattr(args, "train_deterministic", False):
             train_ops.set_deterministic(True)  # (raises with --train_conv fp32)
-            if rank == 0:
+            if rank == 0 and world == 1:
                 print("training step: deterministic weight gradients (fixed-order reduction): bit-reproducible within one process on "
-                      "one GPU with this build%s" % ("; across ranks the all-reduce's order is the backend's" if world > 1 else ""))
+                      "one GPU with this build")
+            elif rank == 0:
+                print("training step: deterministic weight gradients (fixed-order reduction) and gradients summed in rank order across "
+                      "the %d ranks (train_ops.GradExchange, ordered): bit-reproducible for one world size, one build and one GPU type"
+                      % world)
     elif not args.evaluate and getattr(args, "train_deterministic", False):
         from ._lib import AvtError
 
         raise AvtError("--train_deterministic needs --train_layout ndhwc (the hand-written training kernels)")
     if world > 1 and not args.evaluate:  # weights resident per rank, gradients all-reduced over RCCL
-        if getattr(args, "train_graph", 0):
+        if getattr(args, "train_graph", 0) or getattr(args, "train_deterministic", False):
             # every rank replays its step as a HIP graph and the gradients cross the ranks in one flat buffer outside it (train.train):
-            # no DistributedDataParallel wrapper, whose bucketed all-reduce is not captured
+            # no DistributedDataParallel wrapper, whose bucketed all-reduce is not captured — nor ordered: with --train_deterministic
+            # the flat buffer is gathered and summed in rank order (train_ops.GradExchange.exchange), with or without the graph
             from . import train_ops
 
             model = train_ops.prepare_ranks(model)

@@ -665,6 +665,23 @@ def grad_pack_multi(jobs, blk2job, nblocks, scale):
     K.avt_grad_pack_multi(_p(jobs), _p(blk2job), int(nblocks), _p(scale), _stream())
 
 
+def rank_sum(parts, out, n=None):
+    """out[:n] = parts[0][:n] + parts[1][:n] + ... in ascending row order, one fp32 chain per element (csrc/rank_sum.hip, include/avt.h):
+    the sum of the ordered gradient exchange (train_ops.GradExchange).  parts: device fp32 [world, ld], ld a multiple of 4; out: device
+    fp32 with at least n elements, disjoint from parts; n defaults to out.numel().  One launch on the current stream."""
+    _dev(parts, "parts", torch.float32)
+    _dev(out, "out", torch.float32)
+    if parts.dim() != 2:
+        raise _lib.AvtError("parts must be [world, ld], got %s" % (tuple(parts.shape),))
+    n = out.numel() if n is None else int(n)
+    if n > out.numel():
+        raise _lib.AvtError("rank_sum: n = %d but out holds %d elements" % (n, out.numel()))
+    lo, hi = parts.data_ptr(), parts.data_ptr() + 4 * parts.numel()
+    if out.device != parts.device or (out.data_ptr() < hi and lo < out.data_ptr() + 4 * out.numel()):
+        raise _lib.AvtError("rank_sum: out must be on parts' device and disjoint from parts")
+    K.avt_rank_sum_f32(_p(parts), int(parts.shape[0]), n, int(parts.shape[1]), _p(out), _stream())
+
+
 def weight_planes_t_f32(w3d, sel):
     """[cout, taps, cin] fp32 -> (hi, lo) bf16 planes [cin, len(sel) * cout] with out[ci][a][co] = w[co][sel[a]][ci]: the input
     gradient's filter (sel = all taps reversed) or one residue class of a strided layer's (csrc/stem_train.hip)."""

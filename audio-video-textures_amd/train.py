@@ -31,7 +31,9 @@ def train(train_loader, model, optimizer, args, epoch, tb_logger=None):
     # DESIGN.md 5.2).  One process: forward, loss, backward and the optimizer are the graph.  Several ranks (the model prepared by
     # train_ops.prepare_ranks, not wrapped in DistributedDataParallel, whose bucketed all-reduce is not captured): the graph ends with the
     # backward and ONE launch that packs the gradients into a flat buffer (train_ops.GradExchange); one all-reduce and the optimizer
-    # follow every replay eagerly.  A DistributedDataParallel model keeps the eager loop.
+    # follow every replay eagerly.  A DistributedDataParallel model keeps the eager loop.  A model that prepare_ranks prepared takes the
+    # same ranks form WITHOUT --train_graph too, eagerly: forward and backward, the pack, the exchange, the optimizer (main() prepares
+    # it that way with --train_deterministic, whose ordered exchange DistributedDataParallel's bucketed all-reduce is not).
     graphed = model.__dict__.setdefault("_avt_graphed_steps", {})  # (kept on the model: train() is called once per epoch)
     if graphed.get("optimizer") is not optimizer:
         graphed.clear()
@@ -41,10 +43,12 @@ def train(train_loader, model, optimizer, args, epoch, tb_logger=None):
     ddp = isinstance(model, torch.nn.parallel.DistributedDataParallel)
     # (a model that train_ops.prepare_ranks prepared takes the ranks form under a ONE-rank process group too:
     #  tools/probe_train_graph_ranks.py times it on one GPU; main() prepares a model only at world > 1)
-    ranks = bool(getattr(args, "train_graph", 0)) and dist_on and not ddp and (world > 1 or train_ops.prepared_for_ranks(model))
-    use_graph = bool(getattr(args, "train_graph", 0)) and (world == 1 or ranks)
+    want_graph = bool(getattr(args, "train_graph", 0))
+    ranks = dist_on and not ddp and (train_ops.prepared_for_ranks(model) or (want_graph and world > 1))
+    use_graph = want_graph and (world == 1 or ranks)
     if ranks and "exchange" not in graphed:
-        graphed["exchange"] = train_ops.GradExchange(model.parameters(), world)
+        # (ordered: None = summed in rank order exactly when the step is deterministic; args.exchange_ordered lets a probe choose)
+        graphed["exchange"] = train_ops.GradExchange(model.parameters(), world, ordered=getattr(args, "exchange_ordered", None))
     end = time.time()
     for i, batch_data in enumerate(train_loader):
         q_frames, q_audio_wav, q_audio_eg, t_frames, t_audio_wav, t_audio_eg = batch_data
@@ -99,7 +103,11 @@ def train(train_loader, model, optimizer, args, epoch, tb_logger=None):
                 loss = ent[1]()
             losses.update(loss.item(), batch_size)
         else:
-            loss = _eager_step(model, optimizer, criterion, args, q_frames, t_frames, q_audio_eg, t_audio_eg, batch_size)
+            if ranks:
+                loss = _eager_ranks_step(model, optimizer, criterion, args, q_frames, t_frames, q_audio_eg, t_audio_eg, batch_size,
+                                         graphed["exchange"])
+            else:
+                loss = _eager_step(model, optimizer, criterion, args, q_frames, t_frames, q_audio_eg, t_audio_eg, batch_size)
             losses.update(loss.item(), batch_size)
 
         batch_time.update(time.time() - end)
@@ -151,6 +159,17 @@ def _exchange_and_step(optimizer, exchange):
         optimizer.sync_hyper()
     optimizer.step()
     train_ops.invalidate_weight_cache()  # (optimizers that update through .data do not bump Tensor._version)
+
+
+def _eager_ranks_step(model, optimizer, criterion, args, q_frames, t_frames, q_audio_eg, t_audio_eg, batch_size, exchange):
+    """One step across ranks without a graph: forward and backward, the pack of the gradients, the exchange and the optimizer -> the
+    rank's own loss.  What _graphed_ranks_step captures and what follows its replays, issued launch by launch."""
+    loss = _forward_backward(model, optimizer, criterion, args, q_frames, t_frames, q_audio_eg, t_audio_eg, batch_size)
+    if not exchange.bound:
+        exchange.bind()  # (the first backward of the run: which parameters have gradients; one small collective)
+    exchange.pack()
+    _exchange_and_step(optimizer, exchange)
+    return loss.detach()
 
 
 def _graphed_ranks_step(model, optimizer, criterion, args, static, nq, nt, batch_size, exchange):

@@ -117,7 +117,8 @@ CALLS = {"conv_fwd_x3": 0, "dgrad_x3": 0, "dgrad_strided_x3": 0, "wgrad_x3": 0, 
          "miopen_dgrad": 0, "miopen_wgrad": 0, "stem_fwd_patch": 0, "wgrad_stem_patch": 0, "maxpool_hip": 0, "pw_f32": 0,
          "bn_fwd_pre": 0, "bn_bwd_pre": 0, "dgrad_bwdstats": 0, "planes_multi": 0, "maxpool3d_hip": 0, "sgd_multi": 0, "grad_pack_multi": 0,
          "wgrad_det": 0,  # (wgrad_det: launches of the deterministic weight-gradient entries, counted next to the rows above)
-         "state_copy_multi": 0}
+         "state_copy_multi": 0,
+         "rank_sum": 0}  # (rank_sum: launches of the ordered exchange's sum over the ranks, GradExchange.exchange)
 
 
 def _rows(x):
@@ -703,6 +704,11 @@ class ArenaSGD(torch.optim.Optimizer):
 # DistributedDataParallel's bucketed all-reduce is not capturable as it stands, and its hooks issue from the host.  Here the capture
 # ends with ONE launch (csrc/grad_pack.hip) that copies every gradient, times 1 / world, into one flat buffer; the ranks all-reduce
 # that buffer OUTSIDE the graph and the optimizer — any optimizer — steps on views of it.
+# The ORDERED exchange (deterministic mode) replaces the all-reduce, whose order of summation is the backend's, by data movement and a sum
+# of our own: one all-gather of the buffers into parts [world][total] and ONE launch (csrc/rank_sum.hip) that adds the rows in ascending
+# rank order — every rank computes the same fp32 chain, so the ranks stay bit-identical and a seed repeats across ranks.  Its cost: the
+# gather receives world x 4 * total bytes per rank where an all-reduce moves about 2 x 4 * total, `parts` takes world x 4 * total bytes
+# of HBM (world x 269 MB on config 5), and the sum reads and writes (world + 1) x 4 * total bytes.
 def exchange_layout(numels):
     """-> (offsets, total) in floats: tensor k of `numels` starts at a multiple of 4 floats (16 bytes, as _GradArena.take slices),
     total = sum of ceil4(numel)."""
@@ -728,11 +734,15 @@ class GradExchange:
         ex.all_reduce(); ex.install()     # eager: one all-reduce (sum), then p.grad = the parameter's view of the buffer
         optimizer.step()
 
+    ordered=True (None: what deterministic() says when bind() runs): all_reduce() is exchange() — one all-gather of the ranks' buffers
+    into `parts` [world][ceil4(total)] and one launch of ops.rank_sum that adds them in ascending rank order into `flat`: only data
+    movement crosses the ranks, and `flat` holds the same bits on every rank.  The 1 / world scale stays in pack().
+
     `flat` holds parameter k at exchange_layout's offset, through a view with the PARAMETER's strides (a channels-last weight's view is
     an as_strided one: the same memory order as its gradient, so the pack is a flat copy); the padding between tensors stays zero.
     `scale` is a device tensor the kernel loads: a replay follows what the host last wrote there."""
 
-    def __init__(self, params, world, group=None):
+    def __init__(self, params, world, group=None, ordered=None):
         self.candidates = [p for p in params if p.requires_grad]
         if not self.candidates:
             raise _lib.AvtError("GradExchange: no parameter requires a gradient")
@@ -740,6 +750,7 @@ class GradExchange:
         if self.world < 1:
             raise _lib.AvtError("GradExchange: world must be >= 1, got %d" % self.world)
         self.params, self.views, self.flat, self.offsets, self.total = None, None, None, None, 0
+        self.ordered, self.parts, self._parts_host = ordered, None, None
         self.scale = torch.full((1,), 1.0 / self.world, dtype=torch.float32, device=self.candidates[0].device)
         self._jobs = _JobTable("GradExchange.pack()", _PACK_JOB, ops.pack_job_bytes, remedy="pack()")
 
@@ -771,6 +782,10 @@ class GradExchange:
         self.flat = torch.zeros(max(total, 4), dtype=torch.float32, device=params[0].device)
         self.views = [torch.as_strided(self.flat, tuple(p.shape), tuple(p.stride()), o) for p, o in zip(params, offsets)]
         self.params, self.offsets, self.total = params, offsets, total
+        if self.ordered is None:
+            self.ordered = deterministic()
+        if self.ordered:  # (total is a sum of ceil4s: rows of `parts` start 16-byte aligned)
+            self.parts = torch.empty((self.world, self.flat.numel()), dtype=torch.float32, device=self.flat.device)
         self._jobs.reserve(_chunks(p.numel()) for p in params)  # (outside any capture: what a captured pack() stages its table in)
 
     @torch.no_grad()
@@ -805,14 +820,48 @@ class GradExchange:
         CALLS["grad_pack_multi"] += 1
 
     def all_reduce(self):
-        """The sum over the ranks of the packed buffer, one collective on the current stream (the scale made it the mean)."""
+        """The sum over the ranks of the packed buffer, one collective on the current stream (the scale made it the mean); ordered:
+        exchange()."""
         import torch.distributed as dist
         if not self.bound:
             raise _lib.AvtError("GradExchange.all_reduce() before bind()")
+        if self.ordered:
+            return self.exchange()
         if dist.is_available() and dist.is_initialized():
             dist.all_reduce(self.flat, group=self.group)
         elif self.world > 1:
             raise _lib.AvtError("GradExchange.all_reduce(): world %d without an initialised process group" % self.world)
+
+    def exchange(self):
+        """The ordered sum: all_gather_into_tensor(parts, flat) — row r of `parts` is rank r's buffer — then flat = the rows added in
+        ascending rank order by one launch (ops.rank_sum).  Eager, on the current stream.  Under a gloo group (ranks that share one GPU)
+        the gather is staged through the host, as dist.all_gather_rows does; under RCCL it runs on the device tensors.  Without a
+        process group (world 1) `parts` is the buffer itself, copied on the device."""
+        import torch.distributed as dist
+        if not self.bound:
+            raise _lib.AvtError("GradExchange.exchange() before bind()")
+        if not self.ordered:
+            raise _lib.AvtError("GradExchange.exchange(): this exchange was made unordered (ordered=False): use all_reduce()")
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.AvtError("GradExchange.exchange() under stream capture: the gather and the sum follow the replay eagerly")
+        if dist.is_available() and dist.is_initialized():
+            if dist.get_world_size(self.group) != self.world:
+                raise _lib.AvtError("GradExchange.exchange(): made for world %d, the process group has %d ranks"
+                                    % (self.world, dist.get_world_size(self.group)))
+            if dist.get_backend(self.group) == "gloo":
+                if self._parts_host is None:
+                    self._parts_host = torch.empty(self.parts.shape, dtype=torch.float32)
+                # (the output as ONE flat vector, rank r's buffer at r * total: gloo takes no [world, total] output for a [total] input)
+                dist.all_gather_into_tensor(self._parts_host.view(-1), self.flat.cpu(), group=self.group)
+                self.parts.copy_(self._parts_host)
+            else:
+                dist.all_gather_into_tensor(self.parts.view(-1), self.flat, group=self.group)
+        elif self.world > 1:
+            raise _lib.AvtError("GradExchange.exchange(): world %d without an initialised process group" % self.world)
+        else:
+            self.parts[0].copy_(self.flat)
+        ops.rank_sum(self.parts, self.flat)
+        CALLS["rank_sum"] += 1
 
     def install(self):
         """p.grad = the parameter's view of the exchange buffer: whatever optimizer steps next steps on the mean gradient, and on the
@@ -843,7 +892,8 @@ def freeze_checkpoint_only_modules(model):
 
 
 def prepare_ranks(model, group=None):
-    """A model for train()'s graphed step across ranks, in place of the DistributedDataParallel wrapper: the checkpoint-only modules
+    """A model for train()'s step across ranks through GradExchange (replayed as a graph with --train_graph 1, eager without; main()
+    prepares it for --train_graph 1 and for --train_deterministic), in place of the DistributedDataParallel wrapper: the checkpoint-only modules
     frozen, then every parameter and buffer broadcast from rank 0 ONCE (afterwards the ranks apply the same all-reduced gradient to the
     same weights; BatchNorm buffers stay per rank and rank 0 writes the checkpoint).  -> the model itself, unwrapped."""
     import torch.distributed as dist

@@ -824,6 +824,19 @@ typedef struct AvtPackJob {
 int avt_pack_job_bytes(void);
 int avt_grad_pack_multi(const void* jobs, const int32_t* blk2job, int nblocks, const float* scale, void* stream);
 
+/* The sum over the ranks of the ORDERED gradient exchange (csrc/rank_sum.hip; the reference: the gradient reduction of
+ * torch.nn.DataParallel onto GPU 0, main.py:420, whose order is the framework's).  The ranks all-gather their packed buffers — data
+ * movement only — and every rank adds the contributions itself, in ascending rank order: the same bits on every rank and every run, which
+ * an all-reduce does not promise.  `parts` is DEVICE fp32 [world][ld]: row r is rank r's contribution, only the first n floats of a row
+ * are read.  `out` is DEVICE fp32 [n], disjoint from `parts`:
+ *     out[i] = fl(... fl(fl(parts[0][i] + parts[1][i]) + parts[2][i]) ... + parts[world - 1][i])
+ * — one fp32 chain per element, every add rounded on its own, nothing reassociated; world == 1 is a copy.  Nothing outside
+ * [out, out + n) is written.  16-byte lanes, 64-bit offsets, the loads of four rows in flight before the first add of a group; the
+ * n % 4 tail takes dword accesses; no LDS, no atomics; `world` is a run-time loop bound.  n == 0 returns AVT_OK without a launch.
+ * AVT_ERR_ARG before any launch for a NULL pointer, world < 1, n < 0, ld < n, ld % 4 != 0, parts or out not 16-byte aligned, or more
+ * than 2^31 - 1 blocks (256 threads, four floats each).  An additive symbol: the ABI version stays 9. */
+int avt_rank_sum_f32(const float* parts, int world, int64_t n, int64_t ld, float* out, void* stream);
+
 /* The training state — parameters, buffers, momentum buffers — copied between its tensors and ONE flat device buffer in one launch
  * (csrc/state_copy.hip), so that an epoch-end checkpoint costs the training stream one kernel and one device-to-host copy instead of one
  * copy per tensor.  A byte-granular copy in the job-table pattern of avt_sgd_multi and avt_grad_pack_multi: `jobs` a DEVICE array of

@@ -1,13 +1,16 @@
 """Time the one-item training step of config 5's per-rank shape (1 query + 15 target clips, SlowFast at 224^2) through avtex.train's own
-machinery, in three forms interleaved in ONE process under a ONE-rank RCCL group (AVT_FORCE_PG=1) on one GPU:
+machinery, in four forms interleaved in ONE process under a ONE-rank RCCL group (AVT_FORCE_PG=1) on one GPU:
 
   ranks   --train_graph 1 across ranks: forward, loss, backward and the gradient pack replayed as a HIP graph; one (self) all-reduce of the
           flat buffer and one eager ArenaSGD launch after every replay (train_ops.GradExchange, train_ops.prepare_ranks)
   world1  the one-process form: --train_graph 1 --train_optimizer hip, the optimizer inside the graph
   ddp     the eager step under DistributedDataParallel (main.wrap_ddp) with ArenaSGD
+  ordered the ranks form with the ORDERED exchange (train_ops.GradExchange(ordered=True): a (self) all-gather into `parts` and one launch
+          of csrc/rank_sum.hip in place of the all-reduce); the weight gradients stay on the default (atomic) path, as in `ranks`, so
+          that the difference to `ranks` is the exchange alone.  At one rank it shows the added launch and copy, not the gather
 
 A round is one call of train() over `--steps` prepared one-item batches (device tensors from dataset.DeviceSegmentBatcher, so that no host
-preprocessing is timed), between two device synchronisations: wall time per step, train()'s loss.item() per step included in all three.
+preprocessing is timed), between two device synchronisations: wall time per step, train()'s loss.item() per step included in all four.
 The first call of each form (warm-up, capture) is not counted.  Prints every round, medians and spreads.  What it cannot measure on one
 GPU: any all-reduce between devices (RCCL with world > 1) and the scaling over 8 GPUs.
 
@@ -32,7 +35,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--steps", type=int, default=12)
-    ap.add_argument("--forms", default="ranks,world1,ddp")
+    ap.add_argument("--forms", default="ranks,world1,ddp,ordered")
     ap.add_argument("--out", default=None, help="also write the log to this file")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -75,9 +78,10 @@ def main():
         model = avtex.ContrastivePredictionTemporal(SlowFast(), SlowFast(), None, 1, 128, temp=0.1, window=ds.window, stride=ds.stride,
                                                     enc_arch="slowfast", img_size=224).to(dev)
         model = train_ops.training_layout(model)
-        args = SimpleNamespace(print_freq=10 ** 9, log_freq=10 ** 9, bn_replicas=1, train_graph=0 if name == "ddp" else 1)
+        args = SimpleNamespace(print_freq=10 ** 9, log_freq=10 ** 9, bn_replicas=1, train_graph=0 if name == "ddp" else 1,
+                               exchange_ordered=name == "ordered")
         with contextlib.redirect_stdout(quiet):
-            if name == "ranks":
+            if name in ("ranks", "ordered"):
                 model = train_ops.prepare_ranks(model)
             elif name == "ddp":
                 model = wrap_ddp(model, dev, local)
@@ -111,8 +115,9 @@ def main():
         forms[n] = form(n)
         before = dict(train_ops.CALLS)
         ms, loss = epoch(forms[n])  # warm-up steps, the capture
-        say("%-6s first call %.1f ms/step (warm-up, capture), loss %.4f; host launches: sgd_multi %d, grad_pack_multi %d" %
-            (n, ms, loss, train_ops.CALLS["sgd_multi"] - before["sgd_multi"], train_ops.CALLS["grad_pack_multi"] - before["grad_pack_multi"]))
+        say("%-7s first call %.1f ms/step (warm-up, capture), loss %.4f; host launches: sgd_multi %d, grad_pack_multi %d, rank_sum %d" %
+            (n, ms, loss, train_ops.CALLS["sgd_multi"] - before["sgd_multi"], train_ops.CALLS["grad_pack_multi"] - before["grad_pack_multi"],
+             train_ops.CALLS["rank_sum"] - before["rank_sum"]))
     apart("after the first %d steps" % len(batches))
     numel = sum(p.numel() for p in forms[names[0]][0].parameters() if p.requires_grad)
     say("%d trainable elements (%.1f MB); %d one-item batches per round" % (numel, numel * 4 / 1e6, len(batches)))
@@ -123,12 +128,15 @@ def main():
         say("round %2d: %s" % (r, "   ".join("%s %.2f ms/step" % (n, times[n][-1]) for n in names)))
     for n in names:
         m = statistics.median(times[n])
-        say("%-6s median %.2f ms/step (min %.2f, max %.2f, spread %.1f %%): %.1f clips/s per rank" %
+        say("%-7s median %.2f ms/step (min %.2f, max %.2f, spread %.1f %%): %.1f clips/s per rank" %
             (n, m, min(times[n]), max(times[n]), 100 * (max(times[n]) - min(times[n])) / m, 16e3 / m))
     apart("after %d steps" % ((a.rounds + 1) * len(batches)))
     if "ranks" in times and "world1" in times:
         say("ranks - world1: %+.2f ms/step (one pack launch, one self all-reduce, one eager optimizer launch)" %
             (statistics.median(times["ranks"]) - statistics.median(times["world1"])))
+    if "ordered" in times and "ranks" in times:
+        say("ordered - ranks: %+.2f ms/step (a self all-gather and one rank_sum launch in place of the self all-reduce)" %
+            (statistics.median(times["ordered"]) - statistics.median(times["ranks"])))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
