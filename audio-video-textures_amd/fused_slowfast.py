@@ -119,9 +119,16 @@ def new_act(m, c, dims, device, x3=False):
 def split_planes(w, plane_dtype):
     """fp32 tensor -> (hi, lo) 16-bit planes typed bfloat16 (raw bits; fp16 planes are bit-cast), value = hi + lo."""
     w = w.detach().float()
-    dt = torch.float16 if plane_dtype == ops.X3_F16 else torch.bfloat16
-    hi = w.to(dt)
-    lo = (w - hi.float()).to(dt)
+    if plane_dtype == ops.X3_F16:
+        # as the device's split2 (csrc/split_planes.h): finite values clamp to the fp16 range, an infinity or a NaN keeps lo = 0
+        # (without either, 65520 became (inf, -inf) and an infinity (inf, NaN): both join to a NaN)
+        fin = torch.isfinite(w)
+        w = torch.where(fin, w.clamp(-65504.0, 65504.0), w)
+        hi = w.to(torch.float16)
+        lo = torch.where(fin, w - hi.float(), torch.zeros_like(w)).to(torch.float16)
+    else:
+        hi = w.to(torch.bfloat16)
+        lo = (w - hi.float()).to(torch.bfloat16)
     return hi.view(torch.bfloat16).contiguous(), lo.view(torch.bfloat16).contiguous()
 
 

@@ -256,7 +256,9 @@ int avt_conv3d_igemm_wfrag_bf16(const void* in, const void* wt, const float* bia
 /* MaxPool3d((1,3,3), stride (1,2,2), pad (0,1,1)) of the SlowFast stems on NDHWC bf16 rows
  * (bt = batch*frames); out may be a channel slice of a wider row buffer (ldo).
  * tgroup > 1: each input row holds `tgroup` consecutive frames of c/tgroup channels (the
- * time-grouped fast stem); the output is un-grouped to bt*tgroup frames of c/tgroup channels. */
+ * time-grouped fast stem); the output is un-grouped to bt*tgroup frames of c/tgroup channels.
+ * No NaN promise (nor from avt_maxpool_hw2s2_ndhwc_bf16): the maximum is taken on integer keys and the bf16
+ * encoder's ReLUs are fmaxf, so a NaN may be dropped or win; only the plane-pair (_x3) pools keep one. */
 int avt_maxpool_hw3s2_ndhwc_bf16(const void* in, void* out, int bt, int h, int w,
                                  int c, int ldi, int ldo, int tgroup, void* stream);
 
@@ -267,7 +269,8 @@ int avt_mean_positions_bf16(const void* in, int batch, int p, int c, int ldi,
                             float* out, int ldo, void* stream);
 
 /* MaxPool2d(2, stride 2), floor mode, of VGGish (audio_models/vggish.py:15-33: the "M" entries of
- * its feature stack) on NHWC bf16 rows; bt = batch, out [bt, h/2, w/2, c] (row stride ldo). */
+ * its feature stack) on NHWC bf16 rows; bt = batch, out [bt, h/2, w/2, c] (row stride ldo).  No NaN promise,
+ * as for avt_maxpool_hw3s2_ndhwc_bf16. */
 int avt_maxpool_hw2s2_ndhwc_bf16(const void* in, void* out, int bt, int h, int w,
                                  int c, int ldi, int ldo, void* stream);
 
