@@ -13,8 +13,12 @@
 // Statistics accumulate in fp64 with NO atomics (hipcc lowers atomicAdd(double) to a compare-and-swap loop, which under a
 // few thousand workgroups per address cost 6x the whole pass — measured, profiles/r02/train_fused_bn_atomics.log): per-thread
 // registers -> a halving tree in LDS -> one row of partials per workgroup -> a finalize launch where one wavefront per channel
-// sums the rows in a fixed order.  The result is bitwise reproducible run to run, and the mean / variance are the correctly
-// rounded ones.  The finalize launch also turns the sums into the per-channel coefficients the apply pass needs, so that
+// sums the rows in a fixed order.  The result is bitwise reproducible run to run, and the saved mean is the correctly rounded
+// one (an fp64 quotient of an fp64 sum, cast once).  The variance is NOT a second pass over x - mean: it is the single-pass fp64
+// difference E[x^2] - mean^2, whose relative error is about k 2^-53 E[x^2] / var for a chain of k fp64 additions (k = a thread's
+// sweeps + the tree's levels + a finalize lane's rows + 6 shuffles, a few tens) — below an fp32 ulp of invstd while |mean| / std
+// stays under a few thousand, and growing with its square beyond (tests/bn_train_refs.py states the bound the tests hold it
+// to).  The finalize launch also turns the sums into the per-channel coefficients the apply pass needs, so that
 // pass reads two floats per channel instead of redoing the fp64 arithmetic in every thread.
 // A thread walks the rows with a stride that is a multiple of the row's float4 chunks, so it always sees the SAME four
 // channels and keeps their partial sums / scale / shift in registers.

@@ -566,7 +566,9 @@ int avt_clip_gather_frames_f32(const float* table, int n_frames, int out_hw, con
 int64_t avt_bn_train_ws_bytes(int64_t m, int c, int groups); /* workspace both calls need (16-byte aligned); -1 outside the domain */
 /* groups (round 3, ABI 3): the m rows are `groups` equal consecutive slabs, each normalised with its OWN batch statistics — the
  * items of a batch as DataParallel replicas see them (main.py:420) in one launch; save_mean / save_invstd are [groups, c], the
- * running statistics take the groups' updates in order, dgamma / dbeta sum over all groups.  1 = plain BatchNorm. */
+ * running statistics and num_batches_tracked take GROUP 0's update only — one momentum step and +1 per call, whatever `groups`
+ * is: DataParallel keeps the buffers of the replica on device 0 and drops the others' (tests/test_gpu_bn_train_edges.py holds
+ * both to that at 1 to 17 groups) —, dgamma / dbeta sum over all groups.  1 = plain BatchNorm. */
 /* relu_mask (round 3; may be NULL): m * c / 4 bytes, 4 bits per float4 chunk of the rows — the forward writes where its output
  * is positive, the backward reads it INSTEAD of y (with a shortcut the mask cannot be recomputed from x: a sixteenth of y's bytes
  * in each of the backward's two passes). */
@@ -578,7 +580,7 @@ int64_t avt_bn_train_ws_bytes(int64_t m, int c, int groups); /* workspace both c
 int avt_bn_train_fwd(const float* x, const float* res, float* y, int64_t m, int c, const float* gamma,
                      const float* beta, float eps, float momentum, int relu, int groups, void* ws, int64_t ws_size,
                      float* save_mean, float* save_invstd, float* running_mean, float* running_var,
-                     int64_t* num_batches_tracked /* incremented (by groups) when not NULL */, void* relu_mask, int64_t ldy,
+                     int64_t* num_batches_tracked /* +1 per call when not NULL (group 0 alone counts - not by groups) */, void* relu_mask, int64_t ldy,
                      void* stream);
 int avt_bn_train_bwd(const float* dy, const float* y, const float* x, int64_t m, int c, const float* gamma,
                      const float* beta, const float* save_mean, const float* save_invstd, int relu, int groups,
