@@ -15,9 +15,9 @@ import torch
 import torch.nn.functional as F
 from torch.utils.data import Dataset
 
-from .audio_frontend import waveform_to_examples
+from .audio_frontend import waveform_to_examples, waveform_to_examples_device
 from .models import process_cv2_inputs
-from .validate import read_audio, read_video
+from .validate import load_audio, read_video
 
 
 class AudioVideoSegments(Dataset):
@@ -59,12 +59,25 @@ class AudioVideoSegments(Dataset):
                 path = os.path.join(self.adata, "{}.wav".format(video_name))
                 assert os.path.exists(path) or os.path.exists(os.path.splitext(path)[0] + ".npz"), \
                     "No audio found at {}".format(path)
-                audio = read_audio(path)
-            self.audio_w, self.sr = audio
+                audio = path
+            # --audio_resample / --audio_load_sr: with kaiser_best and --train_input device the waveform is resampled and its
+            # examples are built on the MI355X (and stay there, where DeviceSegmentBatcher wants them); on the host otherwise
+            resampler, load_sr = getattr(args, "audio_resample", "scipy"), int(getattr(args, "audio_load_sr", 0) or 0)
+            dev = None
+            if resampler == "kaiser_best" and getattr(args, "train_input", "loader") == "device":
+                dev = torch.device("cuda", torch.cuda.current_device())
+            self.audio_w, self.sr = load_audio(audio, load_sr, resampler, dev)
             self.apf = math.floor(self.sr / self.fps)
-            self.audio_w = np.asarray(self.audio_w)[: len(self.video) * self.apf]
-            self.audio_eg = torch.from_numpy(waveform_to_examples(self.audio_w, self.sr)).unsqueeze(dim=1).float()
-            self.audio_w = torch.tensor(self.audio_w)
+            if dev is not None:
+                if not torch.is_tensor(self.audio_w):
+                    self.audio_w = np.asarray(self.audio_w)
+                self.audio_w = self.audio_w[: len(self.video) * self.apf]
+                self.audio_eg = waveform_to_examples_device(self.audio_w, self.sr, dev, resampler).unsqueeze(dim=1)
+                self.audio_w = torch.as_tensor(self.audio_w)
+            else:
+                self.audio_w = np.asarray(self.audio_w)[: len(self.video) * self.apf]
+                self.audio_eg = torch.from_numpy(waveform_to_examples(self.audio_w, self.sr, resampler)).unsqueeze(dim=1).float()
+                self.audio_w = torch.tensor(self.audio_w)
 
     def __len__(self):
         n = math.floor((len(self.video) - self.window) / self.stride)

@@ -5,7 +5,8 @@ loop with the fps -> window/stride override (main.py:511-516) and default checkp
 Additions (all optional): --stitch_mode {compat,aligned}, --ref_num_gpus, --enc_dtype {fp32,bf16},
 --enc_batch, --train_input {loader,device}, --vcam (the flag validate.py:299 reads but the reference never defines [quirk Q2]),
 --ckpt_async (the epoch-end save off the loop: train_ops.StateSnapshot + checkpoint.AsyncCheckpointWriter) and --ckpt_train_state
-(optimizer, scheduler, generators and loader in the checkpoint; --resume then repeats the uninterrupted run).
+(optimizer, scheduler, generators and loader in the checkpoint; --resume then repeats the uninterrupted run),
+--audio_resample {scipy,kaiser_best} and --audio_load_sr (the reference's resampy filter and librosa.load's rate, both off by default).
 Multi-GPU: one process per GPU under torch.distributed.run instead of torch.nn.DataParallel (main.py:420).  --train_input device works
 there too, with or without --train_graph 1: every rank assembles its share of each global batch in its own HBM
 (dataset.DeviceSegmentBatcher(rank, world)), item for item the batch DataParallel would scatter from one NumPy stream.
@@ -159,6 +160,15 @@ def build_parser():
       help="encoders at -e: SlowFast on the hand-written MFMA convolutions (auto/mfma) or the nn.Module on MIOpen (module); "
            "ResNet3d (resnet10/18/34/50) on the contract-grade MFMA kernels with mfma (fp32 = f16x3, or bf16x3; not bf16), "
            "the nn.Module with auto / module")
+    a("--audio_resample", default="scipy", choices=["scipy", "kaiser_best"],
+      help="how audio at another rate is brought to VGGish's 16 kHz (and to --audio_load_sr): scipy = scipy.signal.resample_poly on the "
+           "host (default); kaiser_best = resampy's windowed-sinc interpolation with its default filter, what the reference computes "
+           "(vggish_utils.py:27-69) — on the MI355X in validate() and with --train_input device (csrc/resample.hip), the same "
+           "arithmetic in NumPy on the DataLoader's host path")
+    a("--audio_load_sr", default=0, type=int,
+      help="resample every decoded source and driving waveform to this rate first and round it to float32, as librosa.load does in "
+           "the reference (validate.py:154, 172; 22050 is librosa's rate); audio samples per frame then follow this rate.  0 "
+           "(default) keeps the file's rate")
     a("--dump_png", default=False, action="store_true",
       help="also write the reference's per-frame PNG folder (validate.py:789-792); default: frames go to the encoder directly")
     a("--vcam", default=False, action="store_true", help="defined for validate.py:299; CAM dumps are out of scope")

@@ -1160,6 +1160,29 @@ def logmel_examples(lm, ex_len, ex_hop):
     return out
 
 
+RESAMPLE_BLOCK = 256  # outputs per workgroup of csrc/resample.hip (kThreads there)
+
+
+def resample_sinc(wave, win, delta, num_table, scale, inc, step, n_out, out_dtype=torch.float64):
+    """wave [n_in] fp32/fp64, win / delta [n_win] fp64 (device) -> [n_out] fp64 or fp32: resampy's windowed-sinc interpolation,
+    one sequential fp64 sum per output (audio_frontend.sinc_plan supplies every argument after `wave`)."""
+    if wave.dtype not in (torch.float32, torch.float64):
+        raise _lib.AvtError("resample_sinc: waveform must be float32 or float64, got %s" % wave.dtype)
+    if out_dtype not in (torch.float32, torch.float64):
+        raise _lib.AvtError("resample_sinc: output must be float32 or float64, got %s" % out_dtype)
+    _dev(wave, "wave", wave.dtype)
+    _dev(win, "win", torch.float64)
+    _dev(delta, "delta", torch.float64)
+    if wave.dim() != 1 or win.dim() != 1 or delta.shape != win.shape:
+        raise _lib.AvtError("resample_sinc: wave [n_in], win [n_win] and delta [n_win] expected, got %s, %s, %s"
+                            % (tuple(wave.shape), tuple(win.shape), tuple(delta.shape)))
+    out = torch.empty((int(n_out),), dtype=out_dtype, device=wave.device)
+    K.avt_resample_sinc_f64(_p(wave), int(wave.dtype == torch.float64), int(wave.numel()), _p(win), _p(delta), int(win.numel()),
+                            int(num_table), float(scale), float(inc), int(step), _p(out), int(out_dtype == torch.float64), int(n_out),
+                            _stream())
+    return out
+
+
 # ---- fused training branch ----------------------------------------------------------------
 def infonce_fwd(q, t, temp, eps=1e-12):
     """q [b,d], t [b,n,d] fp32 -> (logits [b,n], inv_q [b], inv_t [b,n])."""

@@ -73,6 +73,31 @@ def read_audio(path):
         return w.astype(np.float32), int(sr)
 
 
+def load_audio(path_or_pair, load_sr=0, resampler="scipy", device=None):
+    """read_audio (or an already decoded (waveform, rate) pair) followed by what librosa.load does to it in the reference
+    (validate.py:154, 172): with load_sr > 0 and a decoded rate that differs from it, the mono waveform is resampled to load_sr,
+    rounded to float32 (the type librosa.load returns) and load_sr is reported as the rate; `[: n_in * apf]` and apf then use that
+    rate.  resampler: "kaiser_best" = the reference's filter (audio_frontend.resample_sinc), on `device` when one is given — the
+    float32 waveform then stays there as a device tensor; "scipy" = the polyphase resampler, on the host.  load_sr = 0 (the
+    default) keeps the file's rate: the pair comes back as read."""
+    wave, sr = path_or_pair if isinstance(path_or_pair, (tuple, list)) else read_audio(path_or_pair)
+    if not load_sr or load_sr <= 0 or int(sr) == int(load_sr):
+        return wave, sr
+    from . import audio_frontend as af
+
+    wave = np.asarray(wave)
+    if wave.ndim > 1:
+        wave = wave.mean(axis=1)
+    if resampler == "kaiser_best" and device is not None:
+        return af.resample_sinc_device(wave, sr, load_sr, device, out_dtype=torch.float32), int(load_sr)
+    return af._resampler(resampler)(wave, sr, load_sr).astype(np.float32), int(load_sr)
+
+
+def _host_wave(wave):
+    """A waveform for the host's own consumers (the wav written beside the output video): a device tensor comes down here, only."""
+    return wave.cpu().numpy() if torch.is_tensor(wave) else wave
+
+
 def audio_start_segment(audio_eg, driving_eg0):
     """validate.py:223-240: first segment whose flattened log-mel has the highest cosine similarity with
     the first driving example (strict '>', initial max_sim 0, q_id 0)."""
@@ -129,6 +154,8 @@ def validate(model, args, video_name="", epoch=None, tb_logger=None, model_type=
     input_video = video[idxs]  # [Q1] prepared for every model_type
     n_in = len(input_video)
 
+    # --audio_resample / --audio_load_sr (not in the reference's parser: its librosa.load and resampy calls are what they select)
+    resampler, load_sr = getattr(args, "audio_resample", "scipy"), int(getattr(args, "audio_load_sr", 0) or 0)
     audio_w, apf = None, 10
     audio_eg = torch.rand((math.floor((len(video) - W) / S)), 10)  # [Q8] consumes torch RNG like validate.py:148
     sr = None
@@ -136,10 +163,10 @@ def validate(model, args, video_name="", epoch=None, tb_logger=None, model_type=
         print("Preparing source audio. ")
         path = os.path.join(args.adata, "{}.wav".format(video_name)) if args.adata is not None else None
         if audio is not None or (path and (os.path.exists(path) or os.path.exists(os.path.splitext(path)[0] + ".npz"))):
-            audio_w, sr = audio if audio is not None else read_audio(path)
+            audio_w, sr = load_audio(audio if audio is not None else path, load_sr, resampler, dev)
             apf = math.floor((sr * sub) / args.fps)
-            audio_w = np.asarray(audio_w)[: n_in * apf]
-            audio_eg = waveform_to_examples_device(audio_w, sr * sub, dev).unsqueeze(dim=1)  # STFT/mel/log on the GPU
+            audio_w = (audio_w if torch.is_tensor(audio_w) else np.asarray(audio_w))[: n_in * apf]
+            audio_eg = waveform_to_examples_device(audio_w, sr * sub, dev, resampler).unsqueeze(dim=1)  # STFT/mel/log on the GPU
     print("Preparing driving audio. ")
     driving_audio_name, driving_audio_eg, driving_audio_w = None, None, None
     if getattr(args, "driving_audio", None) is not None or driving_audio is not None:
@@ -147,9 +174,11 @@ def validate(model, args, video_name="", epoch=None, tb_logger=None, model_type=
         if driving_audio is None:
             da_path = os.path.join(args.dadata, driving_audio_name + ".wav")
             assert os.path.exists(da_path), "No driving audio found at {}".format(da_path)
-            driving_audio = read_audio(da_path)
-        driving_audio_w, sr_da = driving_audio
-        driving_audio_eg = waveform_to_examples_device(np.asarray(driving_audio_w), sr_da * sub, dev).unsqueeze(dim=1)
+            driving_audio = da_path
+        driving_audio_w, sr_da = load_audio(driving_audio, load_sr, resampler, dev)
+        if not torch.is_tensor(driving_audio_w):
+            driving_audio_w = np.asarray(driving_audio_w)
+        driving_audio_eg = waveform_to_examples_device(driving_audio_w, sr_da * sub, dev, resampler).unsqueeze(dim=1)
     print("Initializing interpolation model. ")
     intp_model, timeline = None, None
     if getattr(args, "interpolation", False) and rank == 0:
@@ -405,7 +434,7 @@ def _write_result(args, video_name, video, new_frames, driving_audio_w, driving_
             from scipy.io import wavfile
 
             audio_file = os.path.join(results_folder, "audio_{}_{}.wav".format(video_name, new_video_id))
-            wavfile.write(audio_file, int(sr or 16000), np.asarray(driving_audio_w[: len(new_frames) * apf], np.float32))
+            wavfile.write(audio_file, int(sr or 16000), np.asarray(_host_wave(driving_audio_w[: len(new_frames) * apf]), np.float32))
         print("Saving frames.")
         frames = timeline.frames(video)
         if getattr(args, "frames_bar", False):
@@ -435,7 +464,7 @@ def _write_result(args, video_name, video, new_frames, driving_audio_w, driving_
         from scipy.io import wavfile
 
         audio_file = os.path.join(results_folder, "audio_{}_{}.wav".format(video_name, new_video_id))
-        wavfile.write(audio_file, int(sr or 16000), np.asarray(driving_audio_w[: len(new_frames) * apf], np.float32))
+        wavfile.write(audio_file, int(sr or 16000), np.asarray(_host_wave(driving_audio_w[: len(new_frames) * apf]), np.float32))
     print("Saving frames.")
     if dump_png:
         save_videos(out_dir, out_dir + ".mp4", args.fps, audio_file=audio_file)

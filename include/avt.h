@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define AVT_ABI_VERSION 9  /* 9: the entries of the two former extension headers (the deterministic weight gradients, the one-launch state copy) folded in, their two extension version entries removed; 8: avt_res2_x3, avt_weight_planes_gather_f32, avt_weight_planes_multi (round 6); 7: BatchNorm statistics on the producing convolution's epilogue: avt_conv3d_igemm_x3_f32_stats, avt_bn_train_fwd_pre (round 5); 2: avt_bn_train_fwd gained num_batches_tracked (round 2); 3: avt_bn_train_* take groups (+ beta, relu in bwd), avt_stem_conv_x3 takes frames_per_tile (round 3); 4: avt_stem_conv_pool_x3 removed, avt_stem_conv_x3 / avt_maxpool_hw3s2_ndhwc_x3 take a frame index, avt_stem_conv_x3_merged, avt_lateral_x3 (round 4); 5: avt_bn_train_fwd / _bwd and avt_maxpool_train_fwd / _bwd take the leading dimension of y / dy (round 4); 6: avt_pw_x3_f32 (round 4) */
+#define AVT_ABI_VERSION 10  /* 10: avt_resample_sinc_f64, the windowed-sinc resampler of the audio front end (round 27); 9: the entries of the two former extension headers (the deterministic weight gradients, the one-launch state copy) folded in, their two extension version entries removed; 8: avt_res2_x3, avt_weight_planes_gather_f32, avt_weight_planes_multi (round 6); 7: BatchNorm statistics on the producing convolution's epilogue: avt_conv3d_igemm_x3_f32_stats, avt_bn_train_fwd_pre (round 5); 2: avt_bn_train_fwd gained num_batches_tracked (round 2); 3: avt_bn_train_* take groups (+ beta, relu in bwd), avt_stem_conv_x3 takes frames_per_tile (round 3); 4: avt_stem_conv_pool_x3 removed, avt_stem_conv_x3 / avt_maxpool_hw3s2_ndhwc_x3 take a frame index, avt_stem_conv_x3_merged, avt_lateral_x3 (round 4); 5: avt_bn_train_fwd / _bwd and avt_maxpool_train_fwd / _bwd take the leading dimension of y / dy (round 4); 6: avt_pw_x3_f32 (round 4) */
 
 typedef enum {
   AVT_OK = 0,
@@ -1014,6 +1014,24 @@ int avt_logmel_f64(const void* wave, int wave_is_f64, int64_t n_samples,
  * out[e, r, m] = (float) logmel[e*ex_hop + r, m], n_ex = 1 + (n_frames - ex_len) / ex_hop. */
 int avt_logmel_examples_f32(const double* logmel, int64_t n_frames, int n_mel,
                             int ex_len, int ex_hop, float* out, void* stream);
+
+/* Band-limited resampling of a mono waveform by resampy 0.4's windowed-sinc interpolation (the reference's resampy.resample in
+ * vggish_utils.py:27-69 and librosa.load in validate.py:154, 172, filter "kaiser_best"), in float64.
+ * x [n_in] float32 (x_is_f64 = 0) or float64 device samples; win / delta [n_win]: the right half of the windowed sinc with
+ * num_table entries per zero crossing (already scaled by the ratio when downsampling) and its forward differences, last one 0 —
+ * float64 device tables built by the caller; scale = min(1, ratio), time_increment = 1 / ratio and index_step =
+ * int(scale * num_table) come from the caller too.  Output t, with tr = t * time_increment, n = int(tr), frac = scale * (tr - n):
+ *   left wing:  idx = frac * num_table, off = int(idx), eta = idx - off;
+ *               for i in 0 .. min(n + 1, (n_win - off) / index_step) - 1:  acc += (win[o] + eta * delta[o]) * x[n - i], o = off + i * index_step
+ *   right wing: frac = scale - frac, idx / off / eta again;
+ *               for k in 0 .. min(n_in - n - 1, (n_win - off) / index_step) - 1:  acc += (win[o] + eta * delta[o]) * x[n + k + 1]
+ * One lane sums one output in that order without contraction: y is bit-identical to the same statement in NumPy float64.
+ * y [n_out] float64 (y_is_f64 = 1) or float32 (the float64 sum rounded to nearest even).  n_out == 0 launches nothing.
+ * AVT_ERR_ARG: a NULL pointer with n_out > 0; index_step < 1, n_win < 1, num_table < 1, n_in < 0 or n_out < 0; scale outside (0, 1] or
+ * scale * num_table >= n_win; time_increment <= 0 or (n_out - 1) * time_increment >= n_in (an output centred past the input). */
+int avt_resample_sinc_f64(const void* x, int x_is_f64, int64_t n_in, const double* win, const double* delta,
+                          int n_win, int num_table, double scale, double time_increment, int index_step,
+                          void* y, int y_is_f64, int64_t n_out, void* stream);
 
 #ifdef __cplusplus
 }
