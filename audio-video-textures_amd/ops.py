@@ -628,7 +628,7 @@ def weight_planes_job_bytes():
 
 def weight_planes_multi(jobs, blk2job, nblocks):
     """Every job of a DEVICE table of AvtPlaneJob (include/avt.h) in one launch: the planes of all of a step's weights, in place
-    (train_ops._refresh_planes builds the table from the single launches' own arguments)."""
+    (weight_planes.PlaneCache.refresh builds the table from the single launches' own arguments)."""
     assert jobs.is_cuda and blk2job.is_cuda and blk2job.dtype == torch.int32 and blk2job.numel() == nblocks
     K.avt_weight_planes_multi(_p(jobs), _p(blk2job), int(nblocks), _stream())
 

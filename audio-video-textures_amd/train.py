@@ -81,11 +81,7 @@ def train(train_loader, model, optimizer, args, epoch, tb_logger=None):
                     # re-make launch is then part of the graph and every replay splits the weights it finds — which the step hook of the
                     # last warm-up step leaves behind
                     saved = _snapshot(model, optimizer)
-
-                    def stale_planes():
-                        assert train_ops.weight_cache_is_stale(), "the capture would start from current weight planes: no re-make in the graph"
-
-                    ent = graphed[key] = (static, train_ops.GraphedStep(device_step, static[0].device, warmup=2, before_capture=stale_planes))
+                    ent = graphed[key] = (static, train_ops.GraphedStep(device_step, static[0].device, warmup=2, before_capture=_stale_planes))
                     _restore(saved)
                     train_ops.invalidate_weight_cache()
                 else:
@@ -126,6 +122,11 @@ def train(train_loader, model, optimizer, args, epoch, tb_logger=None):
                 tb_logger.log_scalar(value, key, iter_count)
             tb_logger.flush()
     return losses.avg
+
+
+def _stale_planes():
+    """GraphedStep's before_capture check of a step whose weight planes the capture must re-make."""
+    assert train_ops.weight_cache_is_stale(), "the capture would start from current weight planes: no re-make in the graph"
 
 
 def _snapshot(model, optimizer):
@@ -193,11 +194,7 @@ def _graphed_ranks_step(model, optimizer, criterion, args, static, nq, nt, batch
     # optimizer — so that the first replay is the ONE step the batch takes.  State the optimizer did not have yet (torch's SGD creates
     # its momentum buffers at the first step) is restored as absent
     saved, absent = _snapshot(model, optimizer), _stateless(optimizer)
-
-    def stale_planes():
-        assert train_ops.weight_cache_is_stale(), "the capture would start from current weight planes: no re-make in the graph"
-
-    step = train_ops.GraphedStep(device_step, static[0].device, warmup=2, before_capture=stale_planes,
+    step = train_ops.GraphedStep(device_step, static[0].device, warmup=2, before_capture=_stale_planes,
                                  after_warmup=lambda: _exchange_and_step(optimizer, exchange))
     _restore(saved)
     for p in absent:

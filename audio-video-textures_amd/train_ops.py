@@ -18,20 +18,23 @@ per product, fp32's exponent range; fp32 atomics in the weight gradient, so its 
 the reference's fp32 (train.py:114-141); "fp32" leaves every convolution to MIOpen's fp32 kernels (what the reference runs)
 and keeps only the fused BatchNorm passes.  tests/test_gpu_train_step.py bounds the loss / gradient deviation of "x3" from an
 fp64 step by the deviation of the stock fp32 step.
-Weight planes are cached per tensor and rebuilt when `weight._version` changes (optimizer.step(), load_state_dict, any
-in-place op on the parameter).  In-place updates through `.data` (EMA / momentum encoders, `p.data.clamp_()`) do NOT bump
-that counter: call `invalidate_weight_cache()` after them (train.train() does after every optimizer step)."""
+Weight planes are cached per tensor (weight_planes.py: the cache, its validity rule and the four makers of planes) and re-made
+when `weight._version` changes (optimizer.step(), load_state_dict, any in-place op on the parameter), after every optimizer
+step of the process and after a GraphedStep's capture.  In-place updates through `.data` (EMA / momentum encoders,
+`p.data.clamp_()`) do NOT bump that counter: call `invalidate_weight_cache()` after them (train.train() does after every
+optimizer step).  The device job tables of the step's multi-tensor launches and the launch counters (CALLS) are job_tables.py's."""
 import contextlib
 import struct
 import weakref
-from collections import namedtuple
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import _lib, ops
-from .ops import _RAW_STREAM, K, _p, _stream
+from . import _lib, ops, weight_planes
+from .job_tables import _PACK_JOB, _SGD_JOB, CALLS, _chunks, _JobTable, _pack_jobs  # noqa: F401  (CALLS: read as train_ops.CALLS)
+from .ops import K, _p, _stream
+from .weight_planes import _grouped_planes, _weight_planes, pack_plane_jobs  # noqa: F401  (pack_plane_jobs: tests/test_abi.py)
 
 # Which passes of the training step run on the hand-written kernels.  Module constants (no environment switches since round 4);
 # `set_conv_mode` (main.py --train_conv) is the user-facing switch, tests set some of these to 0 for the stock-op reference path.
@@ -40,7 +43,6 @@ _CONV_X3 = 1        # convolution forward / stride-1 input gradient on conv_x3 (
 _WGRAD_X3 = 1       # weight gradient on csrc/wgrad_x3.hip
 _DGRAD_S_X3 = 1     # strided input gradients as residue-class convolutions on conv_x3 (0: MIOpen's bwd_data)
 _STEM_WGRAD_X3 = 1  # the stems' weight gradient on the hand-written kernels
-_PLANES_HIP = 1     # weight planes by csrc/stem_train.hip's two kernels (0: torch ops)
 _STEM_PATCH = 1     # the stems on the patch-resident kernels (0: conv_x3 + wgrad slices)
 _FORK = 1           # the shortcut's gradient summed in the a-convolution's input-gradient epilogue
 _EPI_STATS = 1      # BatchNorm forward statistics on the producing convolution's epilogue (round 5: no statistics pass over its output)
@@ -90,35 +92,15 @@ def deterministic():
 
 def invalidate_weight_cache(drop=False):
     """Mark every cached set of weight planes stale (needed after in-place updates through `.data`, which `_version` does not see): the
-    next lookup re-makes them — all of them in one launch (_refresh_planes).  drop=True forgets the entries themselves (tests that
-    compare two ways of MAKING the planes)."""
-    _PLANES_GEN[0] += 1
-    if drop:
-        _PLANES.clear()
-        for tabs in _PLANE_JOBS.values():
-            tabs.forget()
-    _STEM_IMAGES.clear()
+    next lookup re-makes them — all of them in one launch.  drop=True forgets the entries themselves (tests that compare two ways of
+    MAKING the planes)."""
+    weight_planes.CACHE.invalidate(drop)
 
 
-# Optimizers that update their parameters without moving Tensor._version — torch's FUSED kernels (SGD / Adam(W) with fused=True:
-# measured, _version 0 -> 0 over optimizer.step(), tools/experimental/debug_sgd_arena.py), updates through `.data` — would leave the
-# version-keyed plane cache serving the OLD weights to every convolution after them.  Every optimizer step of the process therefore
-# marks the cache stale (one global hook; the next lookup re-makes all planes in one launch, which a version bump would have asked for too).
-try:
-    from torch.optim.optimizer import register_optimizer_step_post_hook as _register_step_hook
-
-    _STEP_HOOK = _register_step_hook(lambda *_a, **_k: invalidate_weight_cache())
-except ImportError:  # (torch < 2.0: callers invalidate by hand, as train() always has)
-    _STEP_HOOK = None
-
-
-# per-process launch counters of the hand-written training kernels (tests assert that the default path really runs them)
-CALLS = {"conv_fwd_x3": 0, "dgrad_x3": 0, "dgrad_strided_x3": 0, "wgrad_x3": 0, "wgrad_stem_x3": 0, "bn_fwd": 0, "bn_bwd": 0,
-         "miopen_dgrad": 0, "miopen_wgrad": 0, "stem_fwd_patch": 0, "wgrad_stem_patch": 0, "maxpool_hip": 0, "pw_f32": 0,
-         "bn_fwd_pre": 0, "bn_bwd_pre": 0, "dgrad_bwdstats": 0, "planes_multi": 0, "maxpool3d_hip": 0, "sgd_multi": 0, "grad_pack_multi": 0,
-         "wgrad_det": 0,  # (wgrad_det: launches of the deterministic weight-gradient entries, counted next to the rows above)
-         "state_copy_multi": 0,
-         "rank_sum": 0}  # (rank_sum: launches of the ordered exchange's sum over the ranks, GradExchange.exchange)
+def weight_cache_is_stale():
+    """True when no cached set of weight planes is current (every lookup re-makes its planes): the state a capture must start from
+    for the re-make launch to be part of its graph."""
+    return weight_planes.CACHE.is_stale()
 
 
 def _rows(x):
@@ -431,105 +413,12 @@ class GraphedStep:
         with torch.cuda.graph(g, stream=self.stream):
             self.out = step_fn()
         self.graph = g
+        # the capture's lookups marked weight planes current and recorded their refresh event although nothing ran
+        weight_planes.CACHE.capture_ended(device)
 
     def __call__(self):
         self.graph.replay()
         return self.out
-
-
-# ------------------------------------------------------------------------------------------------------------------------
-# Device job tables.  A training step has three launches that each cover many tensors (ops.sgd_multi, ops.grad_pack_multi,
-# ops.weight_planes_multi): the kernel reads a device table of jobs and a block -> job map, both built on the host.  One packer
-# (_pack_jobs) and one owner (_JobTable) serve the three, so the rules of a table's lifetime under stream capture are written once.
-_SGD_CHUNK = 4096  # elements per block (csrc/sgd.hip and csrc/grad_pack.hip kChunk)
-_SGD_JOB, _PACK_JOB, _PLANE_JOB = "<3Qq2i", "<2Qq2i", "<5Q12i32i"  # AvtSgdJob, AvtPackJob, AvtPlaneJob (include/avt.h)
-
-
-def _chunks(numel):
-    return (int(numel) + _SGD_CHUNK - 1) // _SGD_CHUNK
-
-
-def _pack_jobs(recs, blocks_of, row):
-    """blocks_of(rec) -> blocks of the job, row(rec, blk0) -> the job's struct as bytes -> (job table as bytes, blk2job int32 array,
-    blocks): job n owns blocks_of(rec) consecutive blocks from its blk0."""
-    raw, blk, b0 = [], [], 0
-    for n, rec in enumerate(recs):
-        nb = blocks_of(rec)
-        raw.append(row(rec, b0))
-        blk.append(np.full(nb, n, dtype=np.int32))
-        b0 += nb
-    return b"".join(raw), (np.concatenate(blk) if blk else np.zeros(0, np.int32)), b0
-
-
-_Table = namedtuple("_Table", "key jobs blk2job blocks captured keep")  # jobs, blk2job: views of ONE uploaded device buffer
-
-
-class _JobTable:
-    """The device job table of one multi-tensor launch and what keeps it valid:
-
-    * `table`: the table of the last launch.  get() reuses it while the key (the tuple of addresses) is unchanged — the same tensors
-      at the same addresses every step: built once — and it was not built under capture: such a table is filled by its own graph's
-      replays only, so no later launch uses it.
-    * `kept`: every table a stream capture launched with.  A HIP graph holds its address: it outlives every later rebuild.
-    * the spare pinned buffer: a table built under capture is uploaded by a copy that is a node of the graph and re-reads its pinned
-      source on every replay.  No pinned allocation inside a capture, so reserve() sets the buffer aside before one.
-
-    capture_builds: what a capture does with a key it does not know.  True (the optimizer and the gradient pack: a captured step's
-    gradients live in the graph's own pool, their addresses are not known before the capture): build, staged in the spare buffer.
-    False (the weight planes: the weights do not move, the warm-up has built the table): get() -> None and the caller does without
-    the launch."""
-
-    def __init__(self, who, fmt, sizeof, remedy=None, capture_builds=True):
-        # who, remedy: the caller and the calls that reserve for it, for the refusal's text; sizeof(): the library's view of fmt
-        self.who, self.fmt, self.sizeof, self.remedy, self.capture_builds = who, fmt, sizeof, remedy, capture_builds
-        self.table, self.kept, self._spare, self._alive = None, [], None, []
-
-    def reserve(self, blocks):
-        """Outside a capture: a pinned buffer for the largest table the next get() under capture may stage in it.  blocks: the blocks
-        of each of its jobs, as the caller's packer counts them (an iterable, read only when no buffer is held)."""
-        if self._spare is None:
-            blocks = list(blocks)
-            nbytes = struct.calcsize(self.fmt) * len(blocks) + 4 * sum(blocks)
-            self._spare = torch.empty(max(nbytes, 8), dtype=torch.uint8, pin_memory=True)
-
-    def unreserve(self):
-        self._spare = None
-
-    def keep_alive(self, obj):
-        """Something else a captured launch read, kept for as long as the tables (not in `kept`: that lists tables only)."""
-        self._alive.append(obj)
-
-    def forget(self):
-        """The next get() builds anew.  What captures launched with stays."""
-        self.table = None
-
-    def get(self, key, device, pack):
-        """-> the table for `key` on the current stream, uploaded (one copy) when it had to be built: pack() -> (job table as bytes,
-        blk2job, blocks), called for a new table only (the caller's checks of the tensors behind the key belong in it)."""
-        capturing = torch.cuda.is_current_stream_capturing()
-        tab = self.table
-        if tab is None or tab.key != key or tab.captured:
-            if capturing and not self.capture_builds:
-                return None
-            raw, blk, blocks = pack()
-            assert len(raw) == len(key) * self.sizeof() == len(key) * struct.calcsize(self.fmt), "%s: job struct layout" % self.who
-            data = torch.from_numpy(np.frombuffer(raw + blk.tobytes(), dtype=np.uint8).copy())  # jobs and blk2job: one buffer, one copy
-            dev = torch.empty(data.numel(), dtype=torch.uint8, device=device)
-            if capturing:
-                host, self._spare = self._spare, None  # (this table keeps it from now on: its graph re-reads it on every replay)
-                if host is None or host.numel() < data.numel():
-                    raise _lib.AvtError("%s under stream capture: no staging buffer is left (two captures in a row: call %s outside a "
-                                        "capture between them)" % (self.who, self.remedy))
-                host[:data.numel()].copy_(data)
-                ops.sgd_upload(dev, host, data.numel())
-            else:
-                host = data.pin_memory()  # (a new pinned tensor per table: an earlier copy may be in flight)
-                dev.copy_(host, non_blocking=True)
-            # (keep: not the tensors behind the addresses — held, gradients would never return to the allocator and move every step)
-            tab = self.table = _Table(key, dev[:len(raw)], dev[len(raw):].view(torch.int32), blocks, capturing, (host, dev))
-        if capturing and not any(t is tab for t in self.kept):
-            self.kept.append(tab)
-        return tab
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -1112,16 +1001,6 @@ class StateSnapshot:
         invalidate_weight_cache()
 
 
-def weight_cache_is_stale():
-    """True when no cached set of weight planes is current (every lookup re-makes its planes): the state a capture must start from
-    for the re-make launch to be part of its graph."""
-    for ent in _PLANES.values():
-        owner = ent.ref()
-        if owner is not None and not ent.stale(owner):
-            return False
-    return True
-
-
 # ------------------------------------------------------------------------------------------------------------------------
 # Gradient accumulation over micro-batches (one optimizer step = several forward/backward passes: config 5's batch of 8 items
 # on fewer than 8 GPUs, each item with its own BatchNorm statistics as a DataParallel replica has, main.py:420).  Left to
@@ -1241,110 +1120,7 @@ class MicroBatchGradients:
 # planes: gradients need fp32's exponent range) per product instead of the fp32 MFMA's rate of 1/16 of the bf16 pipe.
 # The weight gradient is csrc/wgrad_x3.hip (bf16 planes, transposing LDS stage, split over positions with fp32 atomics);
 # the strided layers' input gradients are `_dgrad_strided` below; the stems have kernels of their own (`_StemX3`).
-_TABS, _PLANES = {}, {}
-_PLANES_MULTI = 1      # stale planes are re-made by ONE launch over every cached weight (0: one by one, as rounds 3-5 did; tests)
-_PLANES_GEN = [0]      # invalidate_weight_cache() bumps it
-_PLANE_JOBS = {}       # device -> _JobTable of the multi-job launch
-_PLANE_REFRESH = {}    # device -> {"id", "event", "stream", "waited": {stream handle: id}}
-
-
-class _PlaneEntry:
-    """A cached set of weight planes: `value` is what the lookup returns; `jobs` describes the launches that made its tensors
-    (None: not re-makeable in place — torch-assembled forms), as dicts {"off": byte offset of the source in the owner's storage,
-    "fields": the AvtPlaneJob fields after `w` up to `blk0`, "sel": taps, "blocks": grid size}."""
-    __slots__ = ("ref", "version", "gen", "value", "jobs", "sig")
-
-    def __init__(self, owner, value, jobs=None):
-        self.ref, self.version, self.gen, self.value, self.jobs = weakref.ref(owner), owner._version, _PLANES_GEN[0], value, jobs
-        self.sig = (tuple(owner.shape), tuple(owner.stride()), owner.dtype)  # what the jobs' sizes and offsets were derived from
-
-    def stale(self, owner):
-        return self.version != owner._version or self.gen != _PLANES_GEN[0]
-
-
-def _job_rows(w, owner, hi, lo, ws, f16, rows, k, idx_map=None):
-    kind = 0 if idx_map is None else 2
-    return {"off": w.data_ptr() - owner.data_ptr(), "blocks": int(rows),
-            "fields": (hi.data_ptr(), lo.data_ptr(), ws.data_ptr() if ws is not None else 0, idx_map.data_ptr() if idx_map is not None else 0,
-                       kind, int(bool(f16)), int(rows), int(k), 0, 0, 0, 0, 0, 0),
-            "sel": (), "keep": (hi, lo, ws, idx_map)}
-
-
-def _job_transposed(w, owner, hi, lo, cout, taps, cin, sel):
-    gx, gy = (cin + 31) // 32, (cout + 31) // 32
-    return {"off": w.data_ptr() - owner.data_ptr(), "blocks": gx * gy * len(sel),
-            "fields": (hi.data_ptr(), lo.data_ptr(), 0, 0, 1, 0, 0, 0, int(cout), int(taps), int(cin), len(sel), gx, gy),
-            "sel": tuple(int(v) for v in sel), "keep": (hi, lo)}
-
-
-def pack_plane_jobs(jobs):
-    """jobs: (address of the owner's storage, job dict of _job_rows / _job_transposed) per launch -> (AvtPlaneJob table as bytes,
-    blk2job int32 array, blocks): job n reads its source at the address + "off", has `sel` zero-padded to 32 taps and owns "blocks"
-    consecutive blocks from its blk0 (include/avt.h)."""
-    return _pack_jobs(jobs, lambda r: r[1]["blocks"],
-                      lambda r, b0: struct.pack(_PLANE_JOB, r[0] + r[1]["off"], *r[1]["fields"], b0, 0,
-                                                *r[1]["sel"], *(0,) * (32 - len(r[1]["sel"]))))
-
-
-def _refresh_planes(device):
-    """Re-make EVERY stale cached plane set of `device` whose recipe is known, in place, with one launch (ops.weight_planes_multi);
-    -> False when there was nothing to do.  Other streams order themselves behind the launch in _plane_lookup (one event)."""
-    todo = []
-    for ent in list(_PLANES.values()):
-        owner = ent.ref()
-        if owner is not None and ent.jobs and owner.device == device and ent.stale(owner):
-            if ent.sig != (tuple(owner.shape), tuple(owner.stride()), owner.dtype):
-                ent.jobs = None  # (`param.data = other layout`: the recipe is void; the lookup misses and the planes are made anew)
-                continue
-            todo.append((ent, owner))
-    if not todo:
-        return False
-    jobs = [(owner.data_ptr(), j) for ent, owner in todo for j in ent.jobs]
-    tabs = _PLANE_JOBS.get(device)
-    if tabs is None:
-        # capture_builds=False: the weights' addresses do not move, so the warm-up's table serves the capture (and is then kept alive)
-        tabs = _PLANE_JOBS[device] = _JobTable("the weight-plane refresh", _PLANE_JOB, ops.weight_planes_job_bytes, capture_builds=False)
-    tab = tabs.get(tuple((base + j["off"],) + j["fields"] + j["sel"] for base, j in jobs), device, lambda: pack_plane_jobs(jobs))
-    if tab is None:
-        return False  # (a capture whose warm-up did not see this set of weights: no host-to-device copy inside it — one by one, as before)
-    with torch.no_grad():
-        ops.weight_planes_multi(tab.jobs, tab.blk2job, tab.blocks)
-    for ent, owner in todo:
-        ent.version, ent.gen = owner._version, _PLANES_GEN[0]
-    cur = torch.cuda.current_stream(device)
-    r = _PLANE_REFRESH.setdefault(device, {"id": 0, "waited": {}})
-    r["id"] += 1
-    r["event"] = torch.cuda.Event()
-    r["event"].record(cur)
-    r["stream"] = cur
-    r["waited"] = {}
-    CALLS["planes_multi"] += 1
-    return True
-
-
-def _plane_lookup(key, owner):
-    """The cached planes under `key` if they are `owner`'s and current — made current, together with every other stale entry, by one
-    launch when only the optimizer step lies between (same tensors, new values) — else None."""
-    ent = _PLANES.get(key)
-    if ent is None or ent.ref() is not owner:
-        return None
-    if ent.stale(owner):
-        if not (_PLANES_MULTI and ent.jobs and owner.is_cuda and _refresh_planes(owner.device)) or ent.stale(owner):
-            return None
-    r = _PLANE_REFRESH.get(owner.device) if owner.is_cuda else None
-    if r is not None and r.get("event") is not None and ent.jobs:  # the launch that wrote these planes ran on another stream: behind it, once
-        raw = _RAW_STREAM(owner.device.index) if _RAW_STREAM is not None else torch.cuda.current_stream(owner.device).cuda_stream
-        if raw != r["stream"].cuda_stream and r["waited"].get(raw) != r["id"]:
-            torch.cuda.current_stream(owner.device).wait_event(r["event"])
-            r["waited"][raw] = r["id"]
-    return ent.value
-
-
-def _plane_store(key, owner, value, jobs=None):
-    if len(_PLANES) > 4096:  # entries of models that are gone
-        for k in [k for k, v in _PLANES.items() if v.ref() is None]:
-            del _PLANES[k]
-    _PLANES[key] = _PlaneEntry(owner, value, jobs)
+_TABS = {}
 
 
 def _ktab(cin, kernel, h, w, ldi, device):
@@ -1356,61 +1132,12 @@ def _ktab(cin, kernel, h, w, ldi, device):
     return tab
 
 
-def _weight_planes(weight, transposed):
-    """(hi, lo, wscale) planes of a Conv3d weight in the kernel's [Cout, taps * Cin] order, cached until the optimizer
-    changes the tensor.  transposed: the dgrad filter W'[ci, co, flipped taps], as bf16 planes."""
-    from .fused_slowfast import split_planes
-    # keyed on the tensor that OWNS the storage: conv2d hands over `conv.weight.unsqueeze(2)`, a fresh view per call, which never
-    # hit the cache and left an entry per call behind (ADVICE r4); a view shares its base's version counter
-    owner = weight._base if weight._base is not None else weight
-    key = (id(owner), bool(transposed), tuple(weight.shape))
-    # (the entry remembers WHICH tensor it was made from: an id — like an address — can be reused after the first one died)
-    hit = _plane_lookup(key, owner)
-    if hit is not None:
-        return hit
-    jobs = None
-    with torch.no_grad():
-        w = weight.detach()
-        fast = (_PLANES_HIP and w.dtype == torch.float32 and w.dim() == 5 and w.shape[1] % 8 == 0 and w.shape[0] % 2 == 0 and
-                w.is_contiguous(memory_format=torch.channels_last_3d) and w.shape[2] * w.shape[3] * w.shape[4] <= 32)
-        if fast:  # two launches per convolution and step instead of ~35 torch ops (the memory of a channels-last weight is
-            #       already [cout][taps][cin], the kernels' K order)
-            cout, cin = w.shape[0], w.shape[1]
-            taps = w.shape[2] * w.shape[3] * w.shape[4]
-            rows = w.permute(0, 2, 3, 4, 1).reshape(cout, taps * cin)  # a view
-            if transposed:
-                sel = list(range(taps - 1, -1, -1))
-                planes = ops.weight_planes_t_f32(rows.view(cout, taps, cin), sel) + (None,)
-                jobs = [_job_transposed(rows, owner, planes[0], planes[1], cout, taps, cin, sel)]
-            else:
-                planes = ops.weight_planes_f32(rows, ops.X3_F16)
-                jobs = [_job_rows(rows, owner, planes[0], planes[1], planes[2], True, cout, taps * cin)]
-        else:
-            w = w.float()
-            if w.shape[1] % 8:  # the stems' 3 input channels, padded with zero taps
-                w = torch.cat([w, w.new_zeros((w.shape[0], 8 - w.shape[1] % 8) + tuple(w.shape[2:]))], 1)
-            if transposed:
-                w = w.flip(2, 3, 4).transpose(0, 1)
-            wt = w.permute(0, 2, 3, 4, 1).reshape(w.shape[0], -1)
-            if transposed:
-                hi, lo = split_planes(wt, ops.X3_BF16)
-                planes = (hi, lo, None)
-            else:  # fp16 planes: rows scaled by a power of two into [2^9, 2^10), undone on the accumulator (fused_slowfast.FusedConv)
-                mx = wt.abs().amax(dim=1).clamp_min(1e-30)
-                sc = torch.pow(2.0, 9.0 - torch.floor(torch.log2(mx)))
-                hi, lo = split_planes(wt * sc.view(-1, 1), ops.X3_F16)
-                planes = (hi, lo, (1.0 / sc).float().contiguous())
-    _plane_store(key, owner, planes, jobs)
-    return planes
-
-
 # ---- few-channel layers: g adjacent pixels along W as g * C channels (round 4; the inference path's group_weights_w in the training
 # step).  The fast pathway's 8-channel layers ran their forward / input gradient at 0.8-2.3 TB/s on the general tile (rows of 32
 # bytes, a 32-wide MFMA tile that is 3/4 padding); the same bytes viewed as [.., W / g, g * C] rows with block-Toeplitz weights along W
 # give 4 x fewer, 4 x fuller rows.  The weight gradient keeps the plain form (grouping would multiply its flops by g * g).
 _GROUP = 1
 _PW_F32 = 1         # pointwise layers (forward / stride-1 input gradient) on the streaming fp32-in / fp32-out kernel (csrc/pw_x3.hip)
-_GROUP_IDX = {}
 
 
 _PW_FORM = 0  # _conv_form's answer for the streaming pointwise kernel (1: the general tile, g > 1: g pixels grouped)
@@ -1436,65 +1163,6 @@ def _conv_form(cin, cout, kernel, stride, pad, w):
     while g > 1 and w % g:
         g //= 2
     return g
-
-
-_GROUP_MAPS = {}  # (shape, strides, g, transposed, device) -> int32 [rows, cols] storage offsets of the grouped rows (-1: a zero tap)
-_GROUP_GATHER = 1  # the grouped planes by ONE gather launch per weight (0: the torch assembly of round 4, for tests)
-
-
-def _grouped_rows(w, g, transposed):
-    """The pixel-grouped row form of a [cout, cin, kt, kh, kw] tensor (the weight itself, or — round 6 — the tensor of its storage
-    offsets): rows [(po, n)][(dt, dh, dg)][(pi, c)], block-Toeplitz along W over groups of g pixels; `pad` fills the taps no original
-    tap meets.  -> rows [g * co, kt * kh * kwg * g * ci], (kt, kh, kwg), rg."""
-    pad = 0 if w.is_floating_point() else -1
-    if transposed:
-        w = w.flip(2, 3, 4).transpose(0, 1)  # the input gradient as a convolution of dY: filter [cin][cout][flipped taps]
-    co, ci, kt, kh, kw = w.shape
-    r = kw // 2
-    rg = -(-r // g)
-    kwg = 1 + 2 * rg
-    ikey = (g, kw, str(w.device))
-    idx = _GROUP_IDX.get(ikey)
-    if idx is None:  # tap of the ORIGINAL filter that (output pixel po, input pixel pi, group tap dg) meets; kw = the zero tap
-        po, pi, dg = torch.meshgrid(torch.arange(g), torch.arange(g), torch.arange(kwg), indexing="ij")
-        dw = g * (dg - rg) + pi - po + r
-        idx = torch.where((dw >= 0) & (dw < kw), dw, torch.full_like(dw, kw)).to(w.device)
-        _GROUP_IDX[ikey] = idx
-    w_ext = torch.cat([w, w.new_full((co, ci, kt, kh, 1), pad)], 4)
-    wg = w_ext[..., idx]  # [co, ci, kt, kh, po, pi, dg]
-    rows = wg.permute(4, 0, 2, 3, 6, 5, 1).reshape(g * co, kt * kh * kwg * g * ci).contiguous()
-    return rows, (kt, kh, kwg), rg
-
-
-def _grouped_planes(weight, g, transposed, plane_dtype):
-    """Planes of the pixel-grouped form of a Conv3d weight (transposed: of the input gradient's filter W'[ci][flipped taps][co])
-    -> (hi, lo, wscale | None), (kt, kh, kwg), rg.  The grouped rows are a fixed GATHER of the weight's elements: the map of storage
-    offsets is built once per (shape, layout, g, direction) by running the assembly on the offsets themselves, and every step is one
-    launch (ops.weight_planes_gather_f32) instead of a flip, a cat, an index, a permute and a copy in front of the split."""
-    key = (id(weight), "group", g, bool(transposed))
-    hit = _plane_lookup(key, weight)
-    if hit is not None:
-        return hit
-    jobs = None
-    with torch.no_grad():
-        w = weight.detach()
-        dense = w.dtype == torch.float32 and (w.is_contiguous() or w.is_contiguous(memory_format=torch.channels_last_3d))
-        if _GROUP_GATHER and dense and w.is_cuda and w.numel() < (1 << 31):
-            mkey = (tuple(w.shape), tuple(w.stride()), g, bool(transposed), str(w.device))
-            ent = _GROUP_MAPS.get(mkey)
-            if ent is None:
-                offs = torch.arange(w.numel(), dtype=torch.int32).as_strided(tuple(w.shape), tuple(w.stride()))  # element -> storage offset
-                rows, kern, rg = _grouped_rows(offs, g, transposed)
-                ent = (rows.to(torch.int32).contiguous().to(w.device), kern, rg)
-                _GROUP_MAPS[mkey] = ent
-            pl = ops.weight_planes_gather_f32(w, ent[0], plane_dtype)
-            planes = (pl, ent[1], ent[2])
-            jobs = [_job_rows(w, weight, pl[0], pl[1], pl[2], plane_dtype == ops.X3_F16, ent[0].shape[0], ent[0].shape[1], idx_map=ent[0])]
-        else:
-            rows, kern, rg = _grouped_rows(w.float(), g, transposed)
-            planes = (ops.weight_planes_f32(rows, plane_dtype), kern, rg)
-    _plane_store(key, weight, planes, jobs)
-    return planes
 
 
 def _conv_planes(weight, transposed, cin, cout, kernel, stride, pad, w):
@@ -1713,20 +1381,6 @@ def _conv_dgrad(ctx, dy, dalias, x, weight, stride, padding, kernel, cin, cout):
     return dx
 
 
-def _stride_classes(k, s, p, x, y):
-    """One dimension of a strided convolution's input gradient: for every residue r of the input index mod s, the taps that
-    reach it (descending, so that the offsets into dY ascend), the padding in front of dY and the number of input positions
-    -> [(r, taps, pad_before, count)]; None when a class would need dY shifted the other way (not a SlowFast shape)."""
-    out = []
-    for r in range(s):
-        taps = list(range((r + p) % s, k, s))
-        offs = [(r + p - d) // s for d in taps]  # descending with d ascending
-        if offs and min(offs) > 0:
-            return None
-        out.append((r, taps[::-1], -min(offs) if offs else 0, max(0, -(-(x - r) // s))))
-    return out
-
-
 def _dgrad_strided(dy, weight, stride, padding, kernel, xshape):
     """Input gradient of a STRIDED convolution as convolutions of dY, one per residue class of the input position modulo the
     stride (a transposed convolution decomposed so that no zero is multiplied): class r gathers the taps d = (r + p) mod s,
@@ -1736,7 +1390,6 @@ def _dgrad_strided(dy, weight, stride, padding, kernel, xshape):
     1 ... 8 taps (seven of the projection's eight are zeros).  There frame i_t of a class is frame 2 i_t + r_t, which is the spatial
     remap over PAIRS of frames (2 h rows) as long as T is even — so odd extents (T = 5 and 3 at W = 20) are computed on a grid
     rounded up to even extents and cropped.  -> dx, or None outside that domain (the caller falls back to MIOpen)."""
-    from .fused_slowfast import split_planes
     b, cin, t, h, w = xshape
     cout = weight.shape[0]
     st, sh, sw = stride
@@ -1755,37 +1408,9 @@ def _dgrad_strided(dy, weight, stride, padding, kernel, xshape):
     to, ho, wo = dy.shape[2], dy.shape[3], dy.shape[4]
     if st > 1 and not cube and to * st != t:
         return None
-    key = (id(weight), "strided", tuple(stride), tuple(padding)) + (((t, h, w),) if cube else ())
-    classes = _plane_lookup(key, weight)
+    classes = weight_planes._strided_planes(weight, kernel, stride, padding, (t, h, w), (to, ho, wo))
     if classes is None:
-        per_dim = [_stride_classes(k, s_, p, x, y) for k, s_, p, x, y in zip(kernel, stride, padding, (t, h, w), (to, ho, wo))]
-        if any(c is None for c in per_dim):
-            return None
-        if cube and any(taps and n > y for c, y in zip(per_dim, (to, ho, wo)) for _, taps, _, n in c):
-            return None  # (a class longer than dY with its far-side taps: not a 3D-ResNet shape)
-        classes, jobs = [], []
-        with torch.no_grad():
-            wd = weight.detach()
-            fast = (_PLANES_HIP and wd.dtype == torch.float32 and wd.is_contiguous(memory_format=torch.channels_last_3d) and
-                    cout % 2 == 0)
-            wf = None if fast else wd.float()  # [cout, cin, kt, kh, kw]
-            w3 = wd.permute(0, 2, 3, 4, 1).reshape(cout, kernel[0] * kernel[1] * kernel[2], cin) if fast else None  # a view
-            for rt, dt, pbt, nt in per_dim[0]:
-                for rh, dh, pbh, nh in per_dim[1]:
-                    for rw, dw, pbw, nw in per_dim[2]:
-                        if not (dt and dh and dw):
-                            classes.append(((rt, rh, rw), None))
-                            continue
-                        if fast:  # one launch: the class's taps (row-major over its (dt, dh, dw) lists) gathered and transposed
-                            sel = [(a * kernel[1] + b_) * kernel[2] + c_ for a in dt for b_ in dh for c_ in dw]
-                            hi, lo = ops.weight_planes_t_f32(w3, sel)
-                            jobs.append(_job_transposed(w3, weight, hi, lo, cout, kernel[0] * kernel[1] * kernel[2], cin, sel))
-                        else:
-                            sub = wf[:, :, dt][:, :, :, dh][:, :, :, :, dw]                  # [cout, cin, |dt|, |dh|, |dw|]
-                            wt = sub.transpose(0, 1).permute(0, 2, 3, 4, 1).reshape(cin, -1)   # rows ci, K = (taps, co)
-                            hi, lo = split_planes(wt, ops.X3_BF16)
-                        classes.append(((rt, rh, rw), (hi, lo, (len(dt), len(dh), len(dw)), (pbt, pbh, pbw), (nt, nh, nw))))
-        _plane_store(key, weight, classes, jobs if fast else None)
+        return None
     dx = torch.empty((b, cin, t, h, w), dtype=torch.float32, device=dy.device, memory_format=torch.channels_last_3d)
     if any(c[1] is None for c in classes):  # classes no tap reaches (a 1x1x1 filter at stride 2: three of four) are zeros
         dx.zero_()
@@ -1834,7 +1459,6 @@ class _ConvX3Fork(torch.autograd.Function):
 # input rows once: the forward is the inference stem kernel (pixel-pair form, time-grouped for the 8-channel fast stem, fp16
 # planes) writing fp32, the weight gradient csrc/stem_train.hip (bf16 planes).  The clip is re-split into planes in each
 # direction (a 12-byte read and a 16-byte write per pixel) instead of kept: the saved tensor is the caller's clip itself.
-_STEM_IMAGES = {}
 
 
 def _stem_tgroup(cout, t):
@@ -1856,36 +1480,6 @@ def stem_patch_ok(x, conv):
             ops.stem_wgrad_x3_supported(h, w // 2, conv.out_channels, kt) and x.numel() // 3 * 16 < (1 << 32) - 64)
 
 
-def _stem_weight_image(weight, g):
-    """(hi, lo, wscale) of a stem weight [C, 3, kt, 7, 7] in the LDS image order of csrc/stem_conv.hip: pixel-pair taps
-    (column tap k -> pair tap (k + 1) // 2, pixel (k + 1) % 2; the first is a structural zero), g output frames as g * C
-    channels over kt + g - 1 frame taps, fp16 planes of rows scaled into [2^9, 2^10).  Cached until the tensor changes."""
-    from .fused_slowfast import split_planes, stem_lds_image
-    key = (id(weight), g)
-    hit = _STEM_IMAGES.get(key)
-    if hit is not None and hit[0]() is weight and hit[1] == weight._version:
-        return hit[2]
-    with torch.no_grad():
-        w = weight.detach().float()
-        c, _, kt = w.shape[0], w.shape[1], w.shape[2]
-        w8 = w.new_zeros((c, kt, 7, 8, 4))
-        w8[:, :, :, 1:, :3] = w.permute(0, 2, 3, 4, 1)
-        wg = w.new_zeros((g, c, kt + g - 1, 7, 8, 4))
-        for j in range(g):
-            wg[j, :, j : j + kt] = w8
-        wt = wg.reshape(g * c, -1)
-        mx = wt.abs().amax(dim=1).clamp_min(1e-30)
-        sc = torch.pow(2.0, 9.0 - torch.floor(torch.log2(mx)))
-        hi, lo = split_planes(wt * sc.view(-1, 1), ops.X3_F16)
-        fm = g == 4 and c == 8  # frame-major tiles: the kernel skips the frame taps a tile never meets
-        img = (stem_lds_image(hi, kt + g - 1, fm), stem_lds_image(lo, kt + g - 1, fm), (1.0 / sc).float().contiguous(), 2 if fm else 0)
-    if len(_STEM_IMAGES) > 64:
-        for k in [k for k, v in _STEM_IMAGES.items() if v[0]() is None]:
-            del _STEM_IMAGES[k]
-    _STEM_IMAGES[key] = (weakref.ref(weight), weight._version, img)
-    return img
-
-
 class _StemX3(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight):
@@ -1893,7 +1487,7 @@ class _StemX3(torch.autograd.Function):
         c, kt = weight.shape[0], weight.shape[2]
         g = _stem_tgroup(c, t)
         xh, xl = ops.clip_planes_f32(x, ops.X3_F16)
-        wh, wl, wscale, fpt = _stem_weight_image(weight, g)
+        wh, wl, wscale, fpt = weight_planes._stem_weight_image(weight, g)
         y = torch.empty((b, c, t, h // 2, w // 2), dtype=torch.float32, device=x.device, memory_format=torch.channels_last_3d)
         CALLS["conv_fwd_x3"] += 1
         CALLS["stem_fwd_patch"] += 1

@@ -855,7 +855,7 @@ def test_grouped_planes_by_one_gather_equal_the_torch_assembly(shape, g, transpo
     """Round 6: the pixel-grouped planes of a few-channel layer's weight (forward filter / input-gradient filter) by ONE launch —
     ops.weight_planes_gather_f32 through a cached map of storage offsets — are bit for bit what the torch assembly (flip, cat, index,
     permute, copy) + weight_planes_f32 produced, scales included; channels-last and contiguous weights."""
-    from avtex import ops, train_ops
+    from avtex import ops, train_ops, weight_planes
 
     dev = "cuda:0"
     torch.manual_seed(sum(shape) + g)
@@ -866,12 +866,12 @@ def test_grouped_planes_by_one_gather_equal_the_torch_assembly(shape, g, transpo
         pd = ops.X3_BF16 if transposed else ops.X3_F16
         out = []
         for flag in (1, 0):
-            keep, train_ops._GROUP_GATHER = train_ops._GROUP_GATHER, flag
+            keep, weight_planes._GROUP_GATHER = weight_planes._GROUP_GATHER, flag
             train_ops.invalidate_weight_cache(drop=True)
             try:
-                out.append(train_ops._grouped_planes(w, g, transposed, pd))
+                out.append(weight_planes._grouped_planes(w, g, transposed, pd))
             finally:
-                train_ops._GROUP_GATHER = keep
+                weight_planes._GROUP_GATHER = keep
         (pa, ka, ra), (pb, kb, rb) = out
         assert ka == kb and ra == rb
         for a, b in zip(pa, pb):
@@ -895,7 +895,7 @@ def test_stale_weight_planes_are_remade_by_one_launch_bit_for_bit():
     be, bit for bit and scale for scale, what the one-by-one launches produce from the same weights: plain rows (fp16, row-scaled),
     transposed + tap-selected (the input gradient's filters, stride 1 and the strided layers' residue classes) and the gathered rows of
     the pixel-grouped few-channel layers."""
-    from avtex import train_ops
+    from avtex import train_ops, weight_planes
     from avtex.slowfast import ResBlock
 
     dev = torch.device("cuda:0")
@@ -910,11 +910,11 @@ def test_stale_weight_planes_are_remade_by_one_launch_bit_for_bit():
             net(x).square().mean().backward()
 
     train_ops.invalidate_weight_cache(drop=True)
-    keep, train_ops._PLANES_MULTI = train_ops._PLANES_MULTI, 1
+    keep, weight_planes._PLANES_MULTI = weight_planes._PLANES_MULTI, 1
     try:
         fwd_bwd()                                    # every entry made one by one
         own = {id(p) for p in net.parameters()}
-        mine = {k: e for k, e in train_ops._PLANES.items() if e.ref() is not None and id(e.ref()) in own}
+        mine = {k: e for k, e in weight_planes.CACHE.entries.items() if e.ref() is not None and id(e.ref()) in own}
         kinds = sorted({j["fields"][4] for e in mine.values() if e.jobs for j in e.jobs})
         assert kinds == [0, 1, 2], kinds             # rows, transposed, gathered rows all occur in this net
         assert any(k[1] == "strided" and e.jobs for k, e in mine.items() if isinstance(k[1], str))
@@ -927,21 +927,21 @@ def test_stale_weight_planes_are_remade_by_one_launch_bit_for_bit():
         torch.cuda.synchronize()
         multi = {k: [t.clone() for t in _flat_tensors(e.value, [])] for k, e in mine.items() if e.jobs}
         assert all(not e.stale(e.ref()) for e in mine.values())
-        train_ops._PLANES_MULTI = 0
+        weight_planes._PLANES_MULTI = 0
         train_ops.invalidate_weight_cache(drop=True)
         fwd_bwd()                                    # the same weights, one launch per plane set
         torch.cuda.synchronize()
         assert train_ops.CALLS["planes_multi"] == n0 + 1
         checked = 0
         for k, ts in multi.items():
-            ref = _flat_tensors(train_ops._PLANES[k].value, [])
+            ref = _flat_tensors(weight_planes.CACHE.entries[k].value, [])
             assert len(ref) == len(ts)
             for a, b in zip(ts, ref):
                 assert a.dtype == b.dtype and a.shape == b.shape and torch.equal(a, b), k
                 checked += 1
         assert checked >= 2 * len(multi)
     finally:
-        train_ops._PLANES_MULTI = keep
+        weight_planes._PLANES_MULTI = keep
         train_ops.invalidate_weight_cache(drop=True)
 
 

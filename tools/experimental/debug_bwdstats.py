@@ -3,7 +3,7 @@ import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch, torch.nn as nn
 import avtex
-from avtex import train_ops, ops
+from avtex import train_ops, ops, weight_planes
 
 dev = "cuda:0"
 torch.manual_seed(0)
@@ -40,7 +40,7 @@ print("masked ref dy norm", float((res[0]["dy"] * mask).norm()), " fused dy vs m
 print("dx diff", float((res[1]["dx"] - res[0]["dx"]).norm()), "ref", float(res[0]["dx"].norm()))
 
 # direct kernel calls: the convolution of gy with the transposed filter, relu off / on
-planes = train_ops._weight_planes(conv.weight, True)
+planes = weight_planes._weight_planes(conv.weight, True)
 tab = train_ops._ktab(cout, kernel, h, w, cout, dev)
 save = None
 h_ = handle
