@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void l2norm_vec4(Src s, int64_t n, float eps, 
   }
   ss = avt::wave_sum(ss);
   const float nrm = __builtin_sqrtf((float)ss);
-  const float den = nrm > eps ? nrm : eps;
+  const float den = nrm < eps ? eps : nrm;  // clamp_min: a NaN norm stays NaN (the whole row is NaN, as F.normalize gives)
   auto emit = [&](int v, float4 a) {
     float4 o;
     o.x = __fdiv_rn(a.x, den);
@@ -106,7 +106,7 @@ __global__ __launch_bounds__(256) void l2norm_scalar(Src s, int64_t n, float eps
   }
   ss = avt::wave_sum(ss);
   const float nrm = __builtin_sqrtf((float)ss);
-  const float den = nrm > eps ? nrm : eps;
+  const float den = nrm < eps ? eps : nrm;  // clamp_min, NaN-propagating (see l2norm_vec4)
   for (int k = lane; k < d; k += 64) {
     const float o = __fdiv_rn(load1(s, row, k), den);
     const int64_t off = row * d + k;

@@ -3,9 +3,14 @@
 // (contrastive_video_textures/validate.py:524-572) and the target ordering of
 // validate.py:369-378, for all query rows in one launch.
 //
-// HBM-bound (nq*nt*4 B read once); one 256-thread workgroup per row.  The row's
-// p values live in LDS (rows up to 16384 entries) so the four passes
-// (sum -> p,max -> exp-sum,survivor-sum -> ordered compaction) touch HBM once.
+// HBM-bound; one workgroup per row.  Rows of up to 16384 entries live in
+// registers (256 or 1024 threads, 8 or 16 entries each): the row is read from
+// HBM once and the four passes (sum -> p,max -> exp-sum,survivor-sum -> ordered
+// compaction) run on registers.  row_transition accepts wider rows too, by a
+// 256-thread form that recomputes p from HBM / L2 in every pass; row_topk
+// refuses them.  The row maximum propagates NaN (torch.max does): one NaN p
+// makes row_max, and with it the cut, NaN, and then nothing is cut.  top-k never
+// picks a NaN score.
 // Reductions follow the canonical rounding of oracle/avt_oracle.c: sums in
 // fp64 rounded to fp32 once, every other step one correctly rounded fp32 op
 // (__fdiv_rn/__fmul_rn/... so the compiler cannot contract or reassociate).
@@ -16,7 +21,7 @@
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kMaxLds = 16384;  // row entries cached in LDS (64 KB)
+constexpr int kMaxReg = 16 * 1024;  // widest register-resident row: 1024 threads x 16 entries
 
 __device__ __forceinline__ int64_t target_len(int64_t q, int64_t n_seg) {
   const int64_t pos = q + 1 < n_seg - 1 ? q + 1 : n_seg - 1;
@@ -46,12 +51,19 @@ __device__ __forceinline__ double block_sum(double v, BlockRed& r) {
   __syncthreads();
   return (r.d[0] + r.d[1]) + (r.d[2] + r.d[3]);
 }
+// max that keeps a NaN from either side, as torch.max does (fmaxf drops it); the maximum of finite values is unchanged
+__device__ __forceinline__ float nan_max(float a, float b) { return (b > a || b != b) ? b : a; }
+__device__ __forceinline__ float wave_nan_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = nan_max(v, __shfl_xor(v, o, 64));
+  return v;
+}
 __device__ __forceinline__ float block_max(float v, BlockRed& r) {
-  v = avt::wave_max(v);
+  v = wave_nan_max(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) r.f[threadIdx.x >> 6] = v;
   __syncthreads();
-  return fmaxf(fmaxf(r.f[0], r.f[1]), fmaxf(r.f[2], r.f[3]));
+  return nan_max(nan_max(r.f[0], r.f[1]), nan_max(r.f[2], r.f[3]));
 }
 
 struct TArgs {
@@ -68,9 +80,8 @@ struct TArgs {
   float* stats;
 };
 
-template <bool CACHE>
+// rows wider than kMaxReg: p is recomputed from the scores in every pass
 __global__ __launch_bounds__(kThreads) void row_transition_kernel(TArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float pbuf[];  // CACHE: L floats
   __shared__ BlockRed red;
   __shared__ int s_base;
   const int64_t r = blockIdx.x;
@@ -102,16 +113,14 @@ __global__ __launch_bounds__(kThreads) void row_transition_kernel(TArgs a) {
     }
     return v;
   };
-  auto getp = [&](int64_t i) { return CACHE ? pbuf[i] : pval(i); };
+  auto getp = pval;
 
   // pass 2: p and its max
   float mx = -INFINITY;
   for (int64_t i = tid; i < L; i += kThreads) {
-    const float v = pval(i);
-    if (CACHE) pbuf[i] = v;
-    mx = fmaxf(mx, v);
+    mx = nan_max(mx, pval(i));
   }
-  mx = block_max(mx, red);  // (the barriers inside also publish pbuf)
+  mx = block_max(mx, red);
   const float p0 = getp(0);
 
   // pass 3: CE denominator (validate.py:531) and the survivors' sum (validate.py:554-558)
@@ -177,12 +186,12 @@ __global__ __launch_bounds__(kThreads) void row_transition_kernel(TArgs a) {
   }
 }
 
-// ---- fast path: rows of up to 256*ITEMS entries live in registers ---------------------------------------------
+// ---- rows of up to NTHR*ITEMS entries live in registers (every row up to kMaxReg) ------------------------------
 // Same arithmetic, same order of survivors; the row is read from HBM exactly once (coalesced: thread t owns
 // positions t, t+256, ...), every reduction is one shuffle tree + one LDS hop, and the ordered compaction needs a
 // single table of ITEMS x 4 ballot counts instead of one barrier round per 256 positions.
-// NTHR = 256: rows up to 4096 entries; NTHR = 1024 (16 waves): rows up to 16384 entries — config 4's N = 16384, where the
-// LDS-cached form below spent its time in 64 barrier rounds of compaction per row (0.4 TB/s).
+// NTHR = 256: rows up to 4096 entries; NTHR = 1024 (16 waves): rows up to 16384 entries — config 4's N = 16384, where a
+// 256-thread form spends its time in 64 barrier rounds of compaction per row (0.4 TB/s).
 template <int ITEMS, int NTHR = kThreads>
 __global__ __launch_bounds__(NTHR) void row_transition_reg_kernel(TArgs a) {
   constexpr int NWV = NTHR / 64;
@@ -204,13 +213,13 @@ __global__ __launch_bounds__(NTHR) void row_transition_reg_kernel(TArgs a) {
     return t;
   };
   auto bmax = [&](float v) {
-    v = avt::wave_max(v);
+    v = wave_nan_max(v);
     __syncthreads();
     if (lane == 0) red_f[wid] = v;
     __syncthreads();
     float t = red_f[0];
 #pragma unroll
-    for (int w = 1; w < NWV; ++w) t = fmaxf(t, red_f[w]);
+    for (int w = 1; w < NWV; ++w) t = nan_max(t, red_f[w]);
     return t;
   };
   const float* x = a.sim + (int64_t)r * a.ld;
@@ -256,7 +265,7 @@ __global__ __launch_bounds__(NTHR) void row_transition_reg_kernel(TArgs a) {
     float p = __fdiv_rn(v[k], sf);
     if (xa) p = __fadd_rn(__fmul_rn(a.af, p), __fmul_rn(a.bf, __fdiv_rn(va[k], saf)));
     v[k] = p;
-    if (i < L) mx = fmaxf(mx, p);
+    if (i < L) mx = nan_max(mx, p);
   }
   mx = bmax(mx);
   const float cut = __fsub_rn(mx, __fmul_rn(a.threshold, mx));
@@ -377,61 +386,11 @@ struct KArgs {
   float* top_val;
 };
 
-__global__ __launch_bounds__(kThreads) void row_topk_kernel(KArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float row[];  // nt floats
-  __shared__ float s_v[kThreads / 64];
-  __shared__ int s_i[kThreads / 64];
-  const int64_t r = blockIdx.x;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const float* x = a.sim + r * a.ld;
-  const int64_t self = a.self_col ? a.self_col[r] : -1;
-  // taken / excluded entries are marked NaN so that a genuine -inf score can still be picked once
-  for (int64_t j = tid; j < a.nt; j += kThreads) row[j] = (j == self) ? __builtin_nanf("") : x[j];
-  __syncthreads();
-  for (int s = 0; s < a.k; ++s) {
-    float bv = -INFINITY;
-    int bi = -1;
-    for (int64_t j = tid; j < a.nt; j += kThreads) {
-      const float v = row[j];
-      if (v == v && (bi < 0 || v > bv)) {  // strided ascending j: first max kept -> lowest column on ties
-        bv = v;
-        bi = (int)j;
-      }
-    }
-    // reduce (value desc, index asc); bi < 0 means "nothing left"
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(bv, o, 64);
-      const int oi = __shfl_xor(bi, o, 64);
-      if (oi >= 0 && (bi < 0 || ov > bv || (ov == bv && oi < bi))) {
-        bv = ov;
-        bi = oi;
-      }
-    }
-    if (lane == 0) {
-      s_v[wid] = bv;
-      s_i[wid] = bi;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      float fv = s_v[0];
-      int fi = s_i[0];
-      for (int w = 1; w < kThreads / 64; ++w)
-        if (s_i[w] >= 0 && (fi < 0 || s_v[w] > fv || (s_v[w] == fv && s_i[w] < fi))) {
-          fv = s_v[w];
-          fi = s_i[w];
-        }
-      a.top_idx[r * (int64_t)a.k + s] = fi;
-      a.top_val[r * (int64_t)a.k + s] = fi >= 0 ? fv : -INFINITY;
-      if (fi >= 0) row[fi] = __builtin_nanf("");
-    }
-    __syncthreads();
-  }
-}
-
 // Register-resident top-k: thread t holds positions t, t + NTHR, ... (the row is read from HBM once, coalesced); a round is a
 // per-thread scan of its ITEMS registers + one shuffle tree + one LDS hop, the winner's owner marks its register taken.
-// Same order as the LDS form: value descending, lowest column on ties; excluded / taken entries are NaN.
+// Order: value descending, lowest column on ties.  Excluded and taken entries are marked NaN, so that a genuine -inf score
+// can still be picked once; a NaN score is therefore never picked, and when fewer than k entries can be picked the tail is
+// index -1 / value -inf.
 template <int ITEMS, int NTHR>
 __global__ __launch_bounds__(NTHR) void row_topk_reg_kernel(KArgs a) {
   constexpr int NWV = NTHR / 64;
@@ -537,10 +496,8 @@ extern "C" int avt_row_transition(const float* sim, int64_t nq, int64_t nt, int6
     hipLaunchKernelGGL((row_transition_reg_kernel<8, 1024>), grid, dim3(1024), 0, st, a);
   else if (nt <= 16 * 1024)
     hipLaunchKernelGGL((row_transition_reg_kernel<16, 1024>), grid, dim3(1024), 0, st, a);
-  else if (nt <= kMaxLds)
-    hipLaunchKernelGGL(row_transition_kernel<true>, grid, block, (size_t)nt * sizeof(float), st, a);
   else
-    hipLaunchKernelGGL(row_transition_kernel<false>, grid, block, 0, st, a);
+    hipLaunchKernelGGL(row_transition_kernel, grid, block, 0, st, a);
   return avt::check_launch("avt_row_transition");
 }
 
@@ -549,22 +506,16 @@ extern "C" int avt_row_topk(const float* sim, int64_t nq, int64_t nt, int64_t ld
   AVT_REQUIRE(nq >= 0 && nt > 0 && ld >= nt && k > 0, "avt_row_topk: bad sizes");
   if (nq == 0) return AVT_OK;
   AVT_REQUIRE(sim && top_idx && top_val, "avt_row_topk: NULL pointer");
-  if (nt > kMaxLds) {
-    avt::set_error("avt_row_topk: nt=%lld exceeds the LDS-resident row limit %d", (long long)nt, kMaxLds);
+  if (nt > kMaxReg) {
+    avt::set_error("avt_row_topk: nt=%lld exceeds the register-resident row limit %d", (long long)nt, kMaxReg);
     return AVT_ERR_UNSUPPORTED;
   }
   if (nq == 0) return AVT_OK;
   KArgs a{sim, self_col, nq, nt, ld, k, top_idx, top_val};
   hipStream_t st_ = static_cast<hipStream_t>(stream);
-  if (nt <= 16 * 256) {  // register-resident forms up to 16384-wide rows, the LDS-resident form beyond
+  if (nt <= 16 * 256)
     hipLaunchKernelGGL((row_topk_reg_kernel<16, 256>), dim3((unsigned)nq), dim3(256), 0, st_, a);
-    return avt::check_launch("avt_row_topk");
-  }
-  if (nt <= 16 * 1024) {
+  else
     hipLaunchKernelGGL((row_topk_reg_kernel<16, 1024>), dim3((unsigned)nq), dim3(1024), 0, st_, a);
-    return avt::check_launch("avt_row_topk");
-  }
-  hipLaunchKernelGGL(row_topk_kernel, dim3((unsigned)nq), dim3(kThreads), (size_t)nt * sizeof(float),
-                     static_cast<hipStream_t>(stream), a);
   return avt::check_launch("avt_row_topk");
 }

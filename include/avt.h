@@ -110,6 +110,10 @@ int avt_clip_pack_u8_ndhwc4(const uint8_t* frames, int n_frames, int height,
  *   fp32 once (canonical; see oracle/avt_oracle.c).  Outputs (each optional):
  *   y_f32 [n, d0+d1] fp32; y_hi / y_lo [n, d0+d1] bf16 with
  *   hi = bf16_rne(y), lo = bf16_rne(y - hi).
+ *   max(., eps) is F.normalize's clamp_min: a norm below eps becomes eps, a NaN
+ *   norm stays NaN.  A row that holds a NaN is therefore NaN throughout; a row
+ *   that holds an inf (or whose sum of squares passes the fp32 range) has norm
+ *   inf: zeros, and NaN where the entry itself is inf.
  * ---------------------------------------------------------------------- */
 int avt_l2norm_rows(const float* x0, int d0, const float* x1, int d1, int64_t n,
                     float eps, float* y_f32, void* y_hi, void* y_lo,
@@ -158,6 +162,10 @@ int avt_gemm_nt_x3_f32out(const void* a_hi, const void* a_lo, int lda, const voi
  *   sim_a (optional, same layout) is the driving-audio row (validate.py:525-527).
  *   cap = capacity of surv_* per row; surv_cnt[r] is the true count even if it
  *   exceeds cap.  stats (optional) [nq,4] = {row_sum, row_max, ce, entropy}.
+ *   Slots past min(cnt, cap) are left as the caller filled them; with cap == 0
+ *   the three surv_* pointers may be NULL.  max(p) propagates NaN as torch's
+ *   does: if any p is NaN (a NaN or inf score, a row sum of zero), row_max and
+ *   the cut are NaN, nothing is cut, and every nonzero p (NaN included) survives.
  * ---------------------------------------------------------------------- */
 int avt_row_transition(const float* sim, int64_t nq, int64_t nt, int64_t ld,
                        const int64_t* q_ids, int64_t n_seg, const float* sim_a,
@@ -167,7 +175,9 @@ int avt_row_transition(const float* sim, int64_t nq, int64_t nt, int64_t ld,
 
 /* top-k select used by the sharded N=16384 configuration: per row the k
  * largest scores (ties: lower column first), descending.  self_col (optional)
- * [nq] is a column to exclude (the query itself). */
+ * [nq] is a column to exclude (the query itself).  A NaN score is never picked;
+ * -inf is a score like any other.  When fewer than k columns can be picked the
+ * tail is top_idx = -1, top_val = -inf.  nt <= 16384 (AVT_ERR_UNSUPPORTED beyond). */
 int avt_row_topk(const float* sim, int64_t nq, int64_t nt, int64_t ld,
                  const int64_t* self_col, int k, int32_t* top_idx,
                  float* top_val, void* stream);

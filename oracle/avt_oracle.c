@@ -80,7 +80,7 @@ void avt_oracle_l2norm_rows(const float* x0, int d0, const float* x1, int d1,
     for (int k = 0; k < d0; ++k) ss += (double)a[k] * (double)a[k];
     for (int k = 0; k < d1; ++k) ss += (double)b[k] * (double)b[k];
     float nrm = sqrtf((float)ss);
-    float den = nrm > eps ? nrm : eps;
+    float den = nrm < eps ? eps : nrm; /* clamp_min: a NaN norm gives a NaN row, as F.normalize does */
     for (int k = 0; k < d; ++k) {
       float v = (k < d0 ? a[k] : b[k - d0]) / den;
       if (y_f32) y_f32[r * (int64_t)d + k] = v;
@@ -275,8 +275,9 @@ void avt_oracle_row_transition(const float* sim, int64_t nq, int64_t nt,
       p[i] = v;
     }
     /* validate.py:531 CrossEntropyLoss(output, label 0) — reporting only */
+    /* output.max() propagates NaN: one NaN p makes the maximum, and with it the cut of :554, NaN */
     float mx = p[0];
-    for (int64_t i = 1; i < L; ++i) mx = p[i] > mx ? p[i] : mx;
+    for (int64_t i = 1; i < L; ++i) mx = (p[i] > mx || p[i] != p[i]) ? p[i] : mx;
     double se = 0.0;
     for (int64_t i = 0; i < L; ++i) se += exp((double)p[i] - (double)mx);
     const float ce = (float)((double)mx + log(se) - (double)p[0]);
@@ -328,8 +329,8 @@ void avt_oracle_row_topk(const float* sim, int64_t nq, int64_t nt, int64_t ld,
     if (self_col && self_col[r] >= 0 && self_col[r] < nt) used[self_col[r]] = 1;
     for (int s = 0; s < k; ++s) {
       int64_t best = -1;
-      for (int64_t j = 0; j < nt; ++j)
-        if (!used[j] && (best < 0 || x[j] > x[best])) best = j;
+      for (int64_t j = 0; j < nt; ++j) /* a NaN score is never picked (x[j] == x[j]); the lowest column wins a tie */
+        if (!used[j] && x[j] == x[j] && (best < 0 || x[j] > x[best])) best = j;
       if (best >= 0) used[best] = 1;
       top_idx[r * (int64_t)k + s] = (int32_t)best;
       top_val[r * (int64_t)k + s] = best >= 0 ? x[best] : -INFINITY;
