@@ -6,7 +6,12 @@
 namespace avt {
 
 // fp32 pair -> packed (hi, lo) planes, both round-to-nearest-even; x - hi is exact in fp32.
-// F16 = false: bf16 planes (8 + 8 significant bits, |x - hi - lo| <= 2^-16 |x| at every magnitude; 2^-17 observed).
+// F16 = false: bf16 planes (8 + 8 significant bits, |x - hi - lo| <= max(2^-16 |x|, 2^-134); 2^-17 |x| observed).  The two ends of
+//              fp32's range, stated here because the edge tests met them (tests/weight_planes_refs.py; the arithmetic is as it was):
+//              lo is a bf16 DENORMAL of step 2^-133 once x - hi is below 2^-126, so the error is then absolute, at most half a
+//              step, and an fp32 denormal below 2^-134 splits into (0, 0); and a finite |x| above 0x7f7f7fff (the largest fp32
+//              that rounds to a finite bf16; FLT_MAX is above it) has hi = +-inf and lo = x - hi = -+inf, a pair that joins to a
+//              NaN.  No weight, clip or gradient of a run that is not already lost is near either end.
 // F16 = true : fp16 planes (11 + 11 bits, <= 2^-22 |x| while lo stays a normal fp16, i.e. |x| >= 2^-3; below that the
 //              ABSOLUTE error is <= 2^-24) — FINITE values are clamped to the fp16 range first (65504); a NaN stays a NaN
 //              and an infinity stays that infinity (hi = +-inf, lo = 0), so a poisoned or diverged activation still

@@ -190,9 +190,12 @@ except ImportError:  # (torch < 2.0: callers invalidate by hand, as train() alwa
 
 def _row_scaled_planes(wt):
     """fp16 planes of rows scaled by a power of two into [2^9, 2^10), undone on the accumulator (fused_slowfast.FusedConv)
-    -> hi, lo, the scales."""
-    mx = wt.abs().amax(dim=1).clamp_min(1e-30)
-    sc = torch.pow(2.0, 9.0 - torch.floor(torch.log2(mx)))
+    -> hi, lo, the scales.  The bits of csrc/stem_train.hip's weight_planes_row: the maximum skips NaNs (fmaxf), its exponent comes from
+    frexp — mx = m * 2^e, m in [0.5, 1), scale 2^(10 - e), assembled as the fp32 word (127 + 10 - e) << 23: exact on every device.
+    (2^(9 - floor(log2(mx))) was half of it for a maximum one ulp below a power of two, where fp32 log2 rounds up to the integer; an
+    infinity, whose frexp exponent is 0 here as on the device, made the scale 0 and the row NaNs; a NaN made the whole row NaNs.)"""
+    mx = wt.abs().nan_to_num_(nan=0.0, posinf=float("inf")).amax(dim=1).clamp_min(1e-30)
+    sc = (137 - torch.frexp(mx)[1]).to(torch.int32).bitwise_left_shift_(23).view(torch.float32)
     hi, lo = split_planes(wt * sc.view(-1, 1), ops.X3_F16)
     return hi, lo, sc
 

@@ -761,7 +761,12 @@ int64_t avt_stem_wgrad_x3_det_launches(int kt, int co);
 /* The planes conv_x3 reads, from a training convolution's fp32 weight (re-made after every optimizer step; csrc/stem_train.hip).
  * avt_weight_planes_f32: w [cout][k] fp32 (a channels-last Conv3d weight: k = taps * cin) -> hi / lo [cout][k]; fp16 planes
  *   (plane_dtype 1) are scaled per row by a power of two into [2^9, 2^10) and wscale [cout] receives 1 / scale; bf16 planes
- *   (plane_dtype 0) are unscaled and wscale must be NULL.
+ *   (plane_dtype 0) are unscaled and wscale must be NULL.  The row's maximum is taken over its non-NaN entries, at least 1e-30f, as
+ *   m * 2^e with m in [0.5, 1) (frexpf): scale = 2^(10 - e), wscale = 2^(e - 10), both exact; a NaN stays a NaN at its place only.
+ *   A row that holds an INFINITY (observed on gfx950, tests/test_gpu_weight_planes_edges.py): frexpf of the infinite maximum gives
+ *   e = 0, so wscale = 2^-10 whatever else the row holds; the infinity comes back as that infinity, and the row's finite entries are
+ *   scaled by 2^10 — those of 64 and more clamp at fp16's 65504 and come back as 63.97 (of either sign), those below keep the two roundings'
+ *   max(2^-22 |w|, 2^-35), and nothing finite turns into an infinity or a NaN.  The other rows are not affected.
  * avt_weight_planes_t_f32: the input gradient's filter: hi / lo [cin][nsel][cout] bf16 planes with
  *   out[ci][a][co] = w[co][sel[a]][ci] (sel = HOST array of nsel <= 32 source taps: all taps reversed for a stride-1 layer,
  *   one residue class's taps for a strided one, train_ops._dgrad_strided). */

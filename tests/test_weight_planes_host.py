@@ -18,11 +18,10 @@ def wp(avt):
 
 
 def _row_scaled(rows):
-    from avtex import ops
-    from avtex.fused_slowfast import split_planes
+    import weight_planes_refs as R  # the numpy reference of the kernel's rows (frexp's exponent), not a second copy of the package's formula
 
-    sc = torch.pow(2.0, 9.0 - torch.floor(torch.log2(rows.abs().amax(dim=1).clamp_min(1e-30))))
-    return split_planes(rows * sc.view(-1, 1), ops.X3_F16) + (1.0 / sc,)
+    hi, lo, wscale = R.rows_ref(rows.detach().numpy(), R.F16)
+    return R.plane_tensor(hi), R.plane_tensor(lo), torch.from_numpy(wscale)
 
 
 def _plain_ref(w, transposed):
